@@ -12,9 +12,15 @@ configs[2] / configs[3] under the same contract and emit the same objects.
 Multi-GPU: one process per GPU (torch.distributed.run), triplets sharded embarrassingly, weights packed on rank 0
 and broadcast once over RCCL; no steady-state collective => "scaling": "weak" (B triplets per GPU).
 
-At N = 1 the default run also times BASELINE.json configs[2] (ResNet-50-128d truncated contrastive, B=64, 'norelu') and configs[3]
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, runs the W warm-up and the K timed steps, checks the last step's
+maps (finite, non-negative, unit sum, compiled epilogues only), writes them with --dump-outputs DIR, and prints its line.
+Everything else the benchmark measures runs only with --full:
+
+At N = 1 a --full run also times BASELINE.json configs[2] (ResNet-50-128d truncated contrastive, B=64, 'norelu') and configs[3]
 (Light-CNN-29v2 EBP, B=128, 'affineonly') for a few steps each and appends them as `"secondary": [...]` (--no-secondary skips them;
-absent at N > 1 and when --model selects one of them as the main workload).
+absent at N > 1 and when --model selects one of them as the main workload).  It also compares sample 0 with the reference's map,
+and adds the roofline, the idle-queue enqueue cost, one-triplet latency, the sustained loop, the uint8 end-to-end step, the other
+split-GEMM modes and the CPU baseline (each of them can be left out with its --no-* option).
 
 Prints ONE JSON line on rank 0.  The `roofline` object describes the TIMED schedule: `achieved` is the algorithmic FLOPs over
 the union of the GEMM launches' busy intervals, taken from timestamps the kernels themselves record while the step runs on its
@@ -513,6 +519,24 @@ def timed_loop(W, steps, warmup, barrier, world, dev, comm=None):
     return {'dt': dt, 'dt_rank': dt_rank, 't_enqueue': t_enqueue, 'sal': sal, 'ok': ok, 'chain': cs}
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000 - 4096      # 64 MB in all, the .npy headers included
+
+
+def dump_outputs(out_dir, sal):
+    """--dump-outputs DIR: the maps the timed path returned in its last step, as DIR/saliency.npy (float32, [B, H, W]).  Above 64 MB, a fixed
+    seeded sample of whole maps instead, their row numbers in DIR/saliency_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    maps = sal.detach().float().cpu().numpy()
+    if maps.nbytes > DUMP_LIMIT_BYTES:
+        per_map = maps[0].nbytes
+        keep = max(1, (DUMP_LIMIT_BYTES - 8 * maps.shape[0]) // per_map)
+        rows = np.sort(np.random.RandomState(0).choice(maps.shape[0], keep, replace=False))
+        maps = maps[rows]
+        np.save(os.path.join(out_dir, 'saliency_rows.npy'), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, 'saliency.npy'), np.ascontiguousarray(maps, dtype=np.float32))
+
+
 def executed_flops(W, reps=2):
     """(GEMM ms, launches, executed GEMM FLOPs) per step of the one-stream schedule: HIP events around every launch."""
     eng = W.eng
@@ -798,6 +822,9 @@ def main():
     ap.add_argument('--mode', default=None)
     ap.add_argument('--model', default='resnet101', choices=['resnet101', 'resnet50_128', 'lightcnn'],
                     help='resnet101 = the BASELINE.json headline; the other two are its secondary configurations')
+    ap.add_argument('--full', action='store_true', help='everything beyond the timed steps: reference check of sample 0, roofline, latency, sustained loop, uint8 '
+                                                         'step, split-GEMM modes, secondary configurations, CPU baseline (the --no-* options below trim it)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write the maps of the last timed step as DIR/saliency.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-whole-host', action='store_true', help='cpu_baseline without the P-process whole-host figure')
     ap.add_argument('--no-secondary', action='store_true', help='N = 1, --model resnet101: do not append the ResNet-50-128d / Light-CNN lines')
@@ -825,6 +852,8 @@ def main():
     ap.add_argument('--cpu-worker-seconds', type=float, default=20.0, help=argparse.SUPPRESS)
     ap.add_argument('--cpu-worker-threads', type=int, default=16, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if (args.launch_log_out or args.timeline_json) and not args.full:
+        ap.error('--launch-log-out and --timeline-json describe the roofline object: they need --full')
     if args.cpu_worker:
         return cpu_worker_main(args.model, args.cpu_worker_seconds, args.cpu_worker_threads, args.batch, args.mode)
 
@@ -932,8 +961,11 @@ def run(args, comm):
     ok = ok and (chain_timed[1] == 0 or args.fusion is not None)
     # per-rank rates: a straggler shows up as `spread` (the whole-job value below uses the MAX-over-ranks time)
     rank_rates = shard.gather_rank_rates(B * args.steps / r['dt_rank'], dev, comm)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sal)     # before any further step can reuse the engine's output buffers
+    full = args.full
     row0 = None
-    if rank == 0 and W.fixture:
+    if full and rank == 0 and W.fixture:
         row0 = fixture_cosine(sal[0], W.fixture)
         ok = ok and row0 is not None and row0 >= ROW0_COS
     if args.serial:
@@ -943,19 +975,21 @@ def run(args, comm):
             _tuning.record_launch_log(step, 3, dev, args.launch_log_csv)
         eng.set_profile(False)
     # host cost of enqueueing one step on an EMPTY queue (no back-pressure from a full HIP queue): median of 5
-    idle = []
-    for _ in range(5):
+    host_idle_ms = None
+    if full:
+        idle = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step()
+            idle.append(time.perf_counter() - t1)
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step()
-        idle.append(time.perf_counter() - t1)
-    torch.cuda.synchronize()
-    host_idle_ms = 1e3 * sorted(idle)[2]
-    one_lat = one_triplet_latency(W) if (rank == 0 and world == 1 and not args.serial) else None
+        host_idle_ms = 1e3 * sorted(idle)[2]
+    one_lat = one_triplet_latency(W) if (full and rank == 0 and world == 1 and not args.serial) else None
     # sustained loop outside the timed region (the K timed steps take well under a second): long enough for an external
     # power / utilisation sampler to see the device busy, and a steady-state (thermally settled) rate
     sustained = None
-    if not args.no_sustained:
+    if full and not args.no_sustained:
         n_sus = 0
         t1 = time.perf_counter()
         while time.perf_counter() - t1 < args.sustained_seconds:
@@ -967,7 +1001,7 @@ def run(args, comm):
 
     # the same step with uint8 inputs arriving from pinned host memory: H2D copy and preprocessing inside the timed region (never `value`)
     u8_e2e = None
-    if rank == 0 and world == 1 and getattr(W, 'u8_step', None) is not None and not args.serial:
+    if full and rank == 0 and world == 1 and getattr(W, 'u8_step', None) is not None and not args.serial:
         for _ in range(3):
             s8 = W.u8_step()
         torch.cuda.synchronize()
@@ -985,7 +1019,7 @@ def run(args, comm):
     roof = None
     unfused_leg = None
     ms_step = 1e3 * dt / args.steps
-    if not args.no_profile and rank == 0:
+    if full and not args.no_profile and rank == 0:
         reps = 2
         roof, tl, alg_step = roofline_object(W, step, ms_step, dev, reps=reps, launch_log_out=args.launch_log_out)
         if args.timeline_json:
@@ -1012,7 +1046,7 @@ def run(args, comm):
     # AND the sweep's backward-data GEMMs of the deep-K layers as bf16x6 on the bf16 matrix pipe).  mode 0: fp32 MFMA kernels everywhere.  mode 1: the forward
     # convolutions only (the round-5 default).  Same output checks as the headline.
     split_leg = None
-    if rank == 0 and world == 1 and not args.serial and args.split_gemm is None and not args.no_split_leg:
+    if full and rank == 0 and world == 1 and not args.serial and args.split_gemm is None and not args.no_split_leg:
         split_leg = {}
         for name, mode in (('fp32_mfma_only', 0), ('bf16x6_forward_only', 1)):
             try:
@@ -1030,7 +1064,7 @@ def run(args, comm):
                 eng.set_split_gemm(3)
 
     secondary = None
-    if rank == 0 and world == 1 and args.model == 'resnet101' and not args.no_secondary and not args.serial and args.batch is None and args.mode is None:
+    if full and rank == 0 and world == 1 and args.model == 'resnet101' and not args.no_secondary and not args.serial and args.batch is None and args.mode is None:
         # BASELINE.json configs[2] and configs[3] on the same line (the driver only runs the default command)
         chain_main = chain_stats()
         eng.close()
@@ -1063,7 +1097,7 @@ def run(args, comm):
                        'parallelism': 'independent triplets, %d process(es), weights broadcast once' % world},
             'outputs_ok': ok, 'row0_cosine_vs_reference': row0,
             # host time per step while the queue is full (back-pressure included) and on an empty queue (the true launch cost)
-            'host_enqueue_ms_per_step': 1e3 * t_enqueue / args.steps, 'host_enqueue_idle_ms': host_idle_ms,
+            'host_enqueue_ms_per_step': 1e3 * t_enqueue / args.steps,
             'rank_maps_s': rank_rates,
             'ranks': ranks,
             # how the parameters reached the ranks: 'broadcast' (one RCCL broadcast of the packed arena), 'local_pack_fallback' (the collective
@@ -1076,6 +1110,8 @@ def run(args, comm):
         line['launcher'] = os.environ.get('XFR_LAUNCHER', 'external (torch.distributed.run or the caller\'s environment)' if world > 1 else 'none (one process)')
         if world > 1:
             line['scaling_note'] = 'N > 1 has only ever run with several ranks on ONE GPU here (gloo); no multi-GPU node was available to the builder: no multi-GPU hardware number exists'
+        if host_idle_ms is not None:
+            line['host_enqueue_idle_ms'] = host_idle_ms
         if u8_e2e is not None:
             line['u8_end_to_end'] = u8_e2e
         if one_lat is not None:
@@ -1092,7 +1128,7 @@ def run(args, comm):
             line['roofline'] = roof
         if secondary is not None:
             line['secondary'] = secondary
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = W.cpu_baseline(20.0, not args.no_whole_host)
         print(json.dumps(line))
         sys.stdout.flush()

@@ -34,10 +34,10 @@ for spec in $SPECS; do
   # the same launches timed by the kernels themselves (first GEMM of a step included correctly)
   python profiles/layer_table.py $D/launchlog$T.csv > $P/gemm_layers_inkernel$T.txt
   # the plain bench line (timed three-stream schedule, launch-log roofline, clock, CPU baseline) + the timeline it came from
-  $B --no-secondary --timeline-json $P/gemm_timeline$T.json --launch-log-out $P/launch_log$T.csv > $P/bench_default$T.json 2> $D/bench_default$T.err
+  $B --full --no-secondary --timeline-json $P/gemm_timeline$T.json --launch-log-out $P/launch_log$T.csv > $P/bench_default$T.json 2> $D/bench_default$T.err
 done
 if [ -n "${2:-}" ]; then
-  python bench.py > $P/bench_driver_line.json 2> $D/bench_driver_line.err
+  python bench.py --full > $P/bench_driver_line.json 2> $D/bench_driver_line.err
   mkdir -p gpurun_out/$P && cp -r $P/. gpurun_out/$P/
   echo "collected ($SPECS): $(ls $P | tr '\n' ' ')"
   exit 0
@@ -50,7 +50,7 @@ rm -f $D/pipelined/${R}_kernel_trace.csv
 # on three streams (the chip at its power limit); the in-kernel clock measurements next to them
 smi() { while true; do date +%s.%N; rocm-smi --showclocks --showpower 2>/dev/null | grep -E "sclk|Power|power" ; sleep 1; done; }
 smi > $P/smi_bench_sustained.txt & SMI=$!
-python bench.py --no-cpu-baseline --no-profile --sustained-seconds 15 > /dev/null 2>&1
+python bench.py --full --no-cpu-baseline --no-profile --sustained-seconds 15 > /dev/null 2>&1
 kill $SMI; wait $SMI 2>/dev/null
 smi > $P/smi_gemm_saturated.txt & SMI=$!
 python tools/conv_sweep.py --cfgs 3000007,3000004 --reps 30000 --only 0 --clock > $P/gemm_saturated.txt 2>&1
@@ -63,7 +63,7 @@ python tools/clock_probe.py --steps 10 --serial > $P/clock_probe_serial.json 2> 
 python tools/phase_probe.py 2> /dev/null | grep -v amdgpu > $P/phase_probe_timed.txt
 python tools/phase_probe.py --serial 2> /dev/null | grep -v amdgpu > $P/phase_probe_serial.txt
 python tools/pair_probe.py 2> /dev/null | grep -v amdgpu > $P/pair_probe.txt
-for b in 32 64 96; do python bench.py --batch $b --steps 20 --warmup 4 --no-cpu-baseline --no-sustained --no-secondary 2> /dev/null; done > $P/bench_batch_sweep.jsonl
+for b in 32 64 96; do python bench.py --full --batch $b --steps 20 --warmup 4 --no-cpu-baseline --no-sustained --no-secondary 2> /dev/null; done > $P/bench_batch_sweep.jsonl
 python tools/embeddings_sweep.py --masks 6500 > $P/embeddings_sweep.json 2> /dev/null
 python tools/embeddings_sweep.py --masks 6500 --no-split > $P/embeddings_sweep_nosplit.json 2> /dev/null
 # round 5: the raw launch log of the timed schedule -> frac, recomputed without repo code; the lean schedule against the literal one on this box;
@@ -76,7 +76,7 @@ done; done; done > $P/lean_ab.txt
 # bf16x6 modes (xfr_engine_set_split_gemm; 3 = the default since round 6: forward convolutions and backward-data GEMMs) on this box, alternating; GEMM
 # error of the kernels against float64
 for rep in 1 2; do for m in resnet101 resnet50_128; do for f in "--split-gemm 0" "--split-gemm 1" ""; do
-  python bench.py --model $m $f --no-split-leg --no-cpu-baseline --no-secondary --no-sustained --no-profile --steps 20 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$m [$f]', round(d['value'],1), 'maps/s', round(d['ms_per_step'],3), 'ms', 'outputs_ok', d['outputs_ok'], '1-cos(row 0)', 1-d['row0_cosine_vs_reference'])"
+  python bench.py --full --model $m $f --no-split-leg --no-cpu-baseline --no-secondary --no-sustained --no-profile --steps 20 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$m [$f]', round(d['value'],1), 'maps/s', round(d['ms_per_step'],3), 'ms', 'outputs_ok', d['outputs_ok'], '1-cos(row 0)', 1-d['row0_cosine_vs_reference'])"
 done; done; done > $P/split_gemm_ab.txt
 python tools/conv_error_probe.py --extra 2> /dev/null | grep -v amdgpu > $P/conv_error_probe.txt
 python tools/conv_sweep.py --cfgs 7,4,9 --reps 200 --only 0,1,3,4,10 2> /dev/null | grep -v amdgpu > $P/conv_sweep_bf16x6.txt
@@ -89,7 +89,7 @@ rocprofv3 $ST -d $D/subtree -o $R -- python tools/subtree_probe.py --reps 5 > /d
 cp $D/subtree/${R}_kernel_stats.csv $P/kernel_stats_weighted_subtree.csv
 rm -f $D/subtree/${R}_kernel_trace.csv
 # the line the driver sees: the default command, secondary configurations and whole-host CPU figure included
-python bench.py > $P/bench_driver_line.json 2> $D/bench_driver_line.err
+python bench.py --full > $P/bench_driver_line.json 2> $D/bench_driver_line.err
 python tools/conv_sweep.py --cfgs 4,5,7 --reps 100 --set r101 2> /dev/null | grep -v amdgpu > $P/conv_sweep.txt
 python tools/conv_sweep.py --cfgs 4,7 --reps 100 --set lcnn --nb 128 2> /dev/null | grep -v amdgpu >> $P/conv_sweep.txt
 mkdir -p gpurun_out/$P && cp -r $P/. gpurun_out/$P/

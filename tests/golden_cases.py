@@ -242,3 +242,45 @@ def replay(subject, cases, gold, check):
             continue
         res = fn(subject)
         check(key, res, subject.trace(), gold)
+
+
+REFCHECK_SAMPLES = 128
+
+
+def refcheck_summary(P, at=None):
+    """tests/golden/make_golden_refcheck.py: what a list of P tensors is pinned by when the tensors themselves are too large to commit.  Per
+    tensor: its shape (padded with -1 to 4 dims), the flat position of max|P| (`at`: the reference's positions instead), max|P|, sum, sum of
+    squares and a seeded +-1-weighted sum (float64), and the values at that position and at REFCHECK_SAMPLES seeded positions (float32)."""
+    n = len(P)
+    out = {'shape': -np.ones((n, 4), np.int64), 'argmax': np.zeros(n, np.int64), 'stats': np.zeros((n, 4), np.float64),
+           'samples': np.zeros((n, 1 + REFCHECK_SAMPLES), np.float32)}
+    for i, p in enumerate(P):
+        a = p.detach().cpu().numpy().astype(np.float64).ravel()
+        out['shape'][i, :p.dim()] = tuple(p.shape)
+        rs = np.random.RandomState(1000 + i)
+        idx = rs.randint(0, a.size, REFCHECK_SAMPLES)
+        w = rs.randint(0, 2, a.size).astype(np.float64) * 2 - 1
+        arg = int(np.argmax(np.abs(a))) if at is None else int(at[i])
+        out['argmax'][i] = arg
+        out['stats'][i] = (np.abs(a).max(), a.sum(), (a * a).sum(), (w * a).sum())
+        out['samples'][i] = a[np.concatenate(([arg], idx))]
+    return out
+
+
+def check_refcheck(P, gold, key, rtol=1e-6):
+    """The oracle's P tensors against the reference's summary under key: every bound below follows from max|P - P_ref| <= rtol max|P_ref|
+    (the element-wise test of a live comparison), which holds it exactly at the max|P| position and the seeded positions."""
+    assert len(P) == len(gold[key + '/argmax']), (len(P), len(gold[key + '/argmax']))
+    got = refcheck_summary(P, at=gold[key + '/argmax'])
+    assert np.array_equal(got['shape'], gold[key + '/shape'])
+    st, sa = gold[key + '/stats'], gold[key + '/samples'].astype(np.float64)
+    for i in range(len(P)):
+        amax = st[i, 0]
+        tol = rtol * amax
+        n = float(P[i].numel())
+        d = np.abs(got['samples'][i].astype(np.float64) - sa[i])
+        assert d.max() <= tol, (key, i, float(d.max()), tol)
+        assert abs(got['stats'][i, 0] - amax) <= tol, (key, i, 'max')
+        assert abs(got['stats'][i, 1] - st[i, 1]) <= n * tol, (key, i, 'sum')
+        assert abs(got['stats'][i, 2] - st[i, 2]) <= n * tol * (2 * amax + tol), (key, i, 'sum of squares')
+        assert abs(got['stats'][i, 3] - st[i, 3]) <= n * tol, (key, i, 'weighted sum')
