@@ -78,15 +78,18 @@ class _Call(object):
 class Tape(object):
     """Records one forward of a backbone as hooked module calls + glue, evaluating true values eagerly."""
 
-    def __init__(self, params, with_bias=False):
-        self.p = params
+    def __init__(self, params, with_bias=False, dtype=torch.float32):
+        """dtype: the precision every value on the tape is held in (input, parameters, seed).  float32 (the default) is the
+        reference's own; float64 makes the tape a high-precision yardstick for the engine AND for the fp32 tape."""
+        self.dtype = dtype
+        self.p = params if dtype == torch.float32 else {k: v.detach().to(dtype) for k, v in params.items()}
         self.with_bias = bool(with_bias)
         self.calls = []
         self.T = []  # true value per tensor id
 
     # -- plumbing ---------------------------------------------------------------------------
     def input(self, x):
-        self.T.append(x.detach().clone().float())
+        self.T.append(x.detach().clone().to(self.dtype))
         return 0
 
     def _record(self, name, ins, hooked, fn, inplace=False):
@@ -178,7 +181,7 @@ class Tape(object):
 
     def g_linear(self, x, weight):
         # un-hooked triplet classifier (true signed weights), whitebox.py:93-96
-        w = weight.detach().clone().float()
+        w = weight.detach().clone().to(self.dtype)
         return self._record('classifier', [x], False, lambda ins, positive: F.linear(ins[0], w))
 
     # -- the three passes ---------------------------------------------------------------------
@@ -215,7 +218,7 @@ class Tape(object):
         Pv = self.positive_pass()
         hooks = self.hooks_by_tensor()
         producer = {c.out: k for k, c in enumerate(self.calls)}
-        G = {seed_tensor: seed.detach().clone().float()}
+        G = {seed_tensor: seed.detach().clone().to(self.dtype)}
         P, names = [], []
         eps32 = eps
 
@@ -284,7 +287,7 @@ class Tape(object):
         """The `dA` list of whitebox.py:355-358: in 'activation' mode every hooked module input carries a plain tensor hook
         `_savegrad` that records its (true-weight) gradient; one entry per hook firing, same order as Whitebox.P."""
         hooks = self.hooks_by_tensor()
-        G = {seed_tensor: seed.detach().clone().float()}
+        G = {seed_tensor: seed.detach().clone().to(self.dtype)}
         dA = []
         for k in range(len(self.calls) - 1, -1, -1):
             c = self.calls[k]

@@ -267,6 +267,8 @@ struct ConvParams {
                         // (kh, kw, 4 channel slots), i.e. K = 4 * kh * kw with zero rows for the missing channels
     int K_logical;      // Cin * kh * kw, for FLOP accounting (== K unless tap_major == 2)
     int kh, kw, stride, pad;
+    int pad_dw;         // the columns' padding is pad + pad_dw: a backward-data GEMM of a kernel that is not square (a Linear over an H != W map:
+                        // padding kh - 1 on the rows, kw - 1 on the columns); 0 everywhere else
     int OH, OW;
     int K, M;           // M = NB*OH*OW
     int CoutTot, nhalves, ldw;   // CoutTot = output channels per half

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(NT, CHAIN == 0 ? 1 : (CHAIN == 1 ? 7 : (CHAIN == 4 
             const int oh = r / p.OW;
             const int ow = r - oh * p.OW;
             ih0[s] = m_ok ? oh * p.stride - p.pad : -(1 << 28);
-            iw0[s] = ow * p.stride - p.pad;
+            iw0[s] = ow * p.stride - p.pad - p.pad_dw;
             base_m[s] = n * p.H * p.W + (oh * p.stride - p.pad) * p.W + iw0[s];
             unsigned long long mk = 0ull;
             if ((MODE == MODE_TAP || MODE == MODE_TAP4) && m_ok) {
@@ -519,7 +519,7 @@ __global__ __launch_bounds__(NT, CHAIN == 4 ? XFR_KS_DUAL_WAVES : 5) void conv_g
         const int r = mm - n * ohw;
         const int oh = r / p.OW;
         const int ow = r - oh * p.OW;
-        const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad;
+        const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad - p.pad_dw;
         base_m = n * p.H * p.W + ih0 * p.W + iw0;
         if (m_ok) {
             unsigned long long vw = 0ull;

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
         const int r = mm - n * ohw;
         const int oh = r / p.OW;
         const int ow = r - oh * p.OW;
-        const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad;
+        const int ih0 = oh * p.stride - p.pad, iw0 = ow * p.stride - p.pad - p.pad_dw;
         base_m = n * p.H * p.W + ih0 * p.W + iw0;
         if (m_ok) {
             unsigned long long vw = 0ull;
@@ -485,7 +485,7 @@ bool split_patch_ok(const ConvParams& p)
 {
     const int T = p.kh * p.kw;
     if (T < 5 || T > SPP_MAX_TAPS || (T % 3) != 0 || p.stride != 1 || p.tap_major != 1) return false;        // (T % 3: a pass of three K-steps stays inside one channel block)
-    if (p.OH != p.H || p.OW != p.W || 2 * p.pad != p.kh - 1 || 2 * p.pad != p.kw - 1) return false;
+    if (p.OH != p.H || p.OW != p.W || 2 * p.pad != p.kh - 1 || 2 * p.pad != p.kw - 1 || p.pad_dw != 0) return false;
     static const bool off = getenv("XFR_SPLIT_NO_PATCH") != nullptr;          // A/B runs: the slab for every covered layer
     return spp_halo(p) <= SPP_MAX_HALO && !off;
 }

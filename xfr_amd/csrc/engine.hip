@@ -795,7 +795,11 @@ void fuse_probe_forward(xfr_engine* e, int k, int B, ConvParams& p, hipStream_t 
     const int lean_max_k = [] { const char* v = getenv("XFR_LEAN_MAX_K"); return v ? atoi(v) : 512; }();
     // ... and for KxK convolutions: their two-accumulator form ties with the dual launch up to K = 1152 (measured, profiles/r5/experiments/lean_k_threshold.txt)
     const int lean_max_k3 = [&] { const char* v = getenv("XFR_LEAN_MAX_K3"); return v ? atoi(v) : std::max(lean_max_k, 1152); }();
-    bool lean = lean_try && dual && d.out != 1 && e->ops[k].Kf <= (d.kh * d.kw > 1 ? lean_max_k3 : lean_max_k) && e->tens[d.out].need_pv &&
+    // ... and only where the GEMM has a two-accumulator instantiation: not on the generic (ci, kh, kw) gather, which a KxK layer with Cin % 16 != 0
+    // and a strided 1x1 layer with Cin % 16 != 0 take (launch_cfg) -- such a launch was refused and the whole call failed
+    const int cin = e->tens[d.in0].C;
+    const bool dual_gather = d.kh * d.kw > 1 ? e->ops[k].tap_fwd : ((cin % 16) == 0 || (d.stride == 1 && d.pad == 0));
+    bool lean = lean_try && dual && dual_gather && d.out != 1 && e->ops[k].Kf <= (d.kh * d.kw > 1 ? lean_max_k3 : lean_max_k) && e->tens[d.out].need_pv &&
                 (e->lean_decide || (e->lean_cur && e->lean_cur->lean_q[d.out] == 1));
     if (lean)
         for (const Hook& h : e->tens[d.out].hooks)
@@ -2140,7 +2144,7 @@ void bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& st, int 
         p.as_strided = 1;
     } else if (d.stride == 1) {
         // backward-data of a stride-1 convolution == convolution with the flipped, transposed kernel and padding k-1-p
-        p.kh = d.kh; p.kw = d.kw; p.stride = 1; p.pad = d.kh - 1 - d.pad;
+        p.kh = d.kh; p.kw = d.kw; p.stride = 1; p.pad = d.kh - 1 - d.pad; p.pad_dw = d.kw - d.kh;
         p.OH = a.H; p.OW = a.W;
         p.out_H = a.H; p.out_W = a.W; p.out_stride = 1;
     } else {
@@ -2586,7 +2590,7 @@ static void presplit_weights(xfr_engine* e)
             ConvParams q;
             memset(&q, 0, sizeof(q));
             q.Cin = t.C; q.H = t.H; q.W = t.W;
-            q.kh = d.kh; q.kw = d.kw; q.stride = 1; q.pad = d.kh - 1 - d.pad;
+            q.kh = d.kh; q.kw = d.kw; q.stride = 1; q.pad = d.kh - 1 - d.pad; q.pad_dw = d.kw - d.kh;
             q.OH = a.H; q.OW = a.W; q.out_stride = 1;
             q.tap_major = o.tap_bwd ? 1 : 0;
             q.CoutTot = a.C; q.nhalves = 1; q.ldw = o.ldb; q.K = o.Kb;
