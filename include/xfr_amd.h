@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define XFR_AMD_ABI_VERSION 6
+#define XFR_AMD_ABI_VERSION 7
 
 typedef enum {
     XFR_OK = 0,
@@ -384,6 +384,53 @@ xfr_status xfr_ebp_capture(xfr_engine* e, const float* x_dev, int32_t n, int32_t
 xfr_status xfr_layerwise_ebp(xfr_engine* e, const float* x_dev, int32_t n, int32_t n_sweeps, int32_t seed_tensor,
                              const int32_t* firing_host, const int32_t* elem_host, const float* val_host,
                              const float* dense_prior_dev, float* pooled_dev, void* stream);
+
+/* weighted_subtree_ebp (whitebox.py:647-737) in one call, for N independent probes.  ABI version 7.
+ *
+ * seed_dev: 3 x N x D gradient seeds at seed_tensor -- stream 0 the gate output g0 and stream 1 the non-mate output g1 of
+ * xfr_subtree_weights, stream 2 the EBP channel of xfr_ebp_capture / the layerwise sweeps.  The call holds the forward pass for all its
+ * phases (xfr_engine_hold_forward; the previous setting is restored on every exit) and, per probe b:
+ *   1. w[k], idx[k] as xfr_subtree_weights (gate_ge0 as there), the prior values P[k][idx[k]] as xfr_ebp_capture;
+ *   2. the visiting order: `order_fn(w, n_firings, b, order, order_user)` fills `order` with a permutation of the firings, ascending by
+ *      weight, and returns 0 (anything else fails the call with XFR_INVALID_ARG).  order_fn == NULL: the engine's rule, the order of
+ *      np.argsort(w.astype(np.float64), kind='stable') -- equal weights (hooks that share one gradient tensor) ascend by firing index,
+ *      so the higher index is visited first.  NumPy's default argsort breaks such ties differently, and the reference uses it: a
+ *      caller that must select what the reference selects passes that order through order_fn (the Python wrapper does);
+ *   3. from the heaviest firing down, skipping firings whose prior value is exactly 0 and firing 1 (whitebox.py:706-707), the
+ *      candidates are swept in rounds of xfr_layerwise_ebp sweeps (sweep_batch per probe in the first round, 0 = min(2 * max_batch / N,
+ *      max(8, 2 * topk)); later rounds min(sweep_batch, 2 * (topk - found) + 2)); a sweep whose pooled map has max > 0 is a valid
+ *      subtree; a probe stops at topk valid subtrees or when it runs out of firings.  sweep_batch x N must fit 2 * max_batch rows;
+ *   4. the valid maps in ascending weight order (the reference's [-topk:]) are merged: weights scale-normalised in fp32 (all equal:
+ *      ones), each map times its normalised weight times 1 / (max + 1e-12), summed (do_max_subtree = 0) or maxed (1), then
+ *      output MWP:      / max(sum, eps);
+ *      output SALIENCY: as MWP, then _mwp_to_saliency (ebp_version 6: gaussian blur, clamp, normalise) of the merged AND the top-k maps;
+ *      output UINT8:    the levels of np.uint8(255 * (m - min) / (eps + max - min)) (ebp_version != 6, whitebox.py:726), stored as floats;
+ *                       the reference's PIL blur of those versions stays with the caller.
+ * smap_dev: N x H1 x W1.  top_dev (may be NULL): N x topk x H1 x W1, probe b's valid maps (pooled, or blurred for SALIENCY) in slots
+ * 0 .. n_valid[b]-1, zero beyond.  w_valid_host / k_valid_host: N x topk host arrays, the weights and firings of those maps in the same
+ * ascending-weight order, padded with 0 / -1; n_valid_host: N.  A probe without any valid subtree fails the call with XFR_STATE_ERROR
+ * and the reference's message (whitebox.py:710-715).  Synchronises `stream`. */
+typedef enum {
+    XFR_SUBTREE_MWP = 0,
+    XFR_SUBTREE_SALIENCY = 1,
+    XFR_SUBTREE_UINT8 = 2
+} xfr_subtree_output;
+
+typedef int32_t (*xfr_subtree_order_fn)(const float* w, int32_t n_firings, int32_t probe, int32_t* order, void* user);
+
+typedef struct {
+    int32_t topk;                   /* >= 1 */
+    int32_t gate_ge0;               /* 1: (g0 >= 0) * -g1 (do_mated_similarity_gating); 0: (g0 < 0) * -g1 */
+    int32_t do_max_subtree;         /* 1: max over the valid subtrees; 0: sum */
+    int32_t output;                 /* xfr_subtree_output */
+    int32_t sweep_batch;            /* candidates per probe in the first round; 0: the default above */
+    xfr_subtree_order_fn order_fn;  /* NULL: the engine's order rule */
+    void* order_user;
+} xfr_subtree_args;
+
+xfr_status xfr_weighted_subtree_ebp(xfr_engine* e, const float* x_dev, int32_t n, int32_t seed_tensor, const float* seed_dev,
+                                    const xfr_subtree_args* args, float* smap_dev, float* top_dev, float* w_valid_host,
+                                    int32_t* k_valid_host, int32_t* n_valid_host, void* stream);
 
 /* Whitebox.P[firing] of a standard EBP sweep (whitebox.py:394): out_dev receives N x C x H x W; (c,h,w) receive its shape
  * (out_dev == NULL: shape query only, nothing is run).  firing == xfr_firing_count: the hook on the first convolution's INPUT (the

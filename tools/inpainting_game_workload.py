@@ -22,6 +22,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+class _NativeSubtree(object):
+    """The drop-in caller's Whitebox with weighted_subtree_ebp(..., native=True)."""
+
+    def __init__(self, wb):
+        self._wb = wb
+
+    def __getattr__(self, name):
+        return getattr(self._wb, name)
+
+    def weighted_subtree_ebp(self, *a, **k):
+        return self._wb.weighted_subtree_ebp(*a, native=True, **k)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--jobs', type=int, default=32)
@@ -40,6 +53,7 @@ def main():
     ap.add_argument('--workers', type=int, default=1,
                     help='group mode: job groups in flight per GPU -- that many engines, each on its own host thread and stream; a second one fills the launch '
                          'gaps and host synchronisation points of the first (bench.py: 82 -> 121 jobs/s; an engine for 128 images is ~95 GB of workspace)')
+    ap.add_argument('--native-subtree', action='store_true', help='weighted subtree EBP as one engine call (xfr_weighted_subtree_ebp)')
     ap.add_argument('--numpy-inputs', action='store_true', help='uint8 H x W x 3 images through convert_from_numpy (PIL) per call, like the reference')
     args = ap.parse_args()
     import numpy as np
@@ -128,7 +142,7 @@ def main():
                 jobs.append((list(imgs[1:1 + k]), list(imgs[1 + k:]), imgs[0]))
             t1 = time.perf_counter()
             res = IG.run_jobs_batched(wbs[w], jobs, 'resnetv4_pytorch', 'norelu', 6, dev, topk=args.topk,
-                                      timings=phase if (args.phases and len(wbs) == 1) else None)
+                                      timings=phase if (args.phases and len(wbs) == 1) else None, native_subtree=args.native_subtree)
             torch.cuda.current_stream(dev).synchronize()
             dt_g = time.perf_counter() - t1
             for i, (job, odir) in enumerate(todo):
@@ -182,7 +196,8 @@ def main():
             return IG.run_contrastive_triplet_ebp(wb, mates, nonmates, probe, net_name, ver, 20, dev)
 
         def f_sub():
-            return IG.run_weighted_subtree_triplet_ebp(wb, mates, nonmates, probe, net_name, 'norelu', ver, dev, topk=args.topk)
+            return IG.run_weighted_subtree_triplet_ebp(_NativeSubtree(wb) if args.native_subtree else wb, mates, nonmates, probe, net_name, 'norelu',
+                                                       ver, dev, topk=args.topk)
 
         methods = [(names['meanEBP'], f_mean), (names['contrastive'], f_con), (names['truncated'], f_tru), (names['weighted-subtree'], f_sub)]
         stamps = [time.perf_counter()]

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Where the time of weighted_subtree_ebp_batch goes (BASELINE.json configs[4]'s dominant method): N probes on ResNet-101 ('norelu', top-32), wall
 time per phase (device synchronised between phases) and, from the kernels' own launch log, the GEMM launches by shape / chain / kernel.
-    python tools/subtree_probe.py [--n 8] [--topk 32] [--reps 3] [--log]"""
+    python tools/subtree_probe.py [--n 8] [--topk 32] [--reps 3] [--log] [--native]
+--native: the same probe also through the one-call engine path (xfr_weighted_subtree_ebp), timed in the same run after the Python path; both
+ms_per_call values are printed, with the largest difference between the two merged maps."""
 import argparse
 import collections
 import json
@@ -20,6 +22,7 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--max-batch', type=int, default=128)
     ap.add_argument('--sweep-batch', type=int, default=None, help='candidate layers per probe in the first layerwise round (default: min(2 * max_batch / n, 2 * topk))')
+    ap.add_argument('--native', action='store_true', help='also time weighted_subtree_ebp_batch(..., native=True) in the same run')
     ap.add_argument('--log', action='store_true', help='per-shape table of the GEMM launches of one call (in-kernel launch log)')
     args = ap.parse_args()
     import numpy as np
@@ -65,6 +68,20 @@ def main():
            'phases_ms_per_call': {k: round(1e3 * v[0] / args.reps, 2) for k, v in T.items()}, 'phase_calls_per_call': {k: v[1] / args.reps for k, v in T.items()},
            'valid_subtrees': [len(r[3]) for r in res]}
     out['phases_ms_per_call']['host + merge (rest)'] = round(1e3 * dt - sum(out['phases_ms_per_call'].values()), 2)
+    if args.native:
+        nat = wb.weighted_subtree_ebp_batch(x, xm, xn, topk=args.topk, sweep_batch=args.sweep_batch, native=True)          # warm
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.reps):
+            nat = wb.weighted_subtree_ebp_batch(x, xm, xn, topk=args.topk, sweep_batch=args.sweep_batch, native=True)
+        torch.cuda.synchronize()
+        dn = (time.perf_counter() - t0) / args.reps
+        out['native'] = {'ms_per_call': 1e3 * dn, 'ms_per_probe': 1e3 * dn / n, 'valid_subtrees': [len(r[3]) for r in nat],
+                         'same_k_valid': all(list(a[3]) == list(b[3]) for a, b in zip(res, nat)),
+                         'max_map_diff_rel': max(float(np.abs(np.asarray(a[0]) - np.asarray(b[0])).max() / np.abs(np.asarray(a[0])).max())
+                                                 for a, b in zip(res, nat))}
+        out['python_ms_per_call'] = out['ms_per_call']
+        out['native_ms_per_call'] = out['native']['ms_per_call']
     print(json.dumps(out))
     if args.log:
         csv = tuning.record_launch_log(lambda: wb.weighted_subtree_ebp_batch(x, xm, xn, topk=args.topk, sweep_batch=args.sweep_batch), 0, dev, launches_per_step_cap=40000)

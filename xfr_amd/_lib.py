@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('XFR_AMD_LIB') or os.path.join(_HERE, 'csrc', 'libxfr_amd.so')      # XFR_AMD_LIB: A/B builds of the same ABI (tools/ab_env.sh)
 
 XFR_OK, XFR_INVALID_ARG, XFR_UNSUPPORTED_LAYER, XFR_OOM, XFR_HIP_ERROR, XFR_STATE_ERROR, XFR_RCCL_ERROR = range(7)
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class TensorView(ctypes.Structure):
@@ -17,6 +17,17 @@ class TensorView(ctypes.Structure):
 
 class U8Preprocess(ctypes.Structure):
     _fields_ = [('kind', ctypes.c_int32), ('channels', ctypes.c_int32), ('mean', ctypes.c_double * 4), ('weight', ctypes.c_double * 4)]
+
+
+# xfr_weighted_subtree_ebp: the visiting-order callback, its arguments and its output modes (xfr_subtree_output)
+SUBTREE_ORDER_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_int32,
+                                    ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p)
+SUBTREE_MWP, SUBTREE_SALIENCY, SUBTREE_UINT8 = range(3)
+
+
+class SubtreeArgs(ctypes.Structure):
+    _fields_ = [('topk', ctypes.c_int32), ('gate_ge0', ctypes.c_int32), ('do_max_subtree', ctypes.c_int32), ('output', ctypes.c_int32),
+                ('sweep_batch', ctypes.c_int32), ('order_fn', SUBTREE_ORDER_FN), ('order_user', ctypes.c_void_p)]
 
 
 class XfrError(RuntimeError):
@@ -70,6 +81,8 @@ SYMBOLS = [
     ('xfr_subtree_weights', _I, [_P, _P, _I, _I, _P, _I, ctypes.POINTER(_F), ctypes.POINTER(_I), _I, _P]),
     ('xfr_ebp_capture', _I, [_P, _P, _I, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_F), _I, _P]),
     ('xfr_layerwise_ebp', _I, [_P, _P, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_F), _P, _P, _P]),
+    ('xfr_weighted_subtree_ebp', _I, [_P, _P, _I, _I, _P, ctypes.POINTER(SubtreeArgs), _P, _P, ctypes.POINTER(_F), ctypes.POINTER(_I),
+                                      ctypes.POINTER(_I), _P]),
     ('xfr_ebp_store_firing', _I, [_P, _P, _I, _I, _P, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _P]),
     ('xfr_engine_set_trace', _I, [_P, _I]),
     ('xfr_engine_trace_size', _I, [_P, ctypes.POINTER(_I)]),

@@ -399,3 +399,14 @@ void launch_truncation_threshold(const float* P, const double* sums, float perce
 size_t truncation_scratch_bytes(int N);
 // gaussian(sigma=2, nearest, truncate 4) -> clamp -> /max(sum,eps)    in/out [N][H][W]; tmp same size
 void launch_saliency_blur(const float* in, float* tmp, float* out, int N, int H, int W, float eps, hipStream_t s);
+// weighted subtree EBP in one call (xfr_weighted_subtree_ebp).  launch_pool_rowmax: launch_channel_pool's sums plus key[sb], the row's max as
+// an order-preserving unsigned key (rowmax_from_key turns it back into the float).  launch_gather_rows: dst row pairs[2i+1] = src row pairs[2i].
+// launch_reverse_slots: per probe b, slots 0 .. cnt[b]-1 of its topk-slot block in reverse order.  launch_subtree_merge: one workgroup per probe,
+// sum (do_max = 0) or max of (wn * P[slot]) * inv over the cnt[b] table entries, then / max(sum, eps) or (mode_u8) the uint8 levels as floats.
+struct SubtreeSlot { int slot; float wn; float inv; int pad; };
+void launch_pool_rowmax(const float* P, float* pooled, unsigned* key, int C, int SB, int HW, hipStream_t s);
+float rowmax_from_key(unsigned key);
+void launch_gather_rows(const float* src, float* dst, const int* pairs_dev, int n_pairs, int HW, hipStream_t s);
+void launch_reverse_slots(float* store, const int* cnt_dev, int N, int topk, int HW, hipStream_t s);
+void launch_subtree_merge(const float* store, const SubtreeSlot* tab_dev, const int* cnt_dev, float* out, int N, int topk, int HW, int do_max,
+                          int mode_u8, float eps, hipStream_t s);

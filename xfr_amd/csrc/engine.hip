@@ -192,6 +192,15 @@ struct xfr_engine {
     int store_slot = -1;                              // firing whose full P tensor is kept in store_dev
     float* store_dev = nullptr;
     int store_tensor = -1, store_sb = 0;
+    // xfr_weighted_subtree_ebp: row-max keys of a round (device + pinned host), the round's gather pairs and the merge table (device + pinned
+    // host), and the top-k store used when the caller passes no top_dev (grown on demand)
+    unsigned *wst_key_d = nullptr, *wst_key_h = nullptr;
+    int *wst_pairs_d = nullptr, *wst_pairs_h = nullptr;
+    SubtreeSlot *wst_tab_d = nullptr, *wst_tab_h = nullptr;
+    int *wst_cnt_d = nullptr, *wst_cnt_h = nullptr;
+    size_t wst_tab_cap = 0;
+    float* wst_store = nullptr;
+    size_t wst_store_floats = 0;
     std::vector<char> is_hook_a;       // per tensor: some hook takes its a (and x) from this tensor's forward values
     std::vector<char> fwd_done;        // per forward pass: ops whose work was folded into an earlier GEMM epilogue
     std::vector<char> pos_done;        // ... and whose positive-pass output was produced there too
@@ -2463,6 +2472,15 @@ xfr_status xfr_engine_destroy(xfr_engine* e)
     if (e->stat_desc) (void)hipFree(e->stat_desc);
     if (e->stat_f2u) (void)hipFree(e->stat_f2u);
     if (e->store_dev) (void)hipFree(e->store_dev);
+    if (e->wst_key_d) (void)hipFree(e->wst_key_d);
+    if (e->wst_key_h) (void)hipHostFree(e->wst_key_h);
+    if (e->wst_pairs_d) (void)hipFree(e->wst_pairs_d);
+    if (e->wst_pairs_h) (void)hipHostFree(e->wst_pairs_h);
+    if (e->wst_tab_d) (void)hipFree(e->wst_tab_d);
+    if (e->wst_tab_h) (void)hipHostFree(e->wst_tab_h);
+    if (e->wst_cnt_d) (void)hipFree(e->wst_cnt_d);
+    if (e->wst_cnt_h) (void)hipHostFree(e->wst_cnt_h);
+    if (e->wst_store) (void)hipFree(e->wst_store);
     if (e->idx_ws2) (void)hipFree(e->idx_ws2);
     if (e->idx_ws3) (void)hipFree(e->idx_ws3);
     for (int i = 0; i < 3; ++i) { if (e->seedbuf[i]) (void)hipFree(e->seedbuf[i]); if (e->ev_slot_done[i]) (void)hipEventDestroy(e->ev_slot_done[i]); }
@@ -3260,9 +3278,10 @@ xfr_status xfr_ebp_capture(xfr_engine* e, const float* x_dev, int32_t n, int32_t
     return XFR_OK;
 }
 
-xfr_status xfr_layerwise_ebp(xfr_engine* e, const float* x_dev, int32_t n, int32_t n_sweeps, int32_t seed_tensor,
-                             const int32_t* firing_host, const int32_t* elem_host, const float* val_host,
-                             const float* dense_prior_dev, float* pooled_dev, void* stream)
+// the body of xfr_layerwise_ebp; rowmax_key (may be null): the pooled rows go through launch_pool_rowmax, which also leaves each row's max
+static xfr_status layerwise_run(xfr_engine* e, const float* x_dev, int32_t n, int32_t n_sweeps, int32_t seed_tensor,
+                                const int32_t* firing_host, const int32_t* elem_host, const float* val_host,
+                                const float* dense_prior_dev, float* pooled_dev, unsigned* rowmax_key, hipStream_t stream)
 {
     xfr_status st = check_run(e, x_dev, n);
     if (st != XFR_OK) return st;
@@ -3336,9 +3355,250 @@ xfr_status xfr_layerwise_ebp(xfr_engine* e, const float* x_dev, int32_t n, int32
     e->rc_dense_slot = -1;
     if (st != XFR_OK) return st;
     const Tensor& t1 = e->tens[1];
-    launch_channel_pool(e->ws + e->tap_off, pooled_dev, t1.C, (int)rows, t1.HW(), s);
+    if (rowmax_key)
+        launch_pool_rowmax(e->ws + e->tap_off, pooled_dev, rowmax_key, t1.C, (int)rows, t1.HW(), s);
+    else
+        launch_channel_pool(e->ws + e->tap_off, pooled_dev, t1.C, (int)rows, t1.HW(), s);
     HIP_TRY(hipGetLastError());
     return fence_slot0(e, s);
+}
+
+xfr_status xfr_layerwise_ebp(xfr_engine* e, const float* x_dev, int32_t n, int32_t n_sweeps, int32_t seed_tensor,
+                             const int32_t* firing_host, const int32_t* elem_host, const float* val_host,
+                             const float* dense_prior_dev, float* pooled_dev, void* stream)
+{
+    return layerwise_run(e, x_dev, n, n_sweeps, seed_tensor, firing_host, elem_host, val_host, dense_prior_dev, pooled_dev, nullptr,
+                         (hipStream_t)stream);
+}
+
+// xfr_weighted_subtree_ebp's own scratch: row-max keys and gather pairs of a round (2 * max_batch rows), the merge table of n x topk slots and,
+// when the caller passes no top_dev, the top-k store (both grown on demand)
+static xfr_status ensure_weighted_scratch(xfr_engine* e, int n, int topk, bool need_store)
+{
+    const size_t rows = 2 * (size_t)e->max_batch;
+    if (!e->wst_key_d) {
+        HIP_TRY(hipMalloc(&e->wst_key_d, rows * sizeof(unsigned)));
+        HIP_TRY(hipHostMalloc(&e->wst_key_h, rows * sizeof(unsigned)));
+        HIP_TRY(hipMalloc(&e->wst_pairs_d, 2 * rows * sizeof(int)));
+        HIP_TRY(hipHostMalloc(&e->wst_pairs_h, 2 * rows * sizeof(int)));
+        HIP_TRY(hipMalloc(&e->wst_cnt_d, (size_t)e->max_batch * sizeof(int)));
+        HIP_TRY(hipHostMalloc(&e->wst_cnt_h, (size_t)e->max_batch * sizeof(int)));
+    }
+    const size_t slots = (size_t)n * topk;
+    if (slots > e->wst_tab_cap) {
+        if (e->wst_tab_d) { (void)hipFree(e->wst_tab_d); e->wst_tab_d = nullptr; }
+        if (e->wst_tab_h) { (void)hipHostFree(e->wst_tab_h); e->wst_tab_h = nullptr; }
+        e->wst_tab_cap = 0;
+        HIP_TRY(hipMalloc(&e->wst_tab_d, slots * sizeof(SubtreeSlot)));
+        HIP_TRY(hipHostMalloc(&e->wst_tab_h, slots * sizeof(SubtreeSlot)));
+        e->wst_tab_cap = slots;
+    }
+    const size_t floats = slots * (size_t)e->tens[1].HW();
+    if (need_store && floats > e->wst_store_floats) {
+        if (e->wst_store) { (void)hipFree(e->wst_store); e->wst_store = nullptr; }
+        e->wst_store_floats = 0;
+        HIP_TRY(hipMalloc(&e->wst_store, floats * sizeof(float)));
+        e->wst_store_floats = floats;
+    }
+    return XFR_OK;
+}
+
+xfr_status xfr_weighted_subtree_ebp(xfr_engine* e, const float* x_dev, int32_t n, int32_t seed_tensor, const float* seed_dev,
+                                    const xfr_subtree_args* args, float* smap_dev, float* top_dev, float* w_valid_host,
+                                    int32_t* k_valid_host, int32_t* n_valid_host, void* stream)
+{
+    static const char* const mode_names[4] = {"affineonly", "affineonly_with_prior", "norelu", "all"};
+    xfr_status st = check_run(e, x_dev, n);
+    if (st != XFR_OK) return st;
+    if (!seed_dev || !args || !smap_dev || !w_valid_host || !k_valid_host || !n_valid_host) return fail(XFR_INVALID_ARG, "null argument");
+    const int topk = args->topk;
+    if (topk < 1) return fail(XFR_INVALID_ARG, "xfr_weighted_subtree_ebp: topk %d, must be >= 1", topk);
+    if (args->output < XFR_SUBTREE_MWP || args->output > XFR_SUBTREE_UINT8)
+        return fail(XFR_INVALID_ARG, "xfr_weighted_subtree_ebp: output %d is not an xfr_subtree_output", args->output);
+    if (args->sweep_batch < 0) return fail(XFR_INVALID_ARG, "xfr_weighted_subtree_ebp: sweep_batch %d < 0", args->sweep_batch);
+    if (seed_tensor < 2 || seed_tensor >= (int)e->tens.size()) return fail(XFR_INVALID_ARG, "bad seed tensor %d", seed_tensor);
+    // whitebox.py's first round: min(2 * max_batch / N, max(8, 2 * topk)) candidates per probe
+    const long J = args->sweep_batch > 0 ? (long)args->sweep_batch
+                                         : std::max(1L, std::min((2L * e->max_batch) / n, (long)std::max(8, 2 * topk)));
+    if (J * n > 2L * e->max_batch)
+        return fail(XFR_INVALID_ARG, "xfr_weighted_subtree_ebp: %ld sweeps x %d images exceed the %d gradient rows of this engine", J, n,
+                    2 * e->max_batch);
+    st = ensure_subtree_scratch(e);
+    if (st != XFR_OK) return st;
+    st = ensure_weighted_scratch(e, n, topk, top_dev == nullptr);
+    if (st != XFR_OK) return st;
+    BwdPlan* plan = nullptr;
+    st = get_plan(e, seed_tensor, &plan);
+    if (st != XFR_OK) return st;
+    const int nf = plan->n_firings;
+    const Tensor& t1 = e->tens[1];
+    const int HW = t1.HW();
+    const size_t D = (size_t)e->tens[seed_tensor].per_n();
+    hipStream_t s = (hipStream_t)stream;
+    float* store = top_dev ? top_dev : e->wst_store;
+
+    // 1. one forward for every phase; the caller's hold (an enclosing group) survives the call, ours ends with it
+    struct HoldGuard {
+        xfr_engine* e;
+        bool prev;
+        ~HoldGuard() { if (!prev) { e->hold_forward = false; e->held_x = nullptr; } }
+    } hold{e, e->hold_forward};
+    if (!hold.prev) { e->hold_forward = true; e->held_x = nullptr; }
+
+    // 2-3. layer weights, chosen elements and prior values
+    std::vector<float> w((size_t)nf * n), vals((size_t)nf * n);
+    std::vector<int> idx((size_t)nf * n);
+    st = xfr_subtree_weights(e, x_dev, n, seed_tensor, seed_dev, args->gate_ge0, w.data(), idx.data(), nf * n, stream);
+    if (st != XFR_OK) return st;
+    st = xfr_ebp_capture(e, x_dev, n, seed_tensor, seed_dev + 2 * (size_t)n * D, idx.data(), vals.data(), nf, stream);
+    if (st != XFR_OK) return st;
+
+    // 4. visiting orders, ascending by weight
+    std::vector<std::vector<int>> order(n, std::vector<int>(nf));
+    {
+        std::vector<float> col(nf);
+        std::vector<char> seen(nf);
+        for (int b = 0; b < n; ++b) {
+            for (int k = 0; k < nf; ++k) col[k] = w[(size_t)k * n + b];
+            std::vector<int>& o = order[b];
+            if (args->order_fn) {
+                const int32_t r = args->order_fn(col.data(), nf, b, o.data(), args->order_user);
+                if (r != 0) return fail(XFR_INVALID_ARG, "xfr_weighted_subtree_ebp: order_fn returned %d for probe %d", r, b);
+                std::fill(seen.begin(), seen.end(), 0);
+                for (int k = 0; k < nf; ++k) {
+                    if (o[k] < 0 || o[k] >= nf || seen[o[k]])
+                        return fail(XFR_INVALID_ARG, "xfr_weighted_subtree_ebp: order_fn gave no permutation of the %d firings (probe %d)", nf, b);
+                    seen[o[k]] = 1;
+                }
+            } else {
+                // np.argsort(w.astype(np.float64), kind='stable'); NaN sorts last like NumPy's
+                for (int k = 0; k < nf; ++k) o[k] = k;
+                std::stable_sort(o.begin(), o.end(), [&](int a, int c) {
+                    const double x = col[a], y = col[c];
+                    return x < y || (x == x && y != y);
+                });
+            }
+        }
+    }
+
+    // 5-6. rounds of layerwise sweeps from the heaviest firing down (whitebox.py:700-716 as _weighted_subtree evaluates it)
+    std::vector<int> pos(n, nf);
+    std::vector<std::vector<int>> valid(n);          // per probe: valid firings, heaviest first; slot i of the store holds valid[b][i]
+    std::vector<std::vector<float>> vmax(n);         // ... and the max of each of those maps
+    std::vector<std::vector<int>> ks(n), row(n);
+    std::vector<int> F, E;
+    std::vector<float> V;
+    std::vector<long> lim(n);
+    float* pooled = e->ws + e->pooled_off;          // 2 * max_batch maps
+    if (top_dev) HIP_TRY(hipMemsetAsync(top_dev, 0, (size_t)n * topk * HW * sizeof(float), s));
+    int rounds = 0;
+    for (;;) {
+        bool open = false;
+        for (int b = 0; b < n; ++b) open = open || (pos[b] > 0 && (int)valid[b].size() < topk);
+        if (!open) break;
+        long Jr = 1;
+        for (int b = 0; b < n; ++b) {
+            lim[b] = rounds == 0 ? J : std::min(J, 2L * (topk - (long)valid[b].size()) + 2);
+            if ((int)valid[b].size() < topk) Jr = std::max(Jr, lim[b]);
+        }
+        ++rounds;
+        F.assign((size_t)Jr * n, -1);
+        E.assign((size_t)Jr * n, 0);
+        V.assign((size_t)Jr * n, 0.f);
+        bool work = false;
+        for (int b = 0; b < n; ++b) {
+            ks[b].clear();
+            if ((int)valid[b].size() < topk) {
+                while (pos[b] > 0 && (long)ks[b].size() < lim[b]) {
+                    const int k = order[b][--pos[b]];
+                    if (vals[(size_t)k * n + b] != 0.f && k != 1) ks[b].push_back(k);     // an all-zero prior gives an all-zero map (:706); k == 1 (:707)
+                }
+            }
+            std::vector<int> asc = ks[b];
+            std::sort(asc.begin(), asc.end());                     // ascending firing: a sweep joins at its own firing
+            row[b].assign(ks[b].size(), 0);
+            for (size_t j = 0; j < asc.size(); ++j) {
+                const int k = asc[j];
+                F[j * n + b] = k;
+                E[j * n + b] = idx[(size_t)k * n + b];
+                V[j * n + b] = vals[(size_t)k * n + b];
+                for (size_t q = 0; q < ks[b].size(); ++q) if (ks[b][q] == k) row[b][q] = (int)(j * n + b);
+            }
+            work = work || !ks[b].empty();
+        }
+        if (!work) continue;
+        st = layerwise_run(e, x_dev, n, (int)Jr, seed_tensor, F.data(), E.data(), V.data(), nullptr, pooled, e->wst_key_d, s);
+        if (st != XFR_OK) return st;
+        HIP_TRY(hipMemcpyAsync(e->wst_key_h, e->wst_key_d, (size_t)Jr * n * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));                 // also: the previous round's pairs have left wst_pairs_h
+        int np = 0;
+        for (int b = 0; b < n; ++b)
+            for (size_t q = 0; q < ks[b].size(); ++q) {
+                const float m = rowmax_from_key(e->wst_key_h[row[b][q]]);
+                if (m > 0.f && (int)valid[b].size() < topk) {                          // np.max(P) > 0 (:706)
+                    e->wst_pairs_h[2 * np] = row[b][q];
+                    e->wst_pairs_h[2 * np + 1] = b * topk + (int)valid[b].size();
+                    ++np;
+                    valid[b].push_back(ks[b][q]);
+                    vmax[b].push_back(m);
+                }
+            }
+        if (np > 0) {
+            HIP_TRY(hipMemcpyAsync(e->wst_pairs_d, e->wst_pairs_h, 2 * (size_t)np * sizeof(int), hipMemcpyHostToDevice, s));
+            launch_gather_rows(pooled, store, e->wst_pairs_d, np, HW, s);
+        }
+    }
+    for (int b = 0; b < n; ++b)
+        if (valid[b].empty())
+            return fail(XFR_STATE_ERROR, "Failed to calculate valid subtrees. The ebp subtree mode (%s) may not support by this type of network. "
+                        "You may want to try the \"affineonly_with_prior\" ebp subtree mode.", mode_names[e->mode & 3]);
+
+    // 7. the merge table in the reference's order (ascending weight): scale-normalised weights (_scale_normalized, fp32) and 1 / (max + 1e-12)
+    for (int b = 0; b < n; ++b) {
+        const int c = (int)valid[b].size();
+        e->wst_cnt_h[b] = c;
+        n_valid_host[b] = c;
+        float mn = INFINITY, mx = -INFINITY;
+        for (int t = 0; t < topk; ++t) {
+            k_valid_host[(size_t)b * topk + t] = -1;
+            w_valid_host[(size_t)b * topk + t] = 0.f;
+        }
+        for (int t = 0; t < c; ++t) {
+            const int k = valid[b][c - 1 - t];
+            const float wk = w[(size_t)k * n + b];
+            k_valid_host[(size_t)b * topk + t] = k;
+            w_valid_host[(size_t)b * topk + t] = wk;
+            mn = std::min(mn, wk);
+            mx = std::max(mx, wk);
+        }
+        const float den = e->eps + (mx - mn);
+        bool all_zero = true;
+        for (int t = 0; t < c; ++t) {
+            const float sn = (w_valid_host[(size_t)b * topk + t] - mn) / den;
+            all_zero = all_zero && sn == 0.f;
+            e->wst_tab_h[(size_t)b * topk + t] = SubtreeSlot{c - 1 - t, sn, 1.0f / (vmax[b][c - 1 - t] + 1e-12f), 0};
+        }
+        if (all_zero)
+            for (int t = 0; t < c; ++t) e->wst_tab_h[(size_t)b * topk + t].wn = 1.0f;       // np.sum(sn) == 0 -> ones (:718)
+    }
+    HIP_TRY(hipMemcpyAsync(e->wst_tab_d, e->wst_tab_h, (size_t)n * topk * sizeof(SubtreeSlot), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->wst_cnt_d, e->wst_cnt_h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    launch_subtree_merge(store, e->wst_tab_d, e->wst_cnt_d, smap_dev, n, topk, HW, args->do_max_subtree ? 1 : 0,
+                         args->output == XFR_SUBTREE_UINT8 ? 1 : 0, e->eps, s);
+    if (top_dev) launch_reverse_slots(top_dev, e->wst_cnt_d, n, topk, HW, s);
+    // 8. _mwp_to_saliency (ebp_version 6) of the merged map and the top-k maps, in place
+    if (args->output == XFR_SUBTREE_SALIENCY) {
+        float* tmp = e->ws + e->blur_b_off;                // 2 * max_batch maps
+        launch_saliency_blur(smap_dev, tmp, smap_dev, n, t1.H, t1.W, e->eps, s);
+        if (top_dev) {
+            const long maps = (long)n * topk, cap = 2L * e->max_batch;
+            for (long r0 = 0; r0 < maps; r0 += cap)
+                launch_saliency_blur(top_dev + r0 * HW, tmp, top_dev + r0 * HW, (int)std::min(cap, maps - r0), t1.H, t1.W, e->eps, s);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return XFR_OK;
 }
 
 xfr_status xfr_ebp_store_firing(xfr_engine* e, const float* x_dev, int32_t n, int32_t seed_tensor, const float* seed_dev,

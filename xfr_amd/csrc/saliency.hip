@@ -3,6 +3,7 @@
 // ebp_ver 6 branch).  Wavefront (64-lane) shuffle reductions; fp64 accumulation for the normalisation sums.
 #include "common.h"
 #include <math.h>
+#include <string.h>
 
 namespace {
 
@@ -229,6 +230,126 @@ __global__ __launch_bounds__(NT) void clamp_normalize_kernel(float* __restrict__
     for (int i = threadIdx.x; i < HW; i += NT) p[i] = __fdiv_rn(fmaxf(p[i], 0.f), denom);
 }
 
+// ---- weighted subtree EBP in one call (xfr_weighted_subtree_ebp, whitebox.py:700-737) --------------------------------------
+// Row maxima are kept as order-preserving unsigned keys (sign bit set for x >= 0, all bits flipped for x < 0), so that one vector
+// atomicMax per block combines the blocks of a row; a positive NaN maps above +inf and survives, as torch's amax keeps it.
+__device__ inline unsigned float_key(float x)
+{
+    const unsigned u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ inline float key_max(float a, float b) { return (b != b || b > a) ? b : a; }
+
+__device__ inline float wave_max(float v)
+{
+    for (int o = 32; o > 0; o >>= 1) v = key_max(v, __shfl_down(v, o));
+    return v;
+}
+
+// pooled[sb][hw] = sum_c P[c][sb][hw] exactly as channel_pool_kernel adds it (c ascending, fp32), and key[sb] = max over hw of that
+// row: the maps of a round are read once.  grid = (chunks of the row, SB); key must hold float_key(-inf) or less on entry.
+__global__ __launch_bounds__(NT) void pool_rowmax_kernel(const float* __restrict__ P, float* __restrict__ pooled,
+                                                        unsigned* __restrict__ key, int C, int SB, int HW)
+{
+    const int sb = blockIdx.y;
+    const long per_c = (long)SB * HW;
+    const long row = (long)sb * HW;
+    float m = -INFINITY;
+    for (int i = blockIdx.x * NT + threadIdx.x; i < HW; i += gridDim.x * NT) {
+        float acc = 0.f;
+        for (int c = 0; c < C; ++c) acc += P[(long)c * per_c + row + i];
+        pooled[row + i] = acc;
+        m = key_max(m, acc);
+    }
+    m = wave_max(m);
+    __shared__ float part[NT / 64];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float r = part[0];
+        for (int k = 1; k < NT / 64; ++k) r = key_max(r, part[k]);
+        atomicMax(&key[sb], float_key(r));
+    }
+}
+
+// dst[pair.y][:] = src[pair.x][:] for every (src row, dst row) pair: the valid maps of a round into their slots of the top-k store
+__global__ __launch_bounds__(NT) void gather_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, const int2* __restrict__ pairs,
+                                                        int HW)
+{
+    const int2 p = pairs[blockIdx.y];
+    const float* __restrict__ a = src + (long)p.x * HW;
+    float* __restrict__ b = dst + (long)p.y * HW;
+    if ((HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+        const float4* __restrict__ a4 = reinterpret_cast<const float4*>(a);
+        float4* __restrict__ b4 = reinterpret_cast<float4*>(b);
+        for (int i = blockIdx.x * NT + threadIdx.x; i < (HW >> 2); i += gridDim.x * NT) b4[i] = a4[i];
+    } else {
+        for (int i = blockIdx.x * NT + threadIdx.x; i < HW; i += gridDim.x * NT) b[i] = a[i];
+    }
+}
+
+// slots 0 .. cnt-1 of probe b were filled heaviest first: reverse them into the reference's ascending-weight order
+__global__ __launch_bounds__(NT) void reverse_slots_kernel(float* __restrict__ store, const int* __restrict__ cnt, int topk, int HW)
+{
+    const int b = blockIdx.y;
+    const int c = cnt[b];
+    float* __restrict__ base = store + (long)b * topk * HW;
+    const long total = (long)(c / 2) * HW;
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
+        const int s = (int)(i / HW);
+        const long p = i - (long)s * HW;
+        const float x = base[(long)s * HW + p], y = base[(long)(c - 1 - s) * HW + p];
+        base[(long)s * HW + p] = y;
+        base[(long)(c - 1 - s) * HW + p] = x;
+    }
+}
+
+// One workgroup per probe (whitebox.py:716-726): v = sum (or max) over the valid slots t, in the order of the table, of
+// (wn_t * P_t) * inv_t with wn_t the scale-normalised weight and inv_t = 1 / (max P_t + 1e-12), all fp32 like NumPy's float32 arrays;
+// then out = v / max(sum v, eps), or (mode_u8) the levels of np.uint8(255 * (v - min) / (eps + max - min)) as floats.
+constexpr int MT = 1024;
+
+__global__ __launch_bounds__(MT) void subtree_merge_kernel(const float* __restrict__ store, const SubtreeSlot* __restrict__ tab,
+                                                          const int* __restrict__ cnt, float* __restrict__ out, int topk, int HW,
+                                                          int do_max, int mode_u8, float eps)
+{
+    const int b = blockIdx.x;
+    const int c = cnt[b];
+    const SubtreeSlot* __restrict__ t = tab + (long)b * topk;
+    const float* __restrict__ base = store + (long)b * topk * HW;
+    float* __restrict__ o = out + (long)b * HW;
+    double sum = 0.0;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int i = threadIdx.x; i < HW; i += MT) {
+        float v = 0.f;
+        for (int k = 0; k < c; ++k) {
+            const float x = (t[k].wn * base[(long)t[k].slot * HW + i]) * t[k].inv;
+            v = k == 0 ? x : (do_max ? fmaxf(v, x) : v + x);
+        }
+        o[i] = v;
+        sum += (double)v;
+        mn = fminf(mn, v);
+        mx = fmaxf(mx, v);
+    }
+    sum = wave_sum(sum);
+    for (int d = 32; d > 0; d >>= 1) { mn = fminf(mn, __shfl_down(mn, d)); mx = fmaxf(mx, __shfl_down(mx, d)); }
+    __shared__ double ps[MT / 64];
+    __shared__ float pmn[MT / 64], pmx[MT / 64];
+    if ((threadIdx.x & 63) == 0) { ps[threadIdx.x >> 6] = sum; pmn[threadIdx.x >> 6] = mn; pmx[threadIdx.x >> 6] = mx; }
+    __syncthreads();
+    double tot = 0.0;
+    mn = INFINITY; mx = -INFINITY;
+    for (int k = 0; k < MT / 64; ++k) { tot += ps[k]; mn = fminf(mn, pmn[k]); mx = fmaxf(mx, pmx[k]); }
+    if (mode_u8) {
+        const float den = eps + (mx - mn);
+        for (int i = threadIdx.x; i < HW; i += MT) o[i] = (float)(int)(255.f * __fdiv_rn(o[i] - mn, den));
+    } else {
+        const float den = fmaxf((float)tot, eps);
+        for (int i = threadIdx.x; i < HW; i += MT) o[i] = __fdiv_rn(o[i], den);
+    }
+}
+
 inline int grid_for(long n)
 {
     long b = (n + NT - 1) / NT;
@@ -288,4 +409,38 @@ void launch_saliency_blur(const float* in, float* tmp, float* out, int N, int H,
     hipLaunchKernelGGL(blur_axis_kernel, dim3(grid_for(total)), dim3(NT), 0, s, in, tmp, N, H, W, 0, bw);
     hipLaunchKernelGGL(blur_axis_kernel, dim3(grid_for(total)), dim3(NT), 0, s, tmp, out, N, H, W, 1, bw);
     hipLaunchKernelGGL(clamp_normalize_kernel, dim3(N), dim3(NT), 0, s, out, H * W, eps);
+}
+
+void launch_pool_rowmax(const float* P, float* pooled, unsigned* key, int C, int SB, int HW, hipStream_t s)
+{
+    (void)hipMemsetAsync(key, 0, sizeof(unsigned) * SB, s);        // key 0 lies below float_key(-inf)
+    const int chunks = std::max(1, std::min(64, (HW + NT * 8 - 1) / (NT * 8)));
+    hipLaunchKernelGGL(pool_rowmax_kernel, dim3(chunks, SB), dim3(NT), 0, s, P, pooled, key, C, SB, HW);
+}
+
+float rowmax_from_key(unsigned k)
+{
+    const unsigned u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
+    float f;
+    memcpy(&f, &u, sizeof(f));
+    return f;
+}
+
+void launch_gather_rows(const float* src, float* dst, const int* pairs_dev, int n_pairs, int HW, hipStream_t s)
+{
+    if (n_pairs < 1) return;
+    const int chunks = std::max(1, std::min(64, (HW + NT * 4 * 4 - 1) / (NT * 4 * 4)));
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(chunks, n_pairs), dim3(NT), 0, s, src, dst, reinterpret_cast<const int2*>(pairs_dev), HW);
+}
+
+void launch_reverse_slots(float* store, const int* cnt_dev, int N, int topk, int HW, hipStream_t s)
+{
+    const int chunks = std::max(1, std::min(256, (int)(((long)(topk / 2) * HW + NT * 8 - 1) / (NT * 8))));
+    hipLaunchKernelGGL(reverse_slots_kernel, dim3(chunks, N), dim3(NT), 0, s, store, cnt_dev, topk, HW);
+}
+
+void launch_subtree_merge(const float* store, const SubtreeSlot* tab_dev, const int* cnt_dev, float* out, int N, int topk, int HW, int do_max,
+                          int mode_u8, float eps, hipStream_t s)
+{
+    hipLaunchKernelGGL(subtree_merge_kernel, dim3(N), dim3(MT), 0, s, store, tab_dev, cnt_dev, out, topk, HW, do_max, mode_u8, eps);
 }

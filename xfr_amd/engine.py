@@ -425,6 +425,59 @@ class Engine(object):
                                                   _stream_ptr(self.device)))
         return out if (n > 1 or dense_prior is None) else out[:, 0]
 
+    SUBTREE_OUTPUTS = {'mwp': _lib.SUBTREE_MWP, 'saliency': _lib.SUBTREE_SALIENCY, 'uint8': _lib.SUBTREE_UINT8}
+
+    def weighted_subtree(self, x, seed_tensor, seeds, topk, gate_ge0=True, do_max_subtree=False, output='saliency', sweep_batch=None,
+                         order='numpy', want_top=True):
+        """weighted_subtree_ebp of N probes in one engine call (xfr_weighted_subtree_ebp, include/xfr_amd.h).  seeds: 3 x N x D (gate
+        output, non-mate output, EBP channel).  output: 'mwp', 'saliency' (ebp_version 6) or 'uint8' (the levels, as floats).
+        order: 'numpy' -- np.argsort(w.astype(np.float64)), the reference's own call, through a callback; 'engine' -- the engine's rule
+        (stable: ties ascend by firing index); or a callable f(w, probe) -> ascending order of the n_firings float32 weights w.
+        Returns (smap N x H1 x W1, top N x topk x H1 x W1 or None -- both device tensors, slots in ascending weight order --, w_valid
+        N x topk float32, k_valid N x topk int32 (padding -1), n_valid N int32)."""
+        x, _ = self._prep(x)
+        n = x.shape[0]
+        seeds = seeds.detach().to(self.device, torch.float32).contiguous()
+        d = int(np.prod(self.tensor_shape(seed_tensor)))
+        if seeds.dim() != 3 or tuple(seeds.shape) != (3, n, d):
+            raise ValueError('seeds must be 3 x %d x %d, got %s' % (n, d, tuple(seeds.shape)))
+        topk = int(topk)
+        c1, h1, w1 = self.tensor_shape(1)
+        smap = torch.empty((n, h1, w1), device=self.device)
+        top = torch.empty((n, max(topk, 0), h1, w1), device=self.device) if want_top else None
+        w_valid = np.zeros((n, max(topk, 0)), dtype=np.float32)
+        k_valid = np.full((n, max(topk, 0)), -1, dtype=np.int32)
+        n_valid = np.zeros(n, dtype=np.int32)
+        if order == 'engine':
+            fn = _lib.SUBTREE_ORDER_FN()
+        else:
+            if order == 'numpy':
+                py = lambda w, b: np.argsort(w.astype(np.float64))              # noqa: E731  (whitebox.py:697 on a list of Python floats)
+            elif callable(order):
+                py = order
+            else:
+                raise ValueError("order must be 'numpy', 'engine' or a callable, got %r" % (order,))
+
+            def cb(w_ptr, nf, probe, out_ptr, user):
+                try:
+                    o = np.asarray(py(np.ctypeslib.as_array(w_ptr, shape=(nf,)).copy(), int(probe)), dtype=np.int64)
+                    if o.shape != (nf,):
+                        return 1
+                    np.ctypeslib.as_array(out_ptr, shape=(nf,))[:] = o
+                    return 0
+                except Exception:
+                    return 1
+            fn = _lib.SUBTREE_ORDER_FN(cb)          # referenced until the call returns
+        args = _lib.SubtreeArgs(topk, 1 if gate_ge0 else 0, 1 if do_max_subtree else 0, self.SUBTREE_OUTPUTS[output], int(sweep_batch or 0),
+                                fn, None)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.xfr_weighted_subtree_ebp(self._h, x.data_ptr(), n, int(seed_tensor), seeds.data_ptr(), ctypes.byref(args),
+                                                         smap.data_ptr(), top.data_ptr() if top is not None else None,
+                                                         w_valid.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                         k_valid.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                         n_valid.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _stream_ptr(self.device)))
+        return smap, top, w_valid, k_valid, n_valid
+
     def ebp_firing(self, x, seed_tensor, seed, firing):
         """Whitebox.P[firing] of a standard sweep: N x C x H x W."""
         x, _ = self._prep(x)

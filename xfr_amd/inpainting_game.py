@@ -71,7 +71,7 @@ def run_weighted_subtree_triplet_ebp(wb, im_mates, im_nonmates, probe_im, net_na
     return img_subtree
 
 
-def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, device, topk=32, methods=None, timings=None):
+def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, device, topk=32, methods=None, timings=None, native_subtree=False):
     """Additive: the four saliency methods of generate_wb_smaps (:295-399) for a GROUP of independent jobs in shared launches.
     jobs: list of (im_mates, im_nonmates, probe_im).  Per job the calls of mean_ebp (always over the HOOKED N-way classifier,
     which is what the generator's job loop has installed at that point; the drop-in mean_ebp uses whatever classifier is
@@ -82,7 +82,7 @@ def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, dev
     'meanEBP', 'contrastive', 'truncated', 'weighted-subtree'.  Needs the hooked classifier for meanEBP (restored afterwards)
     and ebp_version 6 maps (float32) for the batched tails.  The three triplet methods run the same probes through the
     network: they share one forward pass (xfr_engine_hold_forward).  timings: optional dict that receives seconds per phase
-    (synchronises the device between phases)."""
+    (synchronises the device between phases).  native_subtree: the weighted subtree method as one engine call (xfr_weighted_subtree_ebp)."""
     import time
     methods = methods or ('meanEBP', 'contrastive', 'truncated', 'weighted-subtree')
     n = len(jobs)
@@ -133,7 +133,8 @@ def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, dev
         if 'weighted-subtree' in methods:
             do_max_subtree, gating = SUBTREE_VERSIONS.get(ebp_version, (False, False))
             res = wb.weighted_subtree_ebp_batch(probes, xm, xn, k_poschannel=0, topk=topk, do_max_subtree=do_max_subtree,
-                                                do_mated_similarity_gating=gating, subtree_mode=subtree_mode_weighted)
+                                                do_mated_similarity_gating=gating, subtree_mode=subtree_mode_weighted,
+                                                native=native_subtree)
             out['weighted-subtree'] = [r[0] for r in res]
             lap('weighted-subtree')
     finally:

@@ -539,8 +539,9 @@ class Whitebox(object):
         return self._mwp_to_saliency(P) if not mwp else P
 
     def weighted_subtree_ebp(self, img_probe, k_poschannel, k_negchannel, topk=1, verbose=True, do_max_subtree=False,
-                             do_mated_similarity_gating=True, subtree_mode='norelu', do_mwp_to_saliency=True, sweep_batch=None):
-        """Weighted subtree EBP (whitebox.py:647-737).  Same result as the reference, computed with: one true-weight
+                             do_mated_similarity_gating=True, subtree_mode='norelu', do_mwp_to_saliency=True, sweep_batch=None, native=False):
+        """Weighted subtree EBP (whitebox.py:647-737).  native=True: the whole method as one engine call (xfr_weighted_subtree_ebp), same
+        result tuple (no per-layer `verbose` lines).  Same result as the reference, computed with: one true-weight
         gradient pass for the layer weights (:652-697), ONE standard EBP sweep for all prior values (the reference repeats
         it for every layer, :567), and layerwise sweeps batched on the GPU and evaluated lazily from the heaviest layer
         downwards until `topk` valid subtrees exist (the reference sweeps all ~377 layers and keeps the last topk, :700-716)."""
@@ -558,13 +559,14 @@ class Whitebox(object):
             g[0, 0] -= 1.0                                                      # d cross_entropy(y,[0])/dy  (:657,:664)
             _, s0 = self.net.seed_for(g, 1)
         _, sk = self.net.seed_for(onehot(k_poschannel), 1)
-        return self._weighted_subtree(eng, img_probe, seed_tensor, s0, s1, sk, topk, verbose, do_max_subtree,
-                                      do_mated_similarity_gating, do_mwp_to_saliency, sweep_batch)[0]
+        run = self._weighted_subtree_native if native else self._weighted_subtree
+        return run(eng, img_probe, seed_tensor, s0, s1, sk, topk, verbose, do_max_subtree, do_mated_similarity_gating, do_mwp_to_saliency,
+                   sweep_batch)[0]
 
     def weighted_subtree_ebp_batch(self, img_probes, x_mates, x_nonmates, k_poschannel=0, topk=1, do_max_subtree=False,
                                    do_mated_similarity_gating=True, subtree_mode='norelu', do_mwp_to_saliency=True,
-                                   sweep_batch=None):
-        """Additive: weighted_subtree_ebp for N independent probes in shared launches.  For probe i equivalent to
+                                   sweep_batch=None, native=False):
+        """Additive: weighted_subtree_ebp for N independent probes in shared launches (native=True: in one engine call).  For probe i equivalent to
         set_triplet_classifier(x_mates[i], x_nonmates[i]); weighted_subtree_ebp(img_probes[i:i+1], k_poschannel, 1 - k_poschannel...)
         with channel 0 the mate and channel 1 the non-mate.  The N forwards run once; the layer-weight pass carries 2N gradient
         streams, the capture pass N, and every round of layerwise sweeps J x N (J * N <= 2 * max_batch).  Returns a list of N
@@ -584,8 +586,35 @@ class Whitebox(object):
             g[:, 0] -= 1.0
             s0 = g[:, 0:1] * xm + g[:, 1:2] * xn                               # g @ W_cls per probe
         sk = xm if k_poschannel == 0 else xn
-        return self._weighted_subtree(eng, img_probes, seed_tensor, s0, xn, sk, topk, False, do_max_subtree,
-                                      do_mated_similarity_gating, do_mwp_to_saliency, sweep_batch)
+        run = self._weighted_subtree_native if native else self._weighted_subtree
+        return run(eng, img_probes, seed_tensor, s0, xn, sk, topk, False, do_max_subtree, do_mated_similarity_gating, do_mwp_to_saliency,
+                   sweep_batch)
+
+    def _weighted_subtree_native(self, eng, x, seed_tensor, s0, s1, sk, topk, verbose, do_max_subtree, do_mated_similarity_gating,
+                                 do_mwp_to_saliency, sweep_batch):
+        """_weighted_subtree as one engine call: selection, merge and (ebp_version 6) saliency conversion on the device; the visiting
+        order is NumPy's argsort of the layer weights, handed to the engine through a callback, so the selection is the reference's.  The
+        uint8 versions get the reference's PIL blur here on the host, as in _merge_subtrees."""
+        uint8 = self.convert_saliency_uint8
+        output = 'uint8' if uint8 else ('saliency' if do_mwp_to_saliency else 'mwp')
+        x, _ = eng._prep(x)
+        seeds = torch.stack([torch.as_tensor(v, dtype=torch.float32).reshape(x.shape[0], -1).to(eng.device) for v in (s0, s1, sk)], dim=0)
+        smap, top, w_valid, k_valid, n_valid = eng.weighted_subtree(x, seed_tensor, seeds, topk, gate_ge0=do_mated_similarity_gating,
+                                                                    do_max_subtree=do_max_subtree, output=output, sweep_batch=sweep_batch,
+                                                                    order='numpy')
+        smap, top = smap.cpu().numpy(), top.cpu().numpy()
+        res = []
+        for b in range(x.shape[0]):
+            k = int(n_valid[b])
+            P_img_valid = [top[b, i] for i in range(k)]
+            m = smap[b]
+            if uint8:
+                m = m.astype(np.uint8)
+                if do_mwp_to_saliency:
+                    m = self._mwp_to_saliency(m)
+                    P_img_valid = [self._mwp_to_saliency(P) for P in P_img_valid]
+            res.append((m, P_img_valid, [float(v) for v in w_valid[b, :k]], [int(v) for v in k_valid[b, :k]]))
+        return res
 
     def _weighted_subtree(self, eng, x, seed_tensor, s0, s1, sk, topk, verbose, do_max_subtree, do_mated_similarity_gating,
                           do_mwp_to_saliency, sweep_batch):
