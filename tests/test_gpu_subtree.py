@@ -199,7 +199,7 @@ print('DIGEST', h.hexdigest())
 
 
 def test_lazy_gradient_zeroing_against_the_eager_fill(gpu_device):
-    """The layerwise / prefix sweeps zero exactly the gradient rows a launch is about to read and nobody has written (engine.hip, run_backward) instead of
+    """The layerwise / prefix sweeps zero exactly the gradient rows a launch is about to read and nobody has written (backward.hip, run_backward) instead of
     the whole region.  XFR_POISON_G=1 NaN-fills the region first, so a row the bookkeeping misses would surface in the maps; XFR_EAGER_ZERO=1 is the old
     whole-region fill.  Both are latched at first use, hence one process each: the three runs (default, poisoned, eager) must agree bit for bit."""
     import subprocess

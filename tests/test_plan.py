@@ -231,8 +231,8 @@ FUSION_TABLE = [
 
 @pytest.mark.parametrize('row', FUSION_TABLE, ids=lambda r: '%s-%s-%s' % (r[0], r[1], r[2]))
 def test_fusion_passes_table(row):
-    """The planner's fusion passes (engine.hip: fuse_copy_forwarding, fuse_pool_pair, fuse_downsample_avgpool / _projection, fuse_stage_head_relu /
-    _branch, fuse_merge_to_fixed_point; lean_prepare), one table row per backbone / mode / switchable pass: what each pass removes is pinned as a
+    """The planner's fusion passes (plan_fuse.hip: fuse_copy_forwarding, fuse_pool_pair, fuse_downsample_avgpool / _projection, fuse_stage_head_relu /
+    _branch, fuse_merge_to_fixed_point; forward.hip: lean_prepare), one table row per backbone / mode / switchable pass: what each pass removes is pinned as a
     launch count, so a change to one pass shows up as the row it moves."""
     import re
     from xfr_amd.models import lightcnn, resnet, resnet50_128

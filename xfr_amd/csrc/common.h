@@ -66,7 +66,7 @@ enum {
 };
 enum { HOOK_DIV = 0, HOOK_RELU = 1, HOOK_PASS = 2,
        // The "lean" forms of a hook nobody observes (no P store, trace, prior or capture): the probe forward left, instead of the hook's literal
-       // operands a and x, what the sweep needs of them (ConvParams::dualacc; engine.hip lean_rewrite).  Within one ulp per hook of the
+       // operands a and x, what the sweep needs of them (ConvParams::dualacc; plan_fuse.hip lean_rewrite_chain).  Within one ulp per hook of the
        // literal expression for every a a real network produces -- gated by the golden tolerances, not bit for bit.
        HOOK_Q = 3,          // g = relu(g) * |p0[a]|:  p0 holds q = a / (x + eps), computed once in the probe forward (BatchNorm and ReLU hooks)
        HOOK_GATE = 4,       // g = p0[a] > 0 ? relu(g) : 0:  a hook whose x IS its a -- a * relu(g) / (a + eps) = relu(g) wherever a > 1.7e-9, 0 at a = 0

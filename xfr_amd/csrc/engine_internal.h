@@ -1,0 +1,326 @@
+// engine_internal.h -- what the host translation units of the engine share: the planner's records (Hook, Tensor, OpRec, BwdStep, BwdPlan), the engine
+// object, the error helpers and the functions that cross files.  Nothing here is part of the C ABI (include/xfr_amd.h).
+//   plan.hip           shape inference, hook table, workspace / arena layout, the un-fused backward schedule (device-free)
+//   plan_fuse.hip      the fusion passes over that schedule and the lean rewrite (device-free)
+//   forward.hip        forward fusers and the forward executor
+//   backward.hip       chain resolution and the sweep executor
+//   engine.hip         the C ABI: create / destroy / weights / setters / forward / EBP / contrastive / triplet / uint8 / profiling
+//   subtree.hip        the C ABI: layerwise and weighted-subtree EBP
+//   comm.hip           the C ABI: the RCCL binding
+//   plan_describe.hip  the C ABI: xfr_plan_describe
+#pragma once
+#include "../../include/xfr_amd.h"
+#include "common.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <string>
+#include <vector>
+
+namespace xfr {
+
+extern thread_local std::string g_err;      // text of the calling thread's last error (xfr_last_error); defined in engine.hip
+xfr_status fail(xfr_status st, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                                     \
+    do {                                                                                                  \
+        hipError_t _e = (expr);                                                                           \
+        if (_e != hipSuccess)                                                                             \
+            return fail(_e == hipErrorOutOfMemory ? XFR_OOM : XFR_HIP_ERROR, "%s failed: %s (%s:%d)", #expr, \
+                        hipGetErrorString(_e), __FILE__, __LINE__);                                       \
+    } while (0)
+
+enum PState { PS_EQ = 0, PS_RELU = 1, PS_OTHER = 2 };
+
+struct Hook {
+    int op;        // hooked module call
+    int j;         // which input of that call
+    int a_tensor;  // tensor providing a (and x): the LAST input of the call (whitebox.py:379-381 late binding)
+};
+
+struct Tensor {
+    int C = 0, H = 0, W = 0;
+    int producer = -1;
+    std::vector<int> consumers;
+    bool nonneg = false;
+    int pstate = PS_OTHER;
+    int alias = -1;          // shares T storage with this tensor (in-place ReLU, Split)
+    int prefix_of = -1;      // T storage = the leading channels of this tensor's (the pooled shortcut inside its zero-padded form; layout_workspace)
+    size_t t_off = 0, pv_off = 0, g_off = 0;   // offsets (floats) into the workspace
+    bool need_pv = false;
+    std::vector<Hook> hooks;
+    long per_n() const { return (long)C * H * W; }
+    int HW() const { return H * W; }
+};
+
+struct OpRec {
+    xfr_op_desc d;
+    // packed parameter offsets (floats) into the arena; -1 if absent
+    long w_true = -1, w_pos = -1, w_bwd = -1, w_bwd_true = -1;   // w_bwd_true: true-weight backward pack (plain gradients)
+    long b_true = -1, b_pos = -1;            // conv/linear bias and relu(bias)
+    long bn_alpha_t = -1, bn_beta_t = -1, bn_alpha_p = -1, bn_beta_p = -1, bn_beta_pb = -1;
+    int ldw = 0, ldb = 0;
+    bool tap_fwd = false, tap_bwd = false;   // K packed tap-major (kh,kw,ci) for the forward / backward-data GEMM
+    bool tap4_fwd = false;                   // image stems (Cin 3 or 4): K packed (kh,kw,4 channel slots); Kf = rows of the forward pack
+    int Kf = 0;
+    int Cin = 0, K = 0, Kb = 0;
+    size_t idx_off = 0;                      // maxpool argmax (bytes into idx workspace)
+    size_t norm_off = 0;                     // normalize: norms (floats into misc workspace)
+    int pair = 0;                            // MaxFeatureMap convolution (Conv -> Split -> max of halves, lightcnn.py:48-62): Co = cout / 2; its forward
+                                             // pack (and bias) holds the output channels interleaved (column 2c = channel c, 2c+1 = channel c + Co)
+    int pair_split = -1, pair_max = -1;      // the Split and G_MAXHALVES ops behind it
+    bool fuse_relu = false;                  // forward: the following in-place ReLU is applied in this op's kernel
+    bool relu_fused_away = false;            // forward: this ReLU is executed by its producer
+};
+
+enum StepKind { ST_EW, ST_CONV_BWD, ST_MAXPOOL_BWD, ST_AVGPOOL_BWD, ST_COPY, ST_MAXHALVES_BWD, ST_NORMALIZE_BWD, ST_ZERO };
+
+
+struct BwdStep {
+    int kind;
+    int op = -1;
+    int src_t = -1, dst_t = -1;
+    int accumulate = 0;
+    long copy_elems_per_sb = 0;   // ST_COPY: channels to copy (prefix), dst/src channel counts differ for concat
+    // ST_EW: symbolic chain (resolved to pointers at run time)
+    struct Sym { int type; int action; int t0; int x_t; float f; int op; int slot; bool tap; };
+    std::vector<Sym> chain;   // ST_EW: the chain; ST_CONV_BWD: epilogue chain fused into the GEMM (may be empty)
+    int ew_t = -1;     // tensor whose shape the chain runs over
+    bool compact = false;   // ST_CONV_BWD of a 1x1 / stride 2 convolution: the result stays on the sampled grid, dense, at the start of dst_t's gradient
+                            // region (the chain head EW_AVGUP_IN of the launch that follows puts it in place)
+};
+
+struct BwdPlan {
+    int seed_tensor = -1;
+    int mode = -1;
+    bool plain = false;              // true-weight gradients without hooks (whitebox.py:652-676 dA lists)
+    std::vector<int> firing_tensor;  // tensor whose gradient each firing sees
+    std::vector<BwdStep> steps;      // one launch per step, no cross-kernel fusion (used when tracing)
+    std::vector<BwdStep> fused;      // after copy forwarding and chain -> chain merging
+    std::vector<BwdStep> fused_gemm; // ... and with the chains that follow a backward GEMM run in its epilogue
+    std::vector<BwdStep> fused_gemm_nofan; // the same without the MaxFeatureMap fan-out (a compiled-only epilogue step): what the interpreted epilogues run
+    std::vector<int> firing_kinds;   // xfr_op_kind per firing, reference order
+    std::vector<int> firing_ops;     // hooked module call (op index) per firing: Whitebox.P_layername is str(module) of these (whitebox.py:393)
+    int n_firings = 0;
+    int fan_ok = -1;                 // does every fan-out epilogue of fused_gemm have a compiled signature (-1: not checked yet; fanout_compiled)
+    // The lean schedule (xfr_engine_set_lean): the probe forward stores quotients instead of hook operands, the sweep reads them.
+    int lean_state = -1;             // -1 not prepared, 0 does not apply to this plan, 1 ready (lean_prepare)
+    std::vector<char> lean_q;        // per tensor: 1 = its T storage holds a / (x + eps) of the BatchNorm hook on it (sign bit: lean_final <= 0),
+                                     // 2 = its Pv storage holds a / (x + eps) of the in-place ReLU hook behind it
+    std::vector<int> lean_final;     // per tensor with lean_q 1: root of the tensor whose positivity the sign bit records (-1: none)
+    std::vector<BwdStep> fused_gemm_lean;
+};
+
+}  // namespace xfr
+using namespace xfr;
+
+struct xfr_engine {
+    int device = 0;
+    int max_batch = 0;
+    int in_c = 0, in_h = 0, in_w = 0;
+    std::vector<OpRec> ops;
+    std::vector<Tensor> tens;
+    int n_weights = 0;
+    // parameters
+    float* arena = nullptr;
+    size_t arena_floats = 0;
+    bool weights_loaded = false;
+    // workspace
+    float* fwd_ws[3] = {nullptr, nullptr, nullptr};      // [0]: the whole workspace (forward slot 0, gradients, scratch); [1], [2]: the forward regions of pipeline slots 1 and 2
+    float*& ws = fwd_ws[0];
+    size_t ws_floats = 0;
+    uint8_t* fwd_idx[3] = {nullptr, nullptr, nullptr};   // max-pool argmax bytes, per forward slot
+    size_t idx_bytes = 0;
+    size_t x_off = 0, seed_off = 0, tap_off = 0, pooled_off = 0, blur_a_off = 0, blur_b_off = 0, misc_off = 0, thr_off = 0;
+    double* dbl_ws = nullptr;      // sums [2*maxB] + trace
+    size_t trace_cap = 0;          // firings capacity
+    void* trunc_ws = nullptr;
+    // mode
+    int mode = XFR_MODE_AFFINEONLY_WITH_PRIOR;
+    float eps = 1e-16f;
+    int with_bias = 0;
+    bool need_dirty = true;
+    // plans
+    std::deque<BwdPlan> plans;         // deque: get_plan() hands out pointers that must survive later insertions
+    // trace / profile
+    int trace_on = 0;
+    // per-call context of the backward sweep ("next" rows: layerwise / weighted-subtree EBP)
+    // xfr_engine_hold_forward: the forward state of (held_x, held_B, held_last) is still in slot 0
+    bool hold_forward = false, held_pos = false;
+    const float* held_x = nullptr;
+    int held_B = 0, held_last = -1;
+    hipStream_t held_stream = nullptr;
+    bool lazy_zero = false;                           // prefix sweeps: run_backward zeroes un-written gradient rows on demand (xfr_layerwise_ebp)
+    std::vector<int> rc_active;                       // layerwise sweeps in ascending firing order: stream j (all its samples) is identically zero before firing rc_active[j]
+    int rc_n = 1;                                     // samples per stream of the current layerwise batch
+    size_t g_begin = 0, g_end = 0;                    // the gradient region of the workspace (floats)
+    // priors / captures of the current sweep: tables [n_firings][tab_sb] over the gradient rows sb (stream * n + sample),
+    // staged in pinned host memory and copied once per call (common.h: EwStep::prior_elem / cap_elem)
+    bool rc_priors = false, rc_caps = false;
+    int tab_sb = 0;                                   // row length of the tables of the current call
+    std::vector<char> rc_prior_row, rc_cap_row;       // per firing: does the row hold any entry?
+    int rc_dense_slot = -1;                           // firing that carries the dense prior (-1: none)
+    const float* rc_prior_dense = nullptr;            // dense prior tensor (single sweep of one image)
+    int *tab_elem_h = nullptr, *tab_elem_d = nullptr; // prior element (or capture element) per (firing, row); -1: none
+    float *tab_val_h = nullptr, *tab_val_d = nullptr; // prior value per (firing, row)
+    size_t tab_cap = 0;                               // entries allocated
+    hipEvent_t ev_tab = nullptr;                      // the last host-to-device table copy
+    float* cap_dev = nullptr;                         // [n_firings][tab_sb] captured values
+    float* stat_v = nullptr;                          // [n_firings][max_batch]
+    int* stat_i = nullptr;
+    void* stat_scratch = nullptr;
+    StatDesc* stat_desc = nullptr;                    // [n_firings] tensor descriptors + firing -> tensor map of the last plan used
+    int* stat_f2u = nullptr;
+    const void* stat_plan = nullptr;
+    int stat_nu = 0;
+    int store_slot = -1;                              // firing whose full P tensor is kept in store_dev
+    float* store_dev = nullptr;
+    int store_tensor = -1, store_sb = 0;
+    // xfr_weighted_subtree_ebp: row-max keys of a round (device + pinned host), the round's gather pairs and the merge table (device + pinned
+    // host), and the top-k store used when the caller passes no top_dev (grown on demand)
+    unsigned *wst_key_d = nullptr, *wst_key_h = nullptr;
+    int *wst_pairs_d = nullptr, *wst_pairs_h = nullptr;
+    SubtreeSlot *wst_tab_d = nullptr, *wst_tab_h = nullptr;
+    int *wst_cnt_d = nullptr, *wst_cnt_h = nullptr;
+    size_t wst_tab_cap = 0;
+    float* wst_store = nullptr;
+    size_t wst_store_floats = 0;
+    std::vector<char> is_hook_a;       // per tensor: some hook takes its a (and x) from this tensor's forward values
+    std::vector<char> fwd_done;        // per forward pass: ops whose work was folded into an earlier GEMM epilogue
+    std::vector<char> pos_done;        // ... and whose positive-pass output was produced there too
+    int fwd_last_op = 0;
+    // tail-balancing scratch (conv_gemm.hip), one per stream that launches GEMMs; kernels on one stream serialise,
+    // so consecutive launches share it
+    struct TailWs { hipStream_t s; float* ws; unsigned* cnt; };
+    TailWs tail_ws[8];
+    int n_tail_ws = 0;
+    bool tail_balance = true;          // xfr_engine_set_tail_balance
+    bool split_forward = true;         // xfr_engine_set_forward_split: forward-only batches of >= 32 images as two halves on the internal streams
+    bool interpret_chains = false;     // xfr_engine_set_epilogue_fusion bit 2: fused chains run through the interpreted epilogue (tests)
+    bool planning_only = false;        // xfr_plan_describe: list what the planner WOULD fuse, whatever the signature table holds
+    bool fuse_probe_fwd = true;        // probe forward (with the positive pass): BatchNorm / ReLU in the (dual) GEMM's epilogue (STORE raw, [FORK positive
+                                       // BatchNorm], affine, clamp).  Round 3, MI355X: +0.6 % maps/s on ResNet-101, +2.2 % on ResNet-50-128d, bit-identical
+    bool fuse_fwd_only = true;         // forward-only runs: BatchNorm / residual add / ReLU in the GEMM epilogue
+    bool hoist_shortcut = true;        // down-sampling blocks: the shortcut (average pool, channel padding) is computed BEFORE the main path's last
+                                       // convolution, so that the residual add joins its epilogue like in every other block (bit 8 of the fusion mask)
+    bool direct_stem = true;           // Light-CNN's 1-channel 5x5 first layer as a direct convolution (xfr_engine_set_epilogue_fusion bit 4 clear; tests set it)
+    bool fuse_avgup = true;            // down-sampling blocks: slice copy + pooled hook + average-pool VJP + strided GEMM's read-modify-write as the head of the
+                                       // hook chain that follows (EW_AVGUP_IN; xfr_engine_set_epilogue_fusion bit 6 clear)
+    bool fuse_branch = true;           // projection-shortcut blocks: the main path's hook chain as a side branch of the Add-output GEMM's epilogue (EW_STORE actions
+                                       // 1 / 2; xfr_engine_set_epilogue_fusion bit 7 clear)
+    // uint8 entry points (xfr_forward_u8 / xfr_triplet_contrastive_u8): the image pointer handed to the forward is uint8 H x W x C and the layout
+    // kernel in front of the first convolution does the reference's preprocessing arithmetic (xfr_engine_set_u8_preprocess)
+    bool u8_on = false;
+    bool u8_set = false;
+    U8Pre u8_pre;
+    bool split_any_grid = false;       // xfr_engine_set_split_gemm mode + 4: covered layers take the bf16x6 kernel whatever the launch's grid (tests, tuning)
+    int split_mask = 3;                // xfr_engine_set_split_gemm: which covered layers run the bf16x6 kernel (conv_gemm_split.hip K17) -- bit 0 the forward
+                                       // convolutions, bit 1 the sweep's backward-data GEMMs; both by default since round 6 (short in-pipe sums)
+    bool lean = true;                  // xfr_engine_set_lean: plain sweeps (no trace / prior / capture / stored firing, batch % 4 == 0) take the lean schedule
+    const BwdPlan* lean_cur = nullptr; // the plan whose lean tables the running probe forward / sweep follow (null: literal)
+    bool lean_decide = false;          // lean_prepare's dry run of the probe forward: decide per convolution, record in lean_q_run / lean_final_run
+    bool dry_run = false;              // ... which launches nothing
+    bool lean_missing_sig = false;     // ... and found a lean epilogue without a compiled signature
+    long lean_launches = 0;            // dual-accumulator launches so far (xfr_engine_lean_stats)
+    std::vector<char> lean_q_run;
+    std::vector<int> lean_final_run;
+    bool pair_tiles = true;            // backward chain GEMMs over two streams walk their m-tiles stream-interleaved (xfr_engine_set_epilogue_fusion bit 5 clear)
+    bool fuse_pools = true;            // Light-CNN's maxpool + avgpool pair: one forward kernel (xfr_engine_set_epilogue_fusion bit 0 switches it with the rest)
+    bool fuse_gemm_epilogue = true;    // hook chains that follow a backward GEMM run in its (vector) epilogue
+                                       // (both: xfr_engine_set_epilogue_fusion; DESIGN.md section 6 has the measurements)
+    int last_trace_firings = 0, last_trace_sb = 0;
+    std::vector<int> last_trace_kinds;
+    int profile_on = 0;
+    std::string profile_csv;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::vector<ConvParams> ev_params;
+    std::vector<int> ev_cfg;           // the configuration each profiled launch really ran
+    double fam_ms[2] = {0.0, 0.0}, fam_flops[2] = {0.0, 0.0};      // last profiled run, by kernel family: [0] fp32 MFMA, [1] bf16x6
+    long fam_launches[2] = {0, 0};
+    size_t ev_used = 0;
+    double prof_flops = 0.0;
+    double last_gemm_ms = 0.0;
+    long last_gemm_launches = 0;
+    double last_gemm_flops = 0.0;
+
+    float* t_bank = nullptr;       // when set, true activations live in this bank (gallery forward of a triplet step)
+    float* ws_enc = nullptr;       // second bank of true activations (T region only), allocated on first use
+    size_t t_region_floats = 0;
+    hipStream_t s_a = nullptr, s_b = nullptr;
+    // xfr_triplet_contrastive_u8_host: the engine's own copy stream and one uint8 staging buffer per forward slot -- fresh inputs keep the cross-call overlap
+    hipStream_t s_copy = nullptr;
+    uint8_t* u8_stage[3] = {nullptr, nullptr, nullptr};
+    size_t u8_stage_bytes = 0;
+    hipEvent_t ev_copied[3] = {nullptr, nullptr, nullptr}, ev_stage_a[3] = {nullptr, nullptr, nullptr}, ev_stage_b[3] = {nullptr, nullptr, nullptr};
+    bool stage_busy[3] = {false, false, false};
+    hipEvent_t inputs_event = nullptr;   // one-shot, set by the _host entry point: the inputs of THIS call are complete when it fires (instead of the caller's stream order)
+    int stage_slot = -1;                 // ... and the staging slot its forwards read
+    hipEvent_t last_copied = nullptr;    // xfr_engine_wait_inputs_copied
+    hipEvent_t ev_fork = nullptr, ev_a = nullptr, ev_b = nullptr;
+    // cross-step pipelining (xfr_engine_set_pipeline): two forward slots (T, Pv, norms, argmax) so that the forward of
+    // triplet call i+1 may run while the backward sweep of call i still reads slot i%2
+    bool pipeline = false;
+    bool pipeline_all = false;     // level 2: xfr_ebp / xfr_contrastive calls are pipelined too
+    bool inputs_ready = false;     // xfr_engine_set_inputs_ready: the NEXT level-2 call may read x_dev without waiting for the caller's stream (one-shot)
+    int cur_slot = 0;
+    long seq = 0;
+    int n_slots = 2;               // xfr_engine_set_pipeline bit 2: three forward slots (the forwards may run two calls ahead of the sweep)
+    size_t fwd_region_floats = 0;
+    float* seedbuf[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev_slot_done[3] = {nullptr, nullptr, nullptr};
+    bool slot_pending[3] = {false, false, false};
+    float* fwd_base() { return fwd_ws[cur_slot]; }
+    uint8_t* idx_base() { return fwd_idx[cur_slot]; }
+    float* T(int t) { const Tensor& x = tens[t]; return (t_bank ? t_bank : fwd_base()) + tens[x.alias >= 0 ? root(t) : t].t_off; }
+    float* Pv(int t) { return fwd_base() + tens[t].pv_off; }
+    float* misc() { return fwd_base() + misc_off; }
+    float* G(int t) { return ws + tens[t].g_off; }
+    int root(int t) const { while (tens[t].alias >= 0) t = tens[t].alias; return t; }
+    size_t max_per_n() const { size_t m = 0; for (const Tensor& x : tens) m = std::max(m, (size_t)x.per_n()); return m; }      // elements per sample of the largest tensor
+};
+
+namespace xfr {
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline bool is_affine_name(int kind)
+{   // whitebox.py:399/:409: 'Conv' | 'Linear' | 'AvgPool' | 'BatchNorm' in str(module)
+    return kind == XFR_OP_CONV || kind == XFR_OP_LINEAR || kind == XFR_OP_AVGPOOL || kind == XFR_OP_BATCHNORM;
+}
+
+// plan.hip (device-free)
+xfr_status build(xfr_engine* e, const xfr_op_desc* ops, int n_ops);
+void compute_need(xfr_engine* e);
+xfr_status layout_workspace(xfr_engine* e);
+xfr_status layout_arena(xfr_engine* e);
+xfr_status get_plan(xfr_engine* e, int seed_tensor, BwdPlan** out, bool plain = false);
+
+// plan_fuse.hip (device-free)
+void fuse_plan(xfr_engine* e, BwdPlan& plan);
+void lean_rewrite_plan(xfr_engine* e, BwdPlan& plan);
+
+// forward.hip
+xfr_status run_conv(xfr_engine* e, const ConvParams& p_in, hipStream_t s);
+void conv_geometry(xfr_engine* e, int k, int NB, ConvParams& p);
+void fuse_forward_only(xfr_engine* e, int k, int B, ConvParams& p, hipStream_t s);
+void fuse_probe_forward(xfr_engine* e, int k, int B, ConvParams& p, hipStream_t s, bool dual = false, bool lean_try = true);
+bool fuse_mfm_forward(xfr_engine* e, int k, int B, bool keep_raw, ConvParams& p);
+xfr_status forward_all(xfr_engine* e, const float* x_dev, int B, int last_tensor, bool with_pos, hipStream_t s);
+void lean_prepare(xfr_engine* e, BwdPlan& plan, int B);
+bool lean_applies(xfr_engine* e, BwdPlan& plan, int B);
+
+// backward.hip
+void resolve_chain(xfr_engine* e, const std::vector<BwdStep::Sym>& syms, EwChain& ch, double* trace, int SB, bool plain = false);
+xfr_status run_backward(xfr_engine* e, BwdPlan& plan, int B, int S, hipStream_t s);
+
+// engine.hip
+xfr_status check_run(xfr_engine* e, const void* x, int n);
+xfr_status fence_slot0(xfr_engine* e, hipStream_t s);
+xfr_status ebp_core(xfr_engine* e, const float* x_dev, int n, int S, int seed_tensor, const float* seed_dev, hipStream_t s);
+void presplit_weights(xfr_engine* e);
+
+}  // namespace xfr
