@@ -308,8 +308,18 @@ bool launch_conv_gemm(const ConvParams& p, hipStream_t s);
 // 2 = MaxFeatureMap step (EW_MAXPAIR / EW_MAXHALF_OUT) without a compiled epilogue.  No device work.
 int conv_gemm_cannot_launch(const ConvParams& p);
 const char* conv_gemm_refusal(int why);
+// Configuration ids: which GEMM kernel a launch takes.  The values are public -- ConvParams::force_cfg, XFR_CFG_REMAP, the launch log and profile CSV,
+// tools/conv_sweep.py --cfgs, xfr_debug_conv -- and do not change.
+enum ConvCfg {
+    CFG_K16 = 4,       // 64 x 64 block tile, 16-deep K-steps, three-stage ring
+    CFG_K32 = 5,       // ... 32-deep K-steps
+    CFG_KS_8_3 = 6,    // intra-workgroup split-K kernel, (BK, ring stages) = (8, 3)
+    CFG_KS_4_4 = 7,    // ... (4, 4)
+    CFG_BF16X6 = 9,    // the bf16x6 split GEMM (conv_gemm_split.hip)
+    CFG_ROW32 = 12,    // 32 x 128 block tile (four waves side by side along m)
+};
 int conv_gemm_pick_cfg(const ConvParams& p);
-int conv_gemm_last_cfg();       // the configuration the calling thread's last launch_conv_gemm really ran (9: the bf16x6 kernel)
+int conv_gemm_last_cfg();       // the configuration the calling thread's last launch_conv_gemm really ran (CFG_BF16X6: the bf16x6 kernel)
 // bf16x6 split GEMM (conv_gemm_split.hip K17, configuration 9; ConvParams::split_ok).  The fp32 pack of a covered layer needs bf16 planes: the engine
 // builds them when the weights arrive (conv_gemm_presplit; a pack that has none at a launch gets them there, on that launch's stream, which is then
 // drained once).  conv_gemm_forget_split: the packs inside [lo, lo + bytes) changed or go away -- drop their planes.

@@ -31,7 +31,6 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
-#include <unordered_map>
 #include <vector>
 #include "common.h"
 #include <cstdio>
@@ -357,7 +356,7 @@ __global__ __launch_bounds__(NT, CHAIN == 0 ? 1 : (CHAIN == 1 ? 7 : (CHAIN == 4 
     stamp(p, wave, lane, 2);
     stamp(p, wave, lane, 3);
 
-    block_epilogue<CHAIN, true, ROW>(p, acc, smem, tid, lane, wave, co0, m0, half, tail_t, part, nparts, osel, bsel, DUAL ? &accp[0][0] : nullptr);      // the launcher allocates at least the four 32 x 36 tiles
+    block_epilogue<CHAIN, ROW>(p, acc[0][0], smem, tid, lane, wave, co0, m0, half, tail_t, part, nparts, osel, bsel, DUAL ? &accp[0][0] : nullptr);      // the launcher allocates at least the four 32 x 36 tiles
     stamp(p, wave, lane, 4);
 }
 
@@ -638,11 +637,11 @@ __global__ __launch_bounds__(NT, CHAIN == 4 ? XFR_KS_DUAL_WAVES : 5) void conv_g
 
     // ---- exchange: park the three foreign quadrants in the own ring, meet, gather the own quadrant in K order
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    v16f accq[1][1];
-    if (wave == 0) ks_exchange<0, WAVE_LDS>(smem, acc, lane, accq[0][0]);
-    else if (wave == 1) ks_exchange<1, WAVE_LDS>(smem, acc, lane, accq[0][0]);
-    else if (wave == 2) ks_exchange<2, WAVE_LDS>(smem, acc, lane, accq[0][0]);
-    else ks_exchange<3, WAVE_LDS>(smem, acc, lane, accq[0][0]);
+    v16f accq;
+    if (wave == 0) ks_exchange<0, WAVE_LDS>(smem, acc, lane, accq);
+    else if (wave == 1) ks_exchange<1, WAVE_LDS>(smem, acc, lane, accq);
+    else if (wave == 2) ks_exchange<2, WAVE_LDS>(smem, acc, lane, accq);
+    else ks_exchange<3, WAVE_LDS>(smem, acc, lane, accq);
     v16f accpq;
     if constexpr (DUAL) {
         __syncthreads();          // every wave has gathered its W quadrant: the rings may be overwritten with the relu(W) tiles
@@ -653,10 +652,9 @@ __global__ __launch_bounds__(NT, CHAIN == 4 ? XFR_KS_DUAL_WAVES : 5) void conv_g
     }
     // the epilogues start with a workgroup barrier before they reuse the LDS (tail parts: before the arrival flag)
     stamp(p, wave, lane, 3);
-    block_epilogue<CHAIN, true>(p, accq, smem, tid, lane, wave, co0, m0, half, tail_t, part, nparts, osel, bsel, DUAL ? &accpq : nullptr);
+    block_epilogue<CHAIN>(p, accq, smem, tid, lane, wave, co0, m0, half, tail_t, part, nparts, osel, bsel, DUAL ? &accpq : nullptr);
     stamp(p, wave, lane, 4);
 }
-
 
 int num_cus()
 {
@@ -723,9 +721,7 @@ void warn_interpreted(const ConvParams& q)
     static std::atomic<int> said{0};
     // (a launch whose rows are not float4-aligned -- M, or images x pixels, not a multiple of 4: stage 4 of a batch of one -- runs the interpreter BY DESIGN:
     // the compiled epilogues load and store float4; nothing to regenerate, nothing to say)
-    const int ohw = q.OH * q.OW;
-    const bool vec_ok = (q.M & 3) == 0 && ((q.chain_B * ohw) & 3) == 0 && ((q.out_nb * ohw) & 3) == 0;
-    if (q.chain_interpret || !vec_ok || getenv("XFR_QUIET") || said.exchange(1)) return;
+    if (q.chain_interpret || !rows_vec4(q) || getenv("XFR_QUIET") || said.exchange(1)) return;
     uint16_t codes[XFR_MAX_EW_STEPS];
     const int n = ew_chain_codes(q.chain, codes);
     fprintf(stderr, "xfr_amd: a GEMM launch (Cout %d, K %d, M %d) runs its %d-step fused chain through the INTERPRETED epilogue: no compiled signature [", q.CoutTot, q.K, q.M, q.chain.n);
@@ -742,9 +738,7 @@ int plan_chain(ConvParams& q)
     EwLoads wide_ld;
     ew_plan_loads(wide, q.out0, wide_ld, EW_FWD_SLOTS_WIDE);
     ew_plan_loads(q.chain, q.out0, q.chain_ld);
-    const int ohw = q.OH * q.OW;
-    const bool vec_ok = (q.M & 3) == 0 && ((q.chain_B * ohw) & 3) == 0 && ((q.out_nb * ohw) & 3) == 0;
-    q.chain_sig = (q.accumulate || !vec_ok || q.chain_interpret) ? -1 : conv_gemm_chain_sig(wide);
+    q.chain_sig = (q.accumulate || !rows_vec4(q) || q.chain_interpret) ? -1 : conv_gemm_chain_sig(wide);
     if (q.chain_sig >= 0) { q.chain = wide; q.chain_ld = wide_ld; }
     if (q.nhalves == 2 && q.chain_sig < 0) return 1;      // a dual launch can only carry a compiled chain: the caller un-fuses
     if ((q.dualacc != 0) != (q.chain_sig >= 0 && chain_sig_is_dual(q.chain_sig))) return 3;   // lean steps <=> two accumulator tiles
@@ -753,12 +747,14 @@ int plan_chain(ConvParams& q)
     return 0;
 }
 
-template <int TCO, int TM, int BK, int NST, int MODE>
-bool launch_one(const ConvParams& p, hipStream_t s)
+// One launch of a tile kernel family.  The grid: n_co x n_m tiles, the last tiles % CUs of them cut into K-parts (pick_tail_split).  The chain's plan,
+// the launch counters, then the instantiation for the launch's (RELU, CHAIN): kern(relu, chain) maps the two -- std::integral_constant values -- to
+// the kernel.  HAS_DUAL: the family has a dual-accumulator (CHAIN 4) instantiation.  false: refused, nothing was launched.
+template <int TCO, int TM, int BK, bool HAS_DUAL, class Kern>
+bool launch_tiles(const ConvParams& p, hipStream_t s, const size_t lds, Kern kern)
 {
     const int n_co = ((p.CoutTot + TCO - 1) / TCO) * p.nhalves;
     const int n_m = (p.M + TM - 1) / TM;
-    const size_t lds = std::max((size_t)NST * BK * (TCO + TM) * sizeof(float) + (MODE == MODE_GEN ? 512 * sizeof(int2) : 0), (size_t)4 * 32 * 36 * sizeof(float));
     ConvParams q = p;
     int grid = n_co * n_m;
     q.tail_q = 0;
@@ -772,79 +768,48 @@ bool launch_one(const ConvParams& p, hipStream_t s)
             grid = q.tail_q + r * S;
         }
     }
+    auto go = [&](auto relu, auto chain) {
+        const auto kernel = kern(relu, chain);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
+        return true;
+    };
+    constexpr std::false_type plain_in{};
     if (p.dualacc && (q.chain.n == 0 || p.nhalves != 1 || p.relu_in)) return false;
-    if constexpr ((TCO == 64 && TM == 64) || (TCO == 32 && TM == 128)) {
-        if (q.chain.n > 0) {      // fused micro-program (no relu_in)
-            if (plan_chain(q)) return false;
-            g_conv_chain_launches[q.chain_sig >= 0 ? 0 : 1]++;
-            if (q.chain_sig < 0) warn_interpreted(q);
-            if constexpr (TCO == 64 && MODE != MODE_TAP4 && MODE != MODE_GEN) {
-                if (q.dualacc) {
-                    hipLaunchKernelGGL((conv_gemm_kernel<TCO, TM, BK, NST, MODE, false, 4>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-                    return true;
-                }
-            }
-            if (q.dualacc) return false;
-            if (q.chain_sig >= 0 && chain_sig_is_mfm(q.chain_sig))
-                hipLaunchKernelGGL((conv_gemm_kernel<TCO, TM, BK, NST, MODE, false, 3>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-            else if (q.chain_sig >= 0)
-                hipLaunchKernelGGL((conv_gemm_kernel<TCO, TM, BK, NST, MODE, false, 1>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-            else
-                hipLaunchKernelGGL((conv_gemm_kernel<TCO, TM, BK, NST, MODE, false, 2>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-            return true;
-        }
-    }
-    if (p.relu_in)
-        hipLaunchKernelGGL((conv_gemm_kernel<TCO, TM, BK, NST, MODE, true, 0>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-    else
-        hipLaunchKernelGGL((conv_gemm_kernel<TCO, TM, BK, NST, MODE, false, 0>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-    return true;
-}
-
-// the split-K kernel: same grid, tail split and chain selection as launch_one
-template <int BK, int NST, int MODE>
-bool launch_one_ks(const ConvParams& p, hipStream_t s)
-{
-    constexpr int TCO = 64, TM = 64;
-    const int n_co = ((p.CoutTot + TCO - 1) / TCO) * p.nhalves;
-    const int n_m = (p.M + TM - 1) / TM;
-    constexpr int RING = NST * BK * (TCO + TM);
-    const size_t lds = (size_t)4 * (RING > 2048 ? RING : 2048) * sizeof(float);
-    ConvParams q = p;
-    int grid = n_co * n_m;
-    q.tail_q = 0;
-    q.tail_s = 1;
-    {
-        const int S = pick_tail_split(p, n_co * n_m, (p.K + BK - 1) / BK, (size_t)TCO * TM * sizeof(float) * (p.dualacc ? 2 : 1));
-        if (S > 1) {
-            const int r = (n_co * n_m) % num_cus();
-            q.tail_q = n_co * n_m - r;
-            q.tail_s = S;
-            grid = q.tail_q + r * S;
-        }
-    }
-    if (p.dualacc && (q.chain.n == 0 || p.nhalves != 1 || p.relu_in)) return false;
-    if (q.chain.n > 0) {
+    if (q.chain.n > 0) {      // fused micro-program (no relu_in)
         if (plan_chain(q)) return false;
         g_conv_chain_launches[q.chain_sig >= 0 ? 0 : 1]++;
         if (q.chain_sig < 0) warn_interpreted(q);
         if (q.dualacc) {
-            hipLaunchKernelGGL((conv_gemm_ks_kernel<BK, NST, MODE, false, 4>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-            return true;
+            if constexpr (HAS_DUAL) return go(plain_in, std::integral_constant<int, 4>{});
+            else return false;
         }
-        if (q.chain_sig >= 0 && chain_sig_is_mfm(q.chain_sig))
-            hipLaunchKernelGGL((conv_gemm_ks_kernel<BK, NST, MODE, false, 3>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-        else if (q.chain_sig >= 0)
-            hipLaunchKernelGGL((conv_gemm_ks_kernel<BK, NST, MODE, false, 1>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-        else
-            hipLaunchKernelGGL((conv_gemm_ks_kernel<BK, NST, MODE, false, 2>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-        return true;
+        if (q.chain_sig >= 0 && chain_sig_is_mfm(q.chain_sig)) return go(plain_in, std::integral_constant<int, 3>{});
+        if (q.chain_sig >= 0) return go(plain_in, std::integral_constant<int, 1>{});
+        return go(plain_in, std::integral_constant<int, 2>{});
     }
-    if (p.relu_in)
-        hipLaunchKernelGGL((conv_gemm_ks_kernel<BK, NST, MODE, true, 0>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-    else
-        hipLaunchKernelGGL((conv_gemm_ks_kernel<BK, NST, MODE, false, 0>), dim3(grid), dim3(NT), lds, s, q, n_co, n_m);
-    return true;
+    if (p.relu_in) return go(std::true_type{}, std::integral_constant<int, 0>{});
+    return go(plain_in, std::integral_constant<int, 0>{});
+}
+
+template <int TCO, int TM, int BK, int NST, int MODE>
+bool launch_one(const ConvParams& p, hipStream_t s)
+{
+    const size_t lds = std::max((size_t)NST * BK * (TCO + TM) * sizeof(float) + (MODE == MODE_GEN ? 512 * sizeof(int2) : 0), (size_t)4 * 32 * 36 * sizeof(float));
+    constexpr bool HAS_DUAL = TCO == 64 && MODE != MODE_TAP4 && MODE != MODE_GEN;      // the stems' gathers and the 32 x 128 tile have none
+    return launch_tiles<TCO, TM, BK, HAS_DUAL>(p, s, lds, [](auto relu, auto chain) {
+        return &conv_gemm_kernel<TCO, TM, BK, NST, MODE, decltype(relu)::value, decltype(chain)::value>;
+    });
+}
+
+// the split-K kernel: four wave-private rings, each at least the two quadrants a wave parks in an exchange round
+template <int BK, int NST, int MODE>
+bool launch_one_ks(const ConvParams& p, hipStream_t s)
+{
+    constexpr int RING = NST * BK * (64 + 64);
+    const size_t lds = (size_t)4 * (RING > 2048 ? RING : 2048) * sizeof(float);
+    return launch_tiles<64, 64, BK, true>(p, s, lds, [](auto relu, auto chain) {
+        return &conv_gemm_ks_kernel<BK, NST, MODE, decltype(relu)::value, decltype(chain)::value>;
+    });
 }
 
 // Layers the split-K kernel covers: stride-1 convolutions whose K-steps lie inside one filter tap -- 1x1 (float4 rows when the launch's
@@ -859,14 +824,18 @@ bool ks_ok(const ConvParams& p)
     return p.stride == 1 && p.tap_major == 1 && p.kh * p.kw <= 64;
 }
 
+// a 1x1 convolution whose im2col matrix IS the input tensor, rows float4-aligned: the B side loads 16 bytes per lane (MODE_VEC)
+bool is_vec_1x1(const ConvParams& p)
+{
+    return p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad == 0 && (p.M % 4) == 0 && p.OH == p.H && p.OW == p.W;
+}
+
 template <int BK, int NST>
 bool launch_cfg_ks(const ConvParams& p, hipStream_t s)
 {
-    const bool vec = (p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad == 0 && (p.M % 4) == 0 && p.OH == p.H && p.OW == p.W);
-    if (vec) return launch_one_ks<BK, NST, MODE_VEC>(p, s);
+    if (is_vec_1x1(p)) return launch_one_ks<BK, NST, MODE_VEC>(p, s);
     return launch_one_ks<BK, NST, MODE_TAP>(p, s);
 }
-
 
 template <int TCO, int TM, int BK, int NST>
 bool launch_cfg(const ConvParams& p_in, hipStream_t s)
@@ -875,8 +844,7 @@ bool launch_cfg(const ConvParams& p_in, hipStream_t s)
     // a strided 1x1 convolution on the dual-accumulator loop: the tap-major gather with its single tap (for one tap the two K orders are the same
     // rows of the same pack) instead of the generic table gather, which has no dual-accumulator instantiation
     if (p.dualacc && p.kh == 1 && p.kw == 1 && p.tap_major == 0 && (p.Cin % 16) == 0) p.tap_major = 1;
-    const bool vec = (p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad == 0 && (p.M % 4) == 0 && p.OH == p.H && p.OW == p.W);
-    if (vec) return launch_one<TCO, TM, BK, NST, MODE_VEC>(p, s);
+    if (is_vec_1x1(p)) return launch_one<TCO, TM, BK, NST, MODE_VEC>(p, s);
     if (p.tap_major == 2) return launch_one<64, 64, 16, 4, MODE_TAP4>(p, s);
     if (p.tap_major && (p.Cin % BK) == 0) return launch_one<TCO, TM, BK, NST, MODE_TAP>(p, s);
     if (p.tap_major) return launch_one<TCO, TM, 16, 4, MODE_TAP>(p, s);
@@ -927,14 +895,12 @@ void conv_gemm_chain_launch_counts(long* compiled, long* interpreted)
     if (interpreted) *interpreted = g_conv_chain_launches[1].load();
 }
 
-static int pick_cfg_impl(const ConvParams& p_in, bool allow_split);
-int conv_gemm_pick_cfg(const ConvParams& p_in) { return pick_cfg_impl(p_in, true); }
 static int pick_cfg_impl(const ConvParams& p_in, bool allow_split)
 {
     // A dual-accumulator launch does the work of the dual (W / relu(W)) launch of the same layer with half the workgroups, twice as long each: it
     // takes the kernel that launch takes (the rules below see the dual launch's tile count), never the 32 x 128 tile.
     ConvParams p = p_in;
-    if (p.dualacc) { p.nhalves = 2; p.dualacc = 0; const int c = pick_cfg_impl(p, false); return c == 12 ? 4 : c; }
+    if (p.dualacc) { p.nhalves = 2; p.dualacc = 0; const int c = pick_cfg_impl(p, false); return c == CFG_ROW32 ? CFG_K16 : c; }
     // Measured on MI355X over the ResNet-101 / ResNet-50 / Light-CNN GEMM shapes (M = 1.5k..400k, K = 64..4608,
     // Cout = 64..2048): the 64x64 tile wins or ties everywhere -- these grids are small (1-12 workgroups per CU), so
     // finer tiles balance the 256 CUs better and keep more waves per SIMD than 128-wide tiles buy in reuse.
@@ -943,13 +909,13 @@ static int pick_cfg_impl(const ConvParams& p_in, bool allow_split)
     // Channel counts that leave the last 64-row tile at most half full (Light-CNN: 96 = 64 + 32): the 32 x 128 block tile wastes no MFMA row.
     // A property of the layer; K order of the 64 x 64 tile, so the bits do not move where that one ran before.
     // bf16x6 (K17): the layers xfr_engine_set_split_gemm covers, when the launch's grid is at least half the CUs (conv_gemm_split.hip)
-    if (allow_split && p.split_ok && conv_gemm_split_wanted(p)) return 9;
+    if (allow_split && p.split_ok && conv_gemm_split_wanted(p)) return CFG_BF16X6;
     {
         const int rem = p.CoutTot % 64;
 #ifndef XFR_NO_ROW_TILE      /* A/B builds only (profiles/r4/experiments/row_tile_ab.txt) */
         // (more than one 64-column tile of positions: a one-image call through an 80013-way classifier has ONE column, and 2501 tiles of 32 x 128 took
         // 183 us where the 64 x 64 tile takes 57 -- same K order, same bits)
-        if (rem > 0 && rem <= 32 && p.tap_major != 2 && p.out_stride == 1 && p.CoutTot > 32 && p.M > 64) return 12;
+        if (rem > 0 && rem <= 32 && p.tap_major != 2 && p.out_stride == 1 && p.CoutTot > 32 && p.M > 64) return CFG_ROW32;
 #endif
     }
     if (ks_ok<8>(p)) {
@@ -958,33 +924,88 @@ static int pick_cfg_impl(const ConvParams& p_in, bool allow_split)
         // 3 / 4) -4..-12 %, 1x1 with K = 512 or K >= 2048 -3..-14 %, K = 1024 +4 % (stays on K1); strided 1x1 convolutions (forward:
         // gathered input, backward: scattered output) -35 % against the generic-gather kernel.  Split-K for every K >= 512 layer is
         // 0.4 % slower in the timed three-stream schedule (32 KB rings crowd out the other streams' workgroups).
-        if (p.kh == 1 && (p.stride == 2 || p.out_stride == 2 || p.as_strided)) return 7;
-        if ((p.kh > 1 && p.K >= 2048) || (p.kh == 1 && (p.K == 512 || p.K >= 2048))) return 7;
+        if (p.kh == 1 && (p.stride == 2 || p.out_stride == 2 || p.as_strided)) return CFG_KS_4_4;
+        if ((p.kh > 1 && p.K >= 2048) || (p.kh == 1 && (p.K == 512 || p.K >= 2048))) return CFG_KS_4_4;
     }
     // Deep-K launches of at most two tiles per CU (layer 3/4 of a 32-image batch) prefer 32-deep K-steps: half the barriers
     // per MFMA.  Their 48 KB ring allows three workgroups per CU, so larger grids (the W / relu(W) dual launch of the
     // same layer has twice the tiles) stay on the 24 KB ring where whole tiles and tail parts are all resident.
     const long tiles = (long)((p.CoutTot + 63) / 64) * p.nhalves * ((p.M + 63) / 64);
-    if (p.K >= 1024 && tiles <= 512 && (p.tap_major ? (p.Cin % 32 == 0) : true)) return 5;
-    return 4;
+    if (p.K >= 1024 && tiles <= 512 && (p.tap_major ? (p.Cin % 32 == 0) : true)) return CFG_K32;
+    return CFG_K16;
 }
+int conv_gemm_pick_cfg(const ConvParams& p_in) { return pick_cfg_impl(p_in, true); }
 
-// Tuning state (stamps, launch log): process-global, shared by every engine of the process.  g_tuning says whether any of it is on -- the launch
-// path takes g_tune_mu only then, so production launches (tuning off) pay one relaxed atomic load; with tuning on, engines launching from several
-// host threads serialise on the mutex while they take their record, and set / dump / clear are safe against them.
-static std::mutex g_tune_mu;
-static thread_local int g_last_cfg = 0;      // configuration of this thread's last launch_conv_gemm (conv_gemm_last_cfg)
-static std::atomic<int> g_tuning{0};
-static unsigned long long* g_stamps = nullptr;
-static int g_stamps_cap = 0;
-static int g_stamp_regions = 0, g_stamp_seq = 0;
+// ---- tuning state (stamps, launch log, configuration remap): process-global, shared by every engine of the process -----------------------------
+// g_tuning says whether stamps or the log are on -- the launch path takes g_tune_mu only then, so production launches (tuning off) pay one relaxed
+// atomic load; with tuning on, engines launching from several host threads serialise on the mutex while they take their record, and set / dump /
+// clear are safe against them.
 namespace {
 struct LogRec { void* stream; int cout, nhalves, K, M, kh, chain, cfg; };
+std::mutex g_tune_mu;
+std::atomic<int> g_tuning{0};
+unsigned long long* g_stamps = nullptr;
+int g_stamps_cap = 0;
+int g_stamp_regions = 0, g_stamp_seq = 0;
 unsigned long long* g_log = nullptr;
 int g_log_cap = 0;
 std::vector<LogRec> g_log_recs;
-bool g_log_on() { return g_log != nullptr; }
+thread_local int g_last_cfg = 0;      // configuration of this thread's last launch_conv_gemm (conv_gemm_last_cfg)
+constexpr size_t NO_LOG = (size_t)-1;
+
+// the launch's share of the tuning state: stamp buffer and sequence number, and its record in the launch log (returned; NO_LOG: none)
+size_t tune_begin(ConvParams& p, hipStream_t s)
+{
+    p.stamps = nullptr;
+    p.stamps_cap = 0;
+    p.stamp_regions = 0;
+    p.stamp_seq = 0;
+    p.span = nullptr;
+    size_t log_idx = NO_LOG;
+    if (g_tuning.load(std::memory_order_relaxed)) {
+        std::lock_guard<std::mutex> lk(g_tune_mu);
+        p.stamps = g_stamps;
+        p.stamps_cap = g_stamps_cap;
+        p.stamp_regions = g_stamp_regions;
+        p.stamp_seq = g_stamps ? g_stamp_seq++ : 0;
+        if (g_log && (int)g_log_recs.size() < g_log_cap) {
+            p.span = g_log + 8 * g_log_recs.size();
+            log_idx = g_log_recs.size();
+            g_log_recs.push_back(LogRec{(void*)s, p.CoutTot, p.dualacc ? 2 : p.nhalves, p.K, p.M, p.kh, p.chain.n, -1});      // cfg: the kernel that really runs (tune_ran)
+        }
+    }
+    return log_idx;
 }
+// the configuration that really runs: the launch log and the engine's per-launch profile record THIS, not the rules' first answer
+void tune_ran(size_t log_idx, int cfg)
+{
+    g_last_cfg = cfg;
+    if (log_idx == NO_LOG) return;
+    std::lock_guard<std::mutex> lk(g_tune_mu);
+    if (log_idx < g_log_recs.size()) g_log_recs[log_idx].cfg = cfg;
+}
+// tuning hook (A/B runs of the timed step on one box, tools/ab_env.sh): XFR_CFG_REMAP="4:5,7:6" sends every launch the rules give configuration 4
+// to 5 and 7 to 6.  Read once; unset in production.
+int cfg_remap(int cfg)
+{
+    struct Remap { int v[32]; };
+    static const Remap remap = [] {                        // function-local static: initialised once, thread-safe
+        Remap r;
+        for (int i = 0; i < 32; ++i) r.v[i] = i;
+        if (const char* e = getenv("XFR_CFG_REMAP")) {
+            int a = 0, b = 0, n = 0;
+            while (sscanf(e, "%d:%d%n", &a, &b, &n) == 2) {
+                if (a >= 0 && a < 32 && b >= 0 && b < 32) r.v[a] = b;
+                e += n;
+                if (*e == ',') ++e;
+            }
+        }
+        return r;
+    }();
+    return (cfg >= 0 && cfg < 32) ? remap.v[cfg] : cfg;
+}
+}  // namespace
+
 // capacity < 0: sampled mode -- |capacity| / 256 regions of 256 records, launch n writes up to 256 evenly spaced workgroups into region n % regions
 void conv_gemm_set_stamps(unsigned long long* dev_ptr, int capacity_workgroups)
 {
@@ -993,7 +1014,7 @@ void conv_gemm_set_stamps(unsigned long long* dev_ptr, int capacity_workgroups)
     g_stamps_cap = dev_ptr ? (capacity_workgroups < 0 ? -capacity_workgroups : capacity_workgroups) : 0;
     g_stamp_regions = (dev_ptr && capacity_workgroups < 0) ? (-capacity_workgroups) / 256 : 0;
     g_stamp_seq = 0;
-    g_tuning.store((g_stamps || g_log_on()) ? 1 : 0);
+    g_tuning.store((g_stamps || g_log) ? 1 : 0);
 }
 
 void conv_gemm_set_log(unsigned long long* log_dev, int capacity)
@@ -1021,68 +1042,24 @@ int conv_gemm_dump_log(const char* path)
     fclose(f);
     return (int)n;
 }
+int conv_gemm_last_cfg() { return g_last_cfg; }
 
+// take the launch's tuning record, pick the configuration, remap, dispatch
 bool launch_conv_gemm(const ConvParams& p_in, hipStream_t s)
 {
     ConvParams p = p_in;
-    p.stamps = nullptr;
-    p.stamps_cap = 0;
-    p.stamp_regions = 0;
-    p.stamp_seq = 0;
-    p.span = nullptr;
-    size_t log_idx = (size_t)-1;
-    if (g_tuning.load(std::memory_order_relaxed)) {
-        std::lock_guard<std::mutex> lk(g_tune_mu);
-        p.stamps = g_stamps;
-        p.stamps_cap = g_stamps_cap;
-        p.stamp_regions = g_stamp_regions;
-        p.stamp_seq = g_stamps ? g_stamp_seq++ : 0;
-        if (g_log && (int)g_log_recs.size() < g_log_cap) {
-            p.span = g_log + 8 * g_log_recs.size();
-            log_idx = g_log_recs.size();
-            g_log_recs.push_back(LogRec{(void*)s, p.CoutTot, p.dualacc ? 2 : p.nhalves, p.K, p.M, p.kh, p.chain.n, -1});      // cfg: the kernel that really runs (below)
-        }
-    }
-    int cfg = p.force_cfg > 0 ? p.force_cfg : conv_gemm_pick_cfg(p);
-    {
-        // tuning hook (A/B runs of the timed step on one box, tools/ab_env.sh): XFR_CFG_REMAP="4:5,7:6" sends every launch the rules above give
-        // configuration 4 to 5 and 7 to 6.  Read once; unset in production.
-        struct Remap { int v[32]; };
-        static const Remap remap = [] {                        // function-local static: initialised once, thread-safe
-            Remap r;
-            for (int i = 0; i < 32; ++i) r.v[i] = i;
-            if (const char* e = getenv("XFR_CFG_REMAP")) {
-                int a = 0, b = 0, n = 0;
-                while (sscanf(e, "%d:%d%n", &a, &b, &n) == 2) {
-                    if (a >= 0 && a < 32 && b >= 0 && b < 32) r.v[a] = b;
-                    e += n;
-                    if (*e == ',') ++e;
-                }
-            }
-            return r;
-        }();
-        if (p.force_cfg <= 0 && cfg >= 0 && cfg < 32) cfg = remap.v[cfg];
-    }
-    // cfg 6 / 7: the intra-workgroup split-K kernel, (BK, ring stages) = (8, 3): 48 KB of LDS, three workgroups per CU; (4, 4): 32 KB, five.
-    // Round 3 sweep (tools/conv_sweep.py): (4, 5) and (4, 6) tie with (4, 4), (16, 3) -- one workgroup per CU -- loses 15 %.
-    // the configuration that really runs: the launch log and the engine's per-launch profile record THIS, not the rules' first answer
-    auto ran = [&](int eff, bool ok) {
-        g_last_cfg = eff;
-        if (log_idx != (size_t)-1) {
-            std::lock_guard<std::mutex> lk(g_tune_mu);
-            if (log_idx < g_log_recs.size()) g_log_recs[log_idx].cfg = eff;
-        }
-        return ok;
-    };
-    if (cfg == 9) {
-        if (conv_gemm_launch_split(p, s)) return ran(9, true);
+    const size_t log_idx = tune_begin(p, s);
+    int cfg = p.force_cfg > 0 ? p.force_cfg : cfg_remap(conv_gemm_pick_cfg(p));
+    auto ran = [&](int eff, bool ok) { tune_ran(log_idx, eff); return ok; };
+    if (cfg == CFG_BF16X6) {
+        if (conv_gemm_launch_split(p, s)) return ran(CFG_BF16X6, true);
         cfg = pick_cfg_impl(p, false);     // refused (a chain family without a split instantiation, no memory for the planes): the fp32 rules
     }
-    if (cfg == 6 && ks_ok<8>(p)) return ran(6, launch_cfg_ks<8, 3>(p, s));
-    if (cfg == 7 && ks_ok<4>(p)) return ran(7, launch_cfg_ks<4, 4>(p, s));
-    if (cfg == 5) return ran(5, launch_cfg<64, 64, 32, 3>(p, s));
-    if (cfg == 12) return ran(12, launch_cfg<32, 128, 16, 3>(p, s));          // the 32 x 128 block tile (four waves side by side along m)
-    return ran(4, launch_cfg<64, 64, 16, 3>(p, s));
+    // the split-K kernel, (BK, ring stages) = (8, 3): 48 KB of LDS, three workgroups per CU; (4, 4): 32 KB, five.
+    // Round 3 sweep (tools/conv_sweep.py): (4, 5) and (4, 6) tie with (4, 4), (16, 3) -- one workgroup per CU -- loses 15 %.
+    if (cfg == CFG_KS_8_3 && ks_ok<8>(p)) return ran(CFG_KS_8_3, launch_cfg_ks<8, 3>(p, s));
+    if (cfg == CFG_KS_4_4 && ks_ok<4>(p)) return ran(CFG_KS_4_4, launch_cfg_ks<4, 4>(p, s));
+    if (cfg == CFG_K32) return ran(CFG_K32, launch_cfg<64, 64, 32, 3>(p, s));
+    if (cfg == CFG_ROW32) return ran(CFG_ROW32, launch_cfg<32, 128, 16, 3>(p, s));
+    return ran(CFG_K16, launch_cfg<64, 64, 16, 3>(p, s));
 }
-
-int conv_gemm_last_cfg() { return g_last_cfg; }

@@ -10,6 +10,13 @@ constexpr int NT = 256;
 
 enum { MODE_VEC = 0, MODE_TAP = 1, MODE_GEN = 2, MODE_TAP4 = 3 };
 
+// Rows whose length is a multiple of 4 on both sides (gradient rows of out_nb images, forward rows of chain_B images): the compiled chain epilogues
+// load and store float4 pieces, so the launcher picks the epilogue by this test, and the interpreted epilogue its path.
+__host__ __device__ inline bool rows_vec4(const ConvParams& p)
+{
+    return (p.M & 3) == 0 && ((p.chain_B * p.OH * p.OW) & 3) == 0 && ((p.out_nb * p.OH * p.OW) & 3) == 0;
+}
+
 // Epilogue of one wave's 32x32 accumulator tile for a chain with signature SIG.  A lane owns, for each of the four 8-channel
 // groups hf, one float4 piece (channel hf*8 + lane/8, positions 4*(lane%8)..+3).  The operand loads of groups 0 and 1 are
 // issued first -- before the accumulators are turned through LDS -- and those of group hf+2 right after group hf's have been
@@ -145,12 +152,13 @@ __device__ __forceinline__ void chain_epilogue_dispatch(int sig, const ConvParam
     }
 }
 
-// Everything after the K loop of a 64x64 block tile whose wave (wrow, wcol) holds the 32x32 quadrant acc[0][0]: the exchange of a
+// Everything after the K loop of a 64x64 block tile whose wave (wrow, wcol) holds the 32x32 quadrant acc: the exchange of a
 // tail tile's K-parts, then the epilogue.  Shared by the two kernels below.  CHAIN: 0 = plain epilogue, 1 = compiled chain epilogue
-// (p.chain_sig), 2 = interpreted chain epilogue; LDS_OK: the workgroup's LDS holds the four 32 x 36 transposition tiles.
+// (p.chain_sig; 3: the MaxFeatureMap signatures), 2 = interpreted chain epilogue, 4 = compiled lean probe forward over acc and *accp.  The workgroup's LDS holds the four
+// 32 x 36 transposition tiles.
 // ROW: the four waves lie side by side along m (a 32 x 128 block tile) instead of 2 x 2 (64 x 64); either way a wave holds one 32 x 32 quadrant.
-template <int CHAIN, bool LDS_OK, bool ROW = false>
-__device__ __forceinline__ void block_epilogue(const ConvParams& p, v16f (&acc)[1][1], float* smem, const int tid, const int lane, const int wave,
+template <int CHAIN, bool ROW = false>
+__device__ __forceinline__ void block_epilogue(const ConvParams& p, v16f& acc, float* smem, const int tid, const int lane, const int wave,
                                                const int co0, const int m0, const int half, const int tail_t, const int part, const int nparts,
                                                float* __restrict__ osel, const float* __restrict__ bsel, v16f* accp = nullptr)
 {
@@ -168,12 +176,7 @@ __device__ __forceinline__ void block_epilogue(const ConvParams& p, v16f (&acc)[
             for (int r = 0; r < 16; ++r) __hip_atomic_store(slab + (16 + r) * NT + tid, (*accp)[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
 #pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    __hip_atomic_store(slab + ((i * NJ + j) * 16 + r) * NT + tid, acc[i][j][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int r = 0; r < 16; ++r) __hip_atomic_store(slab + r * NT + tid, acc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // write-through (agent-scope) stores, then only wait for them: a full __threadfence() would write back AND
         // invalidate this XCD's whole L2 under the other resident workgroups (measured: 37 us per launch at 256 parts)
         wait_vmcnt<0>();
@@ -191,7 +194,6 @@ __device__ __forceinline__ void block_epilogue(const ConvParams& p, v16f (&acc)[
         // Part by part, the sixteen registers of a part in flight together (round 6: with the part loop innermost every one of the 16 x nparts
         // agent-scope loads waited for the one before it -- 4.2 us per part, 40 us of a 43 us launch at eight parts).  Same sums in the same
         // order: element r adds part 0, 1, 2, ... to 0.0f.
-        static_assert(MI == 1 && NJ == 1, "one quadrant per wave");
         constexpr int NACC = CHAIN == 4 ? 32 : 16;
         float sum[NACC];
 #pragma unroll
@@ -205,7 +207,7 @@ __device__ __forceinline__ void block_epilogue(const ConvParams& p, v16f (&acc)[
             for (int r = 0; r < NACC; ++r) sum[r] += v[r];
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[0][0][r] = sum[r];
+        for (int r = 0; r < 16; ++r) acc[r] = sum[r];
         if constexpr (CHAIN == 4) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) (*accp)[r] = sum[16 + r];
@@ -217,19 +219,16 @@ __device__ __forceinline__ void block_epilogue(const ConvParams& p, v16f (&acc)[
     // backward = [+fan-in gradient] -> tensor hooks / ReLU mask / BatchNorm VJP -> next GEMM's input.
     if constexpr (CHAIN == 4) {
         // lean probe forward: the wave holds the W and the relu(W) tile of its quadrant; the compiled chain stores what the sweep needs of them
-        if constexpr (MI == 1 && NJ == 1)
-            chain_epilogue_dispatch<0, 2>(p.chain_sig, p, acc[0][0], accp, smem + wave * (32 * 36), lane, l31, lhi, co0 + wrow * 32,
-                                          m0 + wcol * 32 + (lane & 7) * 4, osel, bsel);
+        chain_epilogue_dispatch<0, 2>(p.chain_sig, p, acc, accp, smem + wave * (32 * 36), lane, l31, lhi, co0 + wrow * 32,
+                                      m0 + wcol * 32 + (lane & 7) * 4, osel, bsel);
     } else if constexpr (CHAIN == 1 || CHAIN == 3) {
         // compiled chain epilogue (CHAIN 3: the MaxFeatureMap signatures); launch_one only selects this instantiation when the float4 layout conditions hold.  The chain
         // belongs to half 0; the relu(W) half of a dual launch (positive activations) leaves as plain dense rows.
-        if constexpr (MI == 1 && NJ == 1) {
-            if (half == 0)
-                chain_epilogue_dispatch<0, CHAIN == 3 ? 1 : 0>(p.chain_sig, p, acc[0][0], nullptr, smem + wave * (32 * 36), lane, l31, lhi, co0 + wrow * 32,
-                                           m0 + wcol * 32 + (lane & 7) * 4, osel, bsel);
-            else
-                dense_epilogue(p, acc[0][0], smem + wave * (32 * 36), lane, l31, lhi, co0 + wrow * 32, m0 + wcol * 32 + (lane & 7) * 4, osel, bsel);
-        }
+        if (half == 0)
+            chain_epilogue_dispatch<0, CHAIN == 3 ? 1 : 0>(p.chain_sig, p, acc, nullptr, smem + wave * (32 * 36), lane, l31, lhi, co0 + wrow * 32,
+                                                           m0 + wcol * 32 + (lane & 7) * 4, osel, bsel);
+        else
+            dense_epilogue(p, acc, smem + wave * (32 * 36), lane, l31, lhi, co0 + wrow * 32, m0 + wcol * 32 + (lane & 7) * 4, osel, bsel);
     } else if constexpr (CHAIN == 2) {
         // Epilogue with a fused micro-program (backward: [+fan-in gradient] -> tensor hooks / ReLU mask / BatchNorm VJP ->
         // the next GEMM's input).  The 16 accumulator registers of a 32x32 tile are 4 groups of 4 consecutive output
@@ -241,19 +240,15 @@ __device__ __forceinline__ void block_epilogue(const ConvParams& p, v16f (&acc)[
         // scratch (2 KB per lane, every step read back from there: a stage-4 launch of a one-image call took 75 us where the compiled chain takes 23).
         // Read the steps from the kernel-argument segment itself -- ConvParams is the first argument of every GEMM kernel -- through the constant cache.
         const EwChain& kchain = ((const ConvParams*)__builtin_amdgcn_kernarg_segment_ptr())->chain;
-        // float4 pieces need rows whose length is a multiple of 4 on both sides (gradient rows of out_nb images, forward
-        // rows of chain_B images); a piece may then straddle two samples (7x7 maps) but never a row
-        const bool vec_ok = MI == 1 && NJ == 1 && LDS_OK && (p.M & 3) == 0 &&
-                            ((p.chain_B * p.OH * p.OW) & 3) == 0 && ((p.out_nb * p.OH * p.OW) & 3) == 0;
-        if (vec_ok) {
+        if (rows_vec4(p)) {
             // vector path: the tile is turned through LDS like in the plain epilogue, a lane then owns float4 pieces
-            // (one channel, four consecutive positions of one sample) and runs the same float4 interpreter as the
+            // (one channel, four consecutive positions; a piece may straddle two samples -- 7x7 maps -- but never a row) and runs the same float4 interpreter as the
             // stand-alone chain kernel, operands fetched as 16-byte loads
             constexpr int LD = 36;
             __syncthreads();
             float* tile = smem + wave * (32 * LD);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) tile[((r & 3) + 8 * (r >> 2) + 4 * lhi) * LD + l31] = acc[0][0][r];
+            for (int r = 0; r < 16; ++r) tile[((r & 3) + 8 * (r >> 2) + 4 * lhi) * LD + l31] = acc[r];
             const int ohw = p.OH * p.OW;
             const long row4 = (long)p.out_nb * ohw / 4, arow4 = (long)p.chain_B * ohw / 4;
             const int mq = (lane & 7) * 4;
@@ -331,7 +326,7 @@ __device__ __forceinline__ void block_epilogue(const ConvParams& p, v16f (&acc)[
                     for (int e8 = 0; e8 < 4; ++e8) {
                         const int rg = hf, q = e8;
                         const int co = co0 + wrow * (TCO / 2) + i * 32 + 4 * lhi + 8 * rg + q;
-                        float v = acc[i][j][rg * 4 + q];
+                        float v = acc[rg * 4 + q];
                         if (ok[e8]) {
                             if (bsel) v += bsel[co];
                             if (p.accumulate) v += osel[gi[e8]];
@@ -421,9 +416,8 @@ __device__ __forceinline__ void block_epilogue(const ConvParams& p, v16f (&acc)[
                 }
             }
         }
-    } else if (MI == 1 && NJ == 1 && LDS_OK && p.out_stride == 1 && (p.M & 3) == 0 && ((p.out_nb * p.OH * p.OW) & 3) == 0) {
-        if constexpr (MI == 1 && NJ == 1)
-            dense_epilogue(p, acc[0][0], smem + wave * (32 * 36), lane, l31, lhi, co0 + wrow * 32, m0 + wcol * 32 + (lane & 7) * 4, osel, bsel);
+    } else if (p.out_stride == 1 && (p.M & 3) == 0 && ((p.out_nb * p.OH * p.OW) & 3) == 0) {
+        dense_epilogue(p, acc, smem + wave * (32 * 36), lane, l31, lhi, co0 + wrow * 32, m0 + wcol * 32 + (lane & 7) * 4, osel, bsel);
     } else {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -450,7 +444,7 @@ __device__ __forceinline__ void block_epilogue(const ConvParams& p, v16f (&acc)[
                     const int co = co0 + wrow * (TCO / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
                     if (co >= p.CoutTot) continue;
                     const long gi = (long)out_row(p, co) * row_stride + col;
-                    float v = acc[i][j][r];
+                    float v = acc[r];
                     if (bsel) v += bsel[co];
                     if (p.accumulate) v += osel[gi];
                     osel[gi] = v;

@@ -407,10 +407,9 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
     // indexes its transposition scratch by the quadrant's wave number; the base is shifted so that every one of the eight waves lands on its own 32 x 36 tile.
 #pragma unroll 1
     for (int c = 0; c < 2; ++c) {
-        v16f t[1][1];
-        t[0][0] = acc[0];
+        v16f t = acc[0];
         const int wq = (wr4 & 1) * 2 + c;
-        block_epilogue<CHAIN, true>(p, t, smem + (wave8 - wq) * (32 * 36), tid & 255, lane, wq, co0 + (wr4 >> 1) * 64, m0 + wc * 64, half, -1, 0, 1, osel, bsel, nullptr);
+        block_epilogue<CHAIN>(p, t, smem + (wave8 - wq) * (32 * 36), tid & 255, lane, wq, co0 + (wr4 >> 1) * 64, m0 + wc * 64, half, -1, 0, 1, osel, bsel, nullptr);
         acc[0] = acc[1];
     }
     if (wave8 < 4) stamp(p, wave8, lane, 4);
@@ -534,7 +533,7 @@ void launch_split_inst(const ConvParams& q, const uint16_t* w0, const uint16_t* 
 // false: the launch is not one the split kernel covers (or its pack is not registered) -- the caller takes the fp32 kernel the rules give
 bool launch_split(const ConvParams& p, hipStream_t s)
 {
-    if (p.force_cfg == 9 ? !split_can_run(p) : !conv_gemm_split_wanted(p)) return false;
+    if (p.force_cfg == CFG_BF16X6 ? !split_can_run(p) : !conv_gemm_split_wanted(p)) return false;
     if (p.chain.n > 0 && p.relu_in) return false;
     ConvParams q = p;
     q.tail_q = 0;

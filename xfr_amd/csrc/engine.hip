@@ -63,7 +63,7 @@ static xfr_status prof_end(xfr_engine* e, hipStream_t s)
         const ConvParams& p = e->ev_params[i];
         const int Kl = p.K_logical ? p.K_logical : p.K;
         const double fl = 2.0 * Kl * (double)p.M * p.CoutTot * (p.dualacc ? 2 : p.nhalves);
-        const int fam = e->ev_cfg[i] == 9 ? 1 : 0;
+        const int fam = e->ev_cfg[i] == CFG_BF16X6 ? 1 : 0;
         e->fam_ms[fam] += t; e->fam_flops[fam] += fl; e->fam_launches[fam] += 1;
         if (f) fprintf(f, "%d,%d,%d,%d,%d,%d,%d,%d,%d,%.4f,%.2f,%d\n", p.CoutTot, p.nhalves, Kl, p.M, p.kh, p.stride, p.out_stride,
                        p.relu_in, p.accumulate, t, fl / (t * 1e-3) / 1e12, e->ev_cfg[i]);
@@ -954,7 +954,7 @@ xfr_status xfr_debug_conv(const float* in_dev, const float* w_host, const float*
     p.tail_cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(tws) + XFR_TAIL_WS_BYTES);
     HIP_TRY(hipMemset(p.tail_cnt, 0, XFR_TAIL_MAX_TILES * sizeof(unsigned)));
     p.tail_force = (cfg / 10000) % 100;  // 0 heuristic, 1 off, S >= 2 forced
-    const bool split = (cfg % 100) == 9;  // the bf16x6 kernel (layers it does not cover run the fp32 kernel the rules give, like in the engine)
+    const bool split = (cfg % 100) == CFG_BF16X6;  // the bf16x6 kernel (layers it does not cover run the fp32 kernel the rules give, like in the engine)
     hipEvent_t a, b;
     HIP_TRY(hipEventCreate(&a));
     HIP_TRY(hipEventCreate(&b));
