@@ -19,8 +19,9 @@
  *     W+ installed in the caller's modules after ebp(): whitebox.py:371-377);
  *   - a call is bit-reproducible for a given batch size and settings.  ACROSS batch sizes a sample's map is the same
  *     arithmetic in a different summation order, not the same bits: three defaults look at the batch -- the lean schedule
- *     (batch % 4 == 0, xfr_engine_set_lean), the bf16x6 kernel (grids of >= 128 tiles, xfr_engine_set_split_gemm) and tail
- *     balancing (xfr_engine_set_tail_balance).  With all three off every launch of a layer runs one kernel in one K order.
+ *     (batch % 4 == 0, xfr_engine_set_lean), the bf16x6 kernel (grids of >= 128 workgroups, xfr_engine_set_split_gemm) and tail
+ *     balancing (xfr_engine_set_tail_balance; without it the bf16x6 kernel does not cut the tiles of a small 7 x 7 grid into K-parts
+ *     either).  With all three off every launch of a layer runs one kernel in one K order.
  */
 #ifndef XFR_AMD_H
 #define XFR_AMD_H
@@ -323,12 +324,15 @@ xfr_status xfr_engine_set_lean(xfr_engine* e, int32_t enable);
  * (rms 5-9e-9 of the sum of magnitudes against 1.1-2.0e-8, no offset: profiles/r6/conv_error_probe.txt).
  * mode 3 (the default since round 6): the forward convolutions AND the sweep's backward-data GEMMs of those layers.  mode 1: the forward convolutions
  * only (the round-5 default).  mode 2: backward only (tuning).  mode 0: fp32 MFMA kernels everywhere.
- * Which launches: a covered layer's launch takes the kernel when its grid has at least 128 tiles of 128 x 128 (half the CUs: about 25 images of a
- * 14 x 14 layer, 6 of a 28 x 28 one); smaller launches -- Whitebox.contrastive_ebp on one image, the weighted-subtree probes -- run the fp32 kernels,
+ * Which launches: a covered layer's launch takes the kernel when its grid has at least 128 workgroups (half the CUs).  On maps of 14 x 14 and more a
+ * workgroup is a tile of 128 x 128: about 25 images of a 14 x 14 layer, 6 of a 28 x 28 one.  On smaller maps (7 x 7) the tiles of a grid that would leave
+ * CUs idle are cut into two K-parts (two workgroups per tile, met in the tail-balancing workspace: none with xfr_engine_set_tail_balance(0)): from 64 tiles,
+ * i.e. from about 40 images of a 512-channel 7 x 7 layer (a 2048-channel one: 128 uncut tiles from 19 images); smaller launches -- Whitebox.contrastive_ebp on one image, the weighted-subtree probes -- run the fp32 kernels,
  * which fill the chip with 64 x 64 tiles where this one would leave it idle.  So a sample's map is bit-reproducible for a given batch size and agrees
  * across batch sizes to the kernels' summation-order difference (~1e-6 of its maximum; tests/test_gpu_parity.py::test_split_gemm_equals_fp32_kernels),
  * like K1's tail balancing (xfr_engine_set_tail_balance) and the lean schedule above.  Callers that need one arithmetic for every batch size: mode 0,
- * or mode + 4 (modes 5 .. 7): the covered layers take the kernel whatever the grid (tests and tuning: small launches are slow on it).
+ * or mode + 4 (modes 5 .. 7) with tail balancing off: the covered layers take the kernel whatever the grid, uncut (tests and tuning: small launches are
+ * slow on it).
  * The weight packs of the covered layers carry bf16 planes (+1.5x their size), built when the weights arrive (xfr_engine_load_weights,
  * xfr_engine_mark_weights_loaded, xfr_broadcast_weights, or this call); every entry point that changes the weights drops the old ones.  After writing
  * through a pointer from xfr_engine_weight_arena, call xfr_engine_mark_weights_loaded again: it rebuilds them.

@@ -23,6 +23,7 @@ R101 = [
     (512, 7, 7, 512, 3, 1, 1), (2048, 7, 7, 512, 1, 1, 0), (512, 7, 7, 2048, 1, 1, 0),
     (3, 224, 224, 64, 7, 2, 3),
     (256, 56, 56, 128, 1, 2, 0), (512, 28, 28, 256, 1, 2, 0), (1024, 14, 14, 512, 1, 2, 0),
+    (1024, 7, 7, 2048, 1, 1, 0),      # stage 4's shortcut as a GEMM (after the stride): the third 1x1 class at 7 x 7
 ]
 LCNN = [
     (128, 16, 16, 256, 3, 1, 1), (192, 16, 16, 384, 3, 1, 1), (96, 32, 32, 192, 3, 1, 1), (48, 64, 64, 96, 3, 1, 1),
@@ -55,7 +56,9 @@ def stamp_report(lib, _lib, torch, dev, a, cfg, ms_ref):
     base = t[:, :, 0].min()
     t = np.where(t > 0, t - base, 0.0)
     t0 = 0.0
-    done = t[:, :, 4].max(axis=1) > 0          # non-last tail parts leave before the epilogue
+    # K-parts that are not the last of their tile to arrive leave before the epilogue (fp32 kernels: no stamp 4; bf16x6: stamps 3 and 4 together at
+    # the exit, so that the launch log sees their end): an epilogue is at least a microsecond
+    done = (t[:, :, 4].max(axis=1) > 0) & ((t[:, :, 4] - t[:, :, 3]).max(axis=1) > 50)
     span = max(t[:, :, 4].max(), t[:, :, 2].max()) - t0
     tick_us = 0.01                             # s_memrealtime: the 100 MHz reference clock, one time base for all XCDs
     f = lambda a_: '%.1f/%.1f/%.1f' % tuple(np.percentile(a_ * tick_us, [10, 50, 90]))

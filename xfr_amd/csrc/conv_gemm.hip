@@ -941,7 +941,7 @@ int conv_gemm_pick_cfg(const ConvParams& p_in) { return pick_cfg_impl(p_in, true
 // atomic load; with tuning on, engines launching from several host threads serialise on the mutex while they take their record, and set / dump /
 // clear are safe against them.
 namespace {
-struct LogRec { void* stream; int cout, nhalves, K, M, kh, chain, cfg; };
+struct LogRec { void* stream; int cout, nhalves, K, M, kh, chain, cfg, parts; };      // parts: K-parts per tile of a bf16x6 launch (1: none)
 std::mutex g_tune_mu;
 std::atomic<int> g_tuning{0};
 unsigned long long* g_stamps = nullptr;
@@ -971,18 +971,18 @@ size_t tune_begin(ConvParams& p, hipStream_t s)
         if (g_log && (int)g_log_recs.size() < g_log_cap) {
             p.span = g_log + 8 * g_log_recs.size();
             log_idx = g_log_recs.size();
-            g_log_recs.push_back(LogRec{(void*)s, p.CoutTot, p.dualacc ? 2 : p.nhalves, p.K, p.M, p.kh, p.chain.n, -1});      // cfg: the kernel that really runs (tune_ran)
+            g_log_recs.push_back(LogRec{(void*)s, p.CoutTot, p.dualacc ? 2 : p.nhalves, p.K, p.M, p.kh, p.chain.n, -1, 1});      // cfg: the kernel that really runs (tune_ran)
         }
     }
     return log_idx;
 }
 // the configuration that really runs: the launch log and the engine's per-launch profile record THIS, not the rules' first answer
-void tune_ran(size_t log_idx, int cfg)
+void tune_ran(size_t log_idx, int cfg, int parts = 1)
 {
     g_last_cfg = cfg;
     if (log_idx == NO_LOG) return;
     std::lock_guard<std::mutex> lk(g_tune_mu);
-    if (log_idx < g_log_recs.size()) g_log_recs[log_idx].cfg = cfg;
+    if (log_idx < g_log_recs.size()) { g_log_recs[log_idx].cfg = cfg; g_log_recs[log_idx].parts = parts; }
 }
 // tuning hook (A/B runs of the timed step on one box, tools/ab_env.sh): XFR_CFG_REMAP="4:5,7:6" sends every launch the rules give configuration 4
 // to 5 and 7 to 6.  Read once; unset in production.
@@ -1034,10 +1034,10 @@ int conv_gemm_dump_log(const char* path)
     if (n && hipMemcpy(h.data(), g_log, 8 * n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     FILE* f = fopen(path, "w");
     if (!f) return -1;
-    fprintf(f, "seq,stream,Cout,nhalves,K,M,kh,chain,cfg,start_10ns,end_10ns\n");
+    fprintf(f, "seq,stream,Cout,nhalves,K,M,kh,chain,cfg,start_10ns,end_10ns,parts\n");      // (parts last: readers index the older columns by position)
     for (size_t i = 0; i < n; ++i) {
         const LogRec& r = g_log_recs[i];
-        fprintf(f, "%zu,%p,%d,%d,%d,%d,%d,%d,%d,%llu,%llu\n", i, r.stream, r.cout, r.nhalves, r.K, r.M, r.kh, r.chain, r.cfg, h[8 * i], *std::max_element(h.begin() + 8 * i + 1, h.begin() + 8 * i + 8));
+        fprintf(f, "%zu,%p,%d,%d,%d,%d,%d,%d,%d,%llu,%llu,%d\n", i, r.stream, r.cout, r.nhalves, r.K, r.M, r.kh, r.chain, r.cfg, h[8 * i], *std::max_element(h.begin() + 8 * i + 1, h.begin() + 8 * i + 8), r.parts);
     }
     fclose(f);
     return (int)n;
@@ -1052,7 +1052,7 @@ bool launch_conv_gemm(const ConvParams& p_in, hipStream_t s)
     int cfg = p.force_cfg > 0 ? p.force_cfg : cfg_remap(conv_gemm_pick_cfg(p));
     auto ran = [&](int eff, bool ok) { tune_ran(log_idx, eff); return ok; };
     if (cfg == CFG_BF16X6) {
-        if (conv_gemm_launch_split(p, s)) return ran(CFG_BF16X6, true);
+        if (conv_gemm_launch_split(p, s)) { tune_ran(log_idx, CFG_BF16X6, conv_gemm_split_last_parts()); return true; }
         cfg = pick_cfg_impl(p, false);     // refused (a chain family without a split instantiation, no memory for the planes): the fp32 rules
     }
     // the split-K kernel, (BK, ring stages) = (8, 3): 48 KB of LDS, three workgroups per CU; (4, 4): 32 KB, five.

@@ -110,7 +110,11 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
     const bool two_dma = wave8 < 4;               // 12 DMA chunks of 1 KB per K-step on eight waves: waves 0-3 issue two, waves 4-7 one
     if (wave8 < 4) stamp(p, wave8, lane, 0, 4);
 
-    const int lid = xcd_remap(blockIdx.x, n_co_tiles * n_m_tiles);
+    // K-parts (p.tail_s > 1): the parts of a tile are neighbours in the grid (they land on different XCDs), the tiles are spread as without parts
+    const int nparts = p.tail_s > 1 ? p.tail_s : 1;
+    const int tile_lin = nparts > 1 ? (int)blockIdx.x / nparts : (int)blockIdx.x;
+    const int part = (int)blockIdx.x - tile_lin * nparts;
+    const int lid = xcd_remap(tile_lin, n_co_tiles * n_m_tiles);
     const int tile_m = lid / n_co_tiles;
     const int tile_co_all = lid - tile_m * n_co_tiles;
     const int n_co_half = n_co_tiles / p.nhalves;
@@ -121,6 +125,13 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
     const float* __restrict__ bsel = half ? p.bias_pos : p.bias;
     float* __restrict__ osel = half ? p.out1 : p.out0;
     const int T = p.kh * p.kw, ncb = p.Cin / SP_BK, nk = p.K / SP_BK;
+    // this part's K range in whole units -- a channel block of T steps (patch) or a pass of three steps (slab), so that the sign phase below stays a
+    // function of the absolute unit index; part sizes differ by at most one unit, the larger parts first.  Steps at or past k_end are out of range for
+    // the W DMA and the X loads: they multiply zeros, as the steps past nk always did.
+    const int units = PATCH ? ncb : (nk + 2) / 3, ustep = PATCH ? T : 3;
+    const int ubase = units / nparts, urem = units - ubase * nparts;
+    const int u0 = part * ubase + min(part, urem), u1 = u0 + ubase + (part < urem ? 1 : 0);
+    const int k0 = u0 * ustep, k_end = min(u1 * ustep, nk);
     const int halo = spp_halo(p), PL = spp_patch_len(p);
     const int PS = PATCH ? (PL + 1) * 16 : SP_T * 16;       // bytes of one (piece, k half) plane of X: a patch (+ zero slot), or a step's 128 columns
     const int XB = 6 * PS;
@@ -194,7 +205,7 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
         for (int r = 0; r < 16; ++r) { acc[j][r] = 0.f; pipe[j][r] = 0.f; }
 
     auto dma = [&](int kt, int stage, int ch) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lptr_t)(lds + stage * SP_A_BYTES + ch * 1024), 16, (ch * 1024 + lane * 16) | (kt < nk ? 0u : OOB),
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lptr_t)(lds + stage * SP_A_BYTES + ch * 1024), 16, (ch * 1024 + lane * 16) | (kt < k_end ? 0u : OOB),
                                                  (tile_co * nk + kt) * SP_A_BYTES, 0, 0);
     };
     auto load_w = [&](int kt, int stage) {
@@ -254,17 +265,17 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
         // then MFMAs -- so that on every SIMD one wave's DMA issue and LDS latency sit under the other wave's MFMAs.  (All eight in the same order -- the
         // first cut of this kernel -- run in lock-step between the barriers and wait for LDS together: no faster than four waves.)
         // Position of the step whose fragments are read NEXT (kt + 1): filter tap, channel block, patch buffer, the tap's shift
-        int tap = 0, cb = 0, buf = 0, shift = -halo, tdw = 0;
+        int tap = 0, cb = u0, buf = 0, shift = -halo, tdw = 0;
         bool xl_prev = false, xl_now = false;
         const bool mfma_first = wave8 < 4;
         // the load part of step kt: DMA of W(kt + 3), the next block's patch (loaded at tap 0 of the position above, split and stored at tap 2 -- BEFORE
         // the DMA, so that the wait for its X registers leaves at most the previous step's DMA in flight), fragments of step kt + 1
         auto load_part = [&](int kt, v8bf (&af)[3], v8bf (&bf)[3][2]) {
             const int st1 = (kt + 1) % 3, st3 = kt % 3;          // (kt >= -1: the prologue calls this with kt = -1, st3 = 2)
-            const bool more = cb + 1 < ncb;
+            const bool more = cb + 1 < u1;
             xl_now = false;
             if (more && tap == 2) store_patch(buf ^ 1, ((cb + 1) & 1) ? 0x80008000u : 0u);
-            load_w(kt + 3, kt < 0 ? 2 : st3);
+            load_w(k0 + kt + 3, kt < 0 ? 2 : st3);
             if (more && tap == 0) { load_patch(cb + 1); xl_now = true; }
             const unsigned char* As = a_lane + (kt < 0 ? 0 : st1) * SP_A_BYTES;
 #pragma unroll
@@ -299,24 +310,30 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
             const v4u z = {0u, 0u, 0u, 0u};
             asm volatile("ds_write_b128 %0, %1" :: "v"(lds_base + XBASE + (tid / 6) * XB + (tid % 6) * PS + PL * 16), "v"(z));
         }
-        load_w(0, 0);
-        load_w(1, 1);
-        load_patch(0);
+        if (u1 - u0 == 1) {
+            // a part of ONE channel block never stores a second patch, but its steps past the end read fragments from buffer 1: zeros there, not
+            // whatever the LDS held (0 x NaN)
+            const v4u z = {0u, 0u, 0u, 0u};
+            for (int i = tid; i < 6 * (PL + 1); i += NT8) asm volatile("ds_write_b128 %0, %1" :: "v"(lds_base + XBASE + XB + i * 16), "v"(z));
+        }
+        load_w(k0, 0);
+        load_w(k0 + 1, 1);
+        load_patch(u0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        store_patch(0, 0u);
+        store_patch(0, (u0 & 1) ? 0x80008000u : 0u);
         sp8_wait_barrier<0>();                       // W(0), W(1), the patch of block 0 and the zero slots are in LDS
         v8bf f0a[3], f0b[3][2], f1a[3], f1b[3][2];
         load_part(-1, f0a, f0b);                     // W(2); fragments of step 0
         end_step();
         if (wave8 < 4) stamp(p, wave8, lane, 1);
         int pass_in_blk = 0;
-        bool neg = false;                            // sign of the channel block the pass being COMPUTED belongs to
+        bool neg = (u0 & 1) != 0;                    // sign of the channel block the pass being COMPUTED belongs to: odd blocks negated, whichever part walks them
         const int passes_per_blk = T / 3;
         auto pass_done = [&]() {
             fold(neg);
             if (++pass_in_blk == passes_per_blk) { pass_in_blk = 0; neg = !neg; }
         };
-        for (int kt = 0; kt < nk; kt += 6) {         // up to five steps past the end multiply zeros (their W stages are zero-filled)
+        for (int kt = 0; kt < k_end - k0; kt += 6) { // (kt: steps from the part's start) up to five steps past the end multiply zeros (their W stages are zero-filled)
             step(kt, f0a, f0b, f1a, f1b, first);
             step(kt + 1, f1a, f1b, f0a, f0b, later);
             step(kt + 2, f0a, f0b, f1a, f1b, later);
@@ -327,10 +344,10 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
             pass_done();
         }
     } else {
-        int ld_tap = 0, ld_ci0 = 0;
-        unsigned ld_voff = (tapmask & 1ull) ? (unsigned)base_m * 4u : OOB;
+        int ld_tap = (k0 * SP_BK) / p.Cin, ld_ci0 = k0 * SP_BK - ld_tap * p.Cin;       // the part's first step
+        unsigned ld_voff = (ld_tap < T && ((tapmask >> ld_tap) & 1ull)) ? (unsigned)(base_m + (ld_tap / p.kw) * p.W + ld_tap % p.kw) * 4u : OOB;
         auto load_x = [&](int kt, float (&v)[4]) {
-            const unsigned voff = ld_voff | (kt < nk ? 0u : OOB);
+            const unsigned voff = ld_voff | (kt < k_end ? 0u : OOB);
             const unsigned so = (unsigned)(ld_ci0 + skq * 4) * chan_bytes;
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rIn, voff, so + (unsigned)i * chan_bytes, 0));
@@ -379,18 +396,18 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
             wst = wst + 1 == NST ? 0 : wst + 1;
         };
         float x0[4], x1[4], x2[4];
-        load_w(0, 0);
-        load_x(0, x0);
+        unsigned flip = (u0 & 1) ? 0x80008000u : 0u;     // odd passes negated, whichever part walks them
+        load_w(k0, 0);
+        load_x(k0, x0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        store_x(x0, 0, 0u);
+        store_x(x0, 0, flip);
 #pragma unroll
-        for (int d = 1; d < D; ++d) load_w(d, d);
-        load_x(1, x0);
-        load_x(2, x1);
+        for (int d = 1; d < D; ++d) load_w(k0 + d, d);
+        load_x(k0 + 1, x0);
+        load_x(k0 + 2, x1);
         if (two_dma) sp8_wait_barrier<8 + 2 * (D - 1)>(); else sp8_wait_barrier<8 + (D - 1)>();
         if (wave8 < 4) stamp(p, wave8, lane, 1);
-        unsigned flip = 0u;
-        for (int kt = 0; kt < nk; kt += 3) {
+        for (int kt = k0; kt < k_end; kt += 3) {
             const bool negated = flip != 0u;
             step(kt, S0, x0, x2, flip, first);
             step(kt + 1, S1, x1, x0, flip, later);
@@ -401,7 +418,51 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
     }
     wait_vmcnt<0>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (wave8 < 4) { stamp(p, wave8, lane, 2); stamp(p, wave8, lane, 3); }
+    if (wave8 < 4) stamp(p, wave8, lane, 2);
+
+    // ---- the exchange of a tile's K-parts (as block_epilogue's for the fp32 tail tiles): every part parks its accumulators -- part-major, one 128 x 128
+    // fp32 tile per (tile, part), a wave's 64 lanes side by side for each register -- and counts its arrival; the last part to arrive sums all parts in
+    // part order from 0.0f (deterministic whoever arrives last) and leaves through the epilogues.  Nobody waits for another workgroup.  Agent-scope
+    // stores / loads: the parts ran on different XCDs, whose L2s are not coherent for plain accesses; no fence (block_epilogue: 37 us per launch).
+    if (nparts > 1) {
+        constexpr int TILE_FLOATS = SP_T * SP_T;
+        float* __restrict__ slab = p.tail_ws + ((long)tile_lin * nparts + part) * TILE_FLOATS + tid;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) __hip_atomic_store(slab + (j * 16 + r) * NT8, acc[j][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        wait_vmcnt<0>();
+        __syncthreads();                                      // (every wave is out of the K loop: the ring is free)
+        int* flag = reinterpret_cast<int*>(smem);
+        if (tid == 0) {
+            const unsigned old = atomicAdd(p.tail_cnt + tile_lin, 1u);
+            const int last = (old == (unsigned)(nparts - 1));
+            if (last) atomicExch(p.tail_cnt + tile_lin, 0u);   // ready for the next launch on this stream
+            *flag = last;
+        }
+        __syncthreads();
+        const int last_part = *flag;
+        __syncthreads();                                      // (the flag word is wave 0's epilogue scratch: everybody has read it before anybody goes on)
+        if (!last_part) {
+            if (wave8 < 4) { stamp(p, wave8, lane, 3); stamp(p, wave8, lane, 4); }
+            return;
+        }
+        // part by part, the 32 registers of a part in flight together (profiles/r6/experiments/tail_exchange.txt: one dependent load after the other
+        // cost 4.2 us per part)
+        const float* __restrict__ src = p.tail_ws + (long)tile_lin * nparts * TILE_FLOATS + tid;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+        for (int q = 0; q < nparts; ++q, src += TILE_FLOATS) {
+            float v[32];
+#pragma unroll
+            for (int r = 0; r < 32; ++r) v[r] = __hip_atomic_load(src + r * NT8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int r = 0; r < 32; ++r) acc[r >> 4][r & 15] += v[r];
+        }
+    }
+    if (wave8 < 4) stamp(p, wave8, lane, 3);
 
     // ---- epilogues of K1: the wave's two 32 x 32 tiles are quadrants (wr4 & 1, 0) and (wr4 & 1, 1) of the 64 x 64 sub-tile (wr4 >> 1, wc).  block_epilogue
     // indexes its transposition scratch by the quadrant's wave number; the base is shifted so that every one of the eight waves lands on its own 32 x 36 tile.
@@ -436,49 +497,6 @@ struct SplitPack { uint16_t* planes; int K, cout, ldw, taps; };      // taps: 1 
 static std::mutex g_split_mu;
 static std::unordered_map<const float*, SplitPack> g_split;
 
-// what the kernel can run at all (xfr_debug_conv with cfg 9 asks for exactly this) ...
-bool split_can_run(const ConvParams& p)
-{
-    if (p.dualacc || p.out_stride != 1 || p.as_strided || p.co_pair > 0 || p.stride != 1) return false;
-    if ((p.Cin % SP_BK) != 0 || (p.K % SP_BK) != 0 || (p.CoutTot % SP_T) != 0) return false;
-    if (p.kh == 1 && p.kw == 1) return p.pad == 0;
-    return p.tap_major == 1 && p.kh * p.kw <= 64;
-}
-// ... the layers the engine sends to it (their packs get bf16 planes when the weights are loaded) ...
-struct SplitPolicy { int min_k1, min_k3, min_tiles; };
-const SplitPolicy& split_policy()
-{
-    // A/B runs only (tools/ab_env.sh): XFR_SPLIT_MIN_K1 / _K3 = the shallowest 1x1 / KxK layer, XFR_SPLIT_MIN_TILES = the smallest grid
-    static const SplitPolicy pol = [] {
-        SplitPolicy q{256, 1152, 128};     // round 6, same box, alternating: 1x1 from K = 512 +0.5 % (ResNet-101) / +1 % (ResNet-50-128d) over K >= 1024; from
-                                           // K = 256 level with that in time (final kernel: 1535 / 2490 against 1532 / 2499 maps/s) and closer to the reference
-                                           // (the kernel's sums are more accurate than the fp32 MFMA kernels': row-0 1 - cosine 1.1e-6 against 4.9e-6); from
-                                           // K = 128 a loss; KxK from K = 576 and grids from 64 / 196 tiles: level
-        if (const char* e = getenv("XFR_SPLIT_MIN_K1")) q.min_k1 = atoi(e);
-        if (const char* e = getenv("XFR_SPLIT_MIN_K3")) q.min_k3 = atoi(e);
-        if (const char* e = getenv("XFR_SPLIT_MIN_TILES")) q.min_tiles = atoi(e);
-        return q;
-    }();
-    return pol;
-}
-bool split_layer_ok(const ConvParams& p)
-{
-    if (!split_can_run(p)) return false;
-    if (p.OH * p.OW < 196) return false;       // 7 x 7 maps (round 5: 68 against 111 TFLOP/s on layer 4)
-    return p.K >= (p.kh == 1 && p.kw == 1 ? split_policy().min_k1 : split_policy().min_k3);
-}
-// ... and the launches of such a layer that take it: grids of at least half the CUs.  One wave per SIMD and 128 x 128 tiles: a small grid leaves most of the
-// chip idle where the 64 x 64 fp32 tiles still fill it (round 6, M = 1568 / 6272 / 12544 on the stage-3 3x3 layer: 13 / 52 / 108 TFLOP/s-equivalent against
-// 49 / 93 / 111 for the fp32 split-K kernel).  A launch's kernel therefore depends on its batch: maps of one image agree across batch sizes to the kernels'
-// summation-order difference (~1e-6 of the maximum), not bit for bit -- as with K1's tail balancing.
-bool split_grid_ok(const ConvParams& p)
-{
-    const long tiles = (long)(p.CoutTot / SP_T) * p.nhalves * ((p.M + SP_T - 1) / SP_T);
-    return tiles >= split_policy().min_tiles;
-}
-
-static std::atomic<long> g_split_launches{0};
-
 // the layers that stage X as a patch: "same" KxK convolutions (output map = input map) with 5 .. 25 taps whose halo fits the patch
 bool split_patch_ok(const ConvParams& p)
 {
@@ -488,6 +506,89 @@ bool split_patch_ok(const ConvParams& p)
     static const bool off = getenv("XFR_SPLIT_NO_PATCH") != nullptr;          // A/B runs: the slab for every covered layer
     return spp_halo(p) <= SPP_MAX_HALO && !off;
 }
+
+// what the kernel can run at all (xfr_debug_conv with cfg 9 asks for exactly this) ...
+bool split_can_run(const ConvParams& p)
+{
+    if (p.dualacc || p.out_stride != 1 || p.as_strided || p.co_pair > 0 || p.stride != 1) return false;
+    if ((p.Cin % SP_BK) != 0 || (p.K % SP_BK) != 0 || (p.CoutTot % SP_T) != 0) return false;
+    if (p.kh == 1 && p.kw == 1) return p.pad == 0;
+    return p.tap_major == 1 && p.kh * p.kw <= 64;
+}
+// ... the layers the engine sends to it (their packs get bf16 planes when the weights are loaded) ...
+struct SplitPolicy { int min_k1, min_k3, min_tiles, min_hw, max_parts, min_steps, min_cb, parts_below_hw; };
+const SplitPolicy& split_policy()
+{
+    // A/B runs only (tools/ab_env.sh): XFR_SPLIT_MIN_K1 / _K3 = the shallowest 1x1 / KxK layer, XFR_SPLIT_MIN_TILES = the smallest grid (tiles x K-parts),
+    // XFR_SPLIT_MIN_HW = the smallest output map, XFR_SPLIT_MAX_PARTS = the most K-parts per tile (1: none), XFR_SPLIT_MIN_STEPS / _MIN_CB = the fewest
+    // K-steps (slab) / channel blocks (patch) a part may walk
+    static const SplitPolicy pol = [] {
+        SplitPolicy q{256, 1152, 128, 49, 2, 32, 4, 196};     // round 6, same box, alternating: 1x1 from K = 512 +0.5 % (ResNet-101) / +1 % (ResNet-50-128d) over K >= 1024; from
+                                           // K = 256 level with that in time (final kernel: 1535 / 2490 against 1532 / 2499 maps/s) and closer to the reference
+                                           // (the kernel's sums are more accurate than the fp32 MFMA kernels': row-0 1 - cosine 1.1e-6 against 4.9e-6); from
+                                           // K = 128 a loss; KxK from K = 576 and grids from 64 / 196 tiles: level.
+                                           // Round 7 (profiles/r7/experiments/split_kparts_ab.txt; same box, alternating, three runs each): maps from 7 x 7 (min_hw
+                                           // 49, was 196), those maps' tiles in two K-parts of >= 4 channel blocks / >= 32 K-steps: 1569.6 / 1569.0 / 1568.6 -> 1613.0 / 1611.0 /
+                                           // 1611.0 maps/s (+2.7 %); in the serial table the stage-4 3x3 launches (two parts) 126 -> 93-102 us, 512 -> 2048 (400
+                                           // tiles, no parts) 69-71 -> 45-53 us, 2048 -> 512 (two parts) 61 -> 54-59 us.  Every cut launch of the step takes two
+                                           // parts (the workspace holds 256 / 100 tiles), so two is what ships (max_parts) and the per-part minima are the
+                                           // issue's starting points, untested against their neighbours
+        if (const char* e = getenv("XFR_SPLIT_MIN_K1")) q.min_k1 = atoi(e);
+        if (const char* e = getenv("XFR_SPLIT_MIN_K3")) q.min_k3 = atoi(e);
+        if (const char* e = getenv("XFR_SPLIT_MIN_TILES")) q.min_tiles = atoi(e);
+        if (const char* e = getenv("XFR_SPLIT_MIN_HW")) q.min_hw = atoi(e);
+        if (const char* e = getenv("XFR_SPLIT_MAX_PARTS")) q.max_parts = atoi(e);
+        if (const char* e = getenv("XFR_SPLIT_MIN_STEPS")) q.min_steps = atoi(e);
+        if (const char* e = getenv("XFR_SPLIT_MIN_CB")) q.min_cb = atoi(e);
+        if (const char* e = getenv("XFR_SPLIT_PARTS_BELOW_HW")) q.parts_below_hw = atoi(e);
+        return q;
+    }();
+    return pol;
+}
+bool split_layer_ok(const ConvParams& p)
+{
+    if (!split_can_run(p)) return false;
+    if (p.OH * p.OW < split_policy().min_hw) return false;       // (round 5 kept 7 x 7 maps out: 68 against 111 TFLOP/s on layer 4 -- a grid of 100 tiles walking the whole K; K-parts below)
+    return p.K >= (p.kh == 1 && p.kw == 1 ? split_policy().min_k1 : split_policy().min_k3);
+}
+// ... and the launches of such a layer that take it: grids of at least half the CUs.  One wave per SIMD and 128 x 128 tiles: a small grid leaves most of the
+// chip idle where the 64 x 64 fp32 tiles still fill it (round 6, M = 1568 / 6272 / 12544 on the stage-3 3x3 layer: 13 / 52 / 108 TFLOP/s-equivalent against
+// 49 / 93 / 111 for the fp32 split-K kernel).  A launch's kernel therefore depends on its batch: maps of one image agree across batch sizes to the kernels'
+// summation-order difference (~1e-6 of the maximum), not bit for bit -- as with K1's tail balancing.
+// K-parts.  A launch lasts as long as ONE tile's K loop (~0.65 us per K-step) however few tiles it has: 196 / 98 / 26 tiles of the stage-3 3x3 layer take
+// 94.6 / 93.6 / 92.8 us (profiles/r6/conv_sweep_bf16x6.txt).  A grid that leaves CUs without a tile is therefore cut along K: S parts per tile, each on
+// its own CU, met in the stream's tail workspace (the kernel's exchange).  S = the most parts that still (a) are all co-resident -- one workgroup per CU
+// in patch mode, two in slab mode, (b) walk at least min_cb channel blocks / min_steps K-steps each (shorter parts are all prologue and exchange), (c) fit
+// the workspace (64 KB per part) and the arrival counters (one per tile).  tail_force: 1 = none, S >= 2 = that many (tests, tools/conv_sweep.py).
+int split_pick_parts(const ConvParams& p)
+{
+    if (!p.tail_ws || !p.tail_cnt || p.tail_force == 1) return 1;
+    const long tiles = (long)(p.CoutTot / SP_T) * p.nhalves * ((p.M + SP_T - 1) / SP_T);
+    if (tiles > XFR_TAIL_MAX_TILES) return 1;
+    const bool patch = split_patch_ok(p);
+    const int nk = p.K / SP_BK, units = patch ? p.Cin / SP_BK : (nk + 2) / 3;
+    const long fit = std::min<long>(units, (long)(p.tail_ws_bytes / ((size_t)SP_T * SP_T * sizeof(float))) / tiles);
+    if (p.tail_force >= 2) return (int)std::max<long>(1, std::min<long>(p.tail_force, fit));
+    const SplitPolicy& pol = split_policy();
+    // only what was measured ships: two parts, and only on the maps under 14 x 14 that this rule brought to the kernel (stage 4 of the ResNets at the step's
+    // batch).  Launches of larger maps with 32 .. 127 tiles stay with the fp32 kernels as before -- nobody has timed them with parts
+    // (XFR_SPLIT_PARTS_BELOW_HW, XFR_SPLIT_MAX_PARTS open both for such a measurement)
+    if (p.OH * p.OW >= pol.parts_below_hw) return 1;
+    const long resident = patch ? 256 : 512;
+    const int min_units = patch ? pol.min_cb : (pol.min_steps + 2) / 3;
+    int S = 1;
+    for (int s = 2; s <= pol.max_parts && s <= fit; ++s)
+        if (tiles * s <= resident && units / s >= min_units) S = s;
+    return S;
+}
+bool split_grid_ok(const ConvParams& p)
+{
+    const long tiles = (long)(p.CoutTot / SP_T) * p.nhalves * ((p.M + SP_T - 1) / SP_T);
+    return tiles * split_pick_parts(p) >= split_policy().min_tiles;
+}
+
+static std::atomic<long> g_split_launches{0};
+static thread_local int g_split_last_parts = 1;
 
 // the planes of pack w, split now if this is its first launch: the split runs on the launch's stream, which is drained before the entry becomes visible
 // (another stream's launch of the same layer may follow at once)
@@ -525,7 +626,7 @@ void launch_split_inst(const ConvParams& q, const uint16_t* w0, const uint16_t* 
         (void)hipFuncSetAttribute((const void*)conv_gemm_split_kernel<RELU, CHAIN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PATCH_LDS_MAX);
         done.fetch_or(bit);
     }
-    const dim3 grid(n_co * n_m);
+    const dim3 grid(n_co * n_m * (q.tail_s > 1 ? q.tail_s : 1));
     if (patch) hipLaunchKernelGGL((conv_gemm_split_kernel<RELU, CHAIN, true>), grid, dim3(NT8), spp_lds_bytes(q), s, q, w0, w1, n_co, n_m);
     else hipLaunchKernelGGL((conv_gemm_split_kernel<RELU, CHAIN, false>), grid, dim3(NT8), SP_LDS, s, q, w0, w1, n_co, n_m);
 }
@@ -537,7 +638,7 @@ bool launch_split(const ConvParams& p, hipStream_t s)
     if (p.chain.n > 0 && p.relu_in) return false;
     ConvParams q = p;
     q.tail_q = 0;
-    q.tail_s = 1;
+    q.tail_s = split_pick_parts(p);        // K-parts per tile (1: none)
     int family = p.relu_in ? -1 : 0;       // -1: relu on the input, 0: plain epilogue, 1 / 3: compiled chain (3: MaxFeatureMap), 2: interpreted
     if (q.chain.n > 0) {
         if (conv_gemm_plan_chain(q)) return false;
@@ -551,6 +652,7 @@ bool launch_split(const ConvParams& p, hipStream_t s)
     if (!w0 || (p.nhalves == 2 && !w1)) return false;
     // counted only now: every refusal above sends the launch to an fp32 kernel
     g_split_launches++;
+    g_split_last_parts = q.tail_s;
     if (q.chain.n > 0) {
         g_conv_chain_launches[q.chain_sig >= 0 ? 0 : 1]++;
         if (q.chain_sig < 0) conv_gemm_warn_interpreted(q);
@@ -587,4 +689,5 @@ bool conv_gemm_presplit(const ConvParams& p, const float* w, hipStream_t s) { re
 bool conv_gemm_split_wanted(const ConvParams& p) { return split_layer_ok(p) && (p.split_ok == 2 || split_grid_ok(p)); }
 bool conv_gemm_launch_split(const ConvParams& p, hipStream_t s) { return launch_split(p, s); }
 long conv_gemm_split_launches() { return g_split_launches.load(); }
+int conv_gemm_split_last_parts() { return g_split_last_parts; }
 

@@ -948,11 +948,16 @@ xfr_status xfr_debug_conv(const float* in_dev, const float* w_host, const float*
     p.relu_in = relu_in; p.out_H = p.OH; p.out_W = p.OW; p.out_stride = 1;
     p.in_bytes = (unsigned)((size_t)cin * nb * h * w * sizeof(float));
     p.tap_major = tap4 ? 2 : (tap ? 1 : 0); p.force_cfg = cfg % 100;
-    float* tws = nullptr;
-    HIP_TRY(hipMalloc(&tws, XFR_TAIL_WS_BYTES + XFR_TAIL_MAX_TILES * sizeof(unsigned)));
+    // ONE tail workspace for every call of the process (null stream; never freed), its arrival counters zeroed when it is made and never again: like
+    // a stream's workspace in the engine, it sees launches of different kernels and part counts one after the other, and a launch that left a counter
+    // behind would break the next call's (tests/test_gpu_split_kparts.py)
+    static float* tws = nullptr;
+    if (!tws) {
+        HIP_TRY(hipMalloc(&tws, XFR_TAIL_WS_BYTES + XFR_TAIL_MAX_TILES * sizeof(unsigned)));
+        HIP_TRY(hipMemset(reinterpret_cast<char*>(tws) + XFR_TAIL_WS_BYTES, 0, XFR_TAIL_MAX_TILES * sizeof(unsigned)));
+    }
     p.tail_ws = tws; p.tail_ws_bytes = XFR_TAIL_WS_BYTES;
     p.tail_cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(tws) + XFR_TAIL_WS_BYTES);
-    HIP_TRY(hipMemset(p.tail_cnt, 0, XFR_TAIL_MAX_TILES * sizeof(unsigned)));
     p.tail_force = (cfg / 10000) % 100;  // 0 heuristic, 1 off, S >= 2 forced
     const bool split = (cfg % 100) == CFG_BF16X6;  // the bf16x6 kernel (layers it does not cover run the fp32 kernel the rules give, like in the engine)
     hipEvent_t a, b;
@@ -1006,7 +1011,6 @@ xfr_status xfr_debug_conv(const float* in_dev, const float* w_host, const float*
     (void)hipEventDestroy(a); (void)hipEventDestroy(b);
     if (split) conv_gemm_forget_split(wd, host.size() * sizeof(float));
     (void)hipFree(wd);
-    (void)hipFree(tws);
     if (bd) (void)hipFree(bd);
     HIP_TRY(hipGetLastError());
     return XFR_OK;
