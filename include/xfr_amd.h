@@ -443,6 +443,56 @@ xfr_status xfr_weighted_subtree_ebp(xfr_engine* e, const float* x_dev, int32_t n
 xfr_status xfr_ebp_store_firing(xfr_engine* e, const float* x_dev, int32_t n, int32_t seed_tensor, const float* seed_dev,
                                 int32_t firing, float* out_dev, int32_t* c, int32_t* h, int32_t* w, void* stream);
 
+/* ---- STRise blackbox saliency (python/xfr/models/blackbox.py:299-442).  Additive entry points, ABI version 7. -------------------
+ * The reference builds num_masks float64 masks (blackbox.py:320-336), the masked probes (:338-345), scores them (:366-414) and merges the masks
+ * weighted by their scores (:416-442), all on the host.  Here a mask is never stored: it is its drawn cells (the zeros of the gh x gw grid of
+ * blackbox.py:320-323, row-major indices) and its shift (x, y) of :331-332, and every kernel evaluates it from those in float64:
+ *     c = (o + 0.5) * gh / (H + mask_scale) - 0.5,  o = output row + x  (columns alike with gw, W, y);  rows floor(c) and floor(c) + 1 through the
+ *     mirror map i -> |i| mod 2 (gh - 1), folded at gh - 1;  mask = bilinear blend of the four grid values
+ * which is skimage.transform.resize(order=1, mode='reflect', anti_aliasing=False) of skimage >= 0.19 cropped at [x : x + H, y : y + W] (:333).
+ * H x W is the engine's input size.  cells_host: n_masks x num_elements int32, shifts_host: n_masks x 2 int32, both HOST arrays.  Every call
+ * returns XFR_INVALID_ARG, before anything is launched, for a cell index outside [0, gh * gw), a shift outside [0, mask_scale),
+ * mask_scale > min(H, W) or gh * gw > 4096. */
+typedef struct {
+    int32_t grid_h, grid_w;     /* gh, gw: ceil(H / mask_scale), ceil(W / mask_scale) in the reference (:302) */
+    int32_t mask_scale;
+    int32_t num_elements;       /* num_mask_elements: drawn cells per mask */
+} xfr_strise_geometry;
+
+/* blackbox.py:338-345 (apply_masks_using_image), resnet.py:25-37 (convert_resnet101v4_image), :366-394 (resnet_bb_fn, contrastive_triplet_similarity)
+ * and :396-414 (score_masks) for all masks of one probe.
+ *   probe_u8_dev  H x W x 3 uint8, fill_dev H x W x 3 float64 (the blurred probe of :352-357 or the constant 0.5 of :348): masked probe k is
+ *                 (float)(mask_k * probe + (1 - mask_k) * fill - mean[c]), evaluated in float64, written by the device straight into the forward's
+ *                 input; the engine's uint8 preprocessing must be XFR_U8_SUB_MEAN with 3 channels (its means are used), else XFR_INVALID_ARG
+ *   refs_dev      n_refs x D, gallery_dev n_gal x D: fp32 embeddings at encode_tensor (D = C * H * W of it); n_refs == n_gal, or one of them is 1
+ *                 (the broadcast of :391-393), else XFR_INVALID_ARG
+ *   scores_dev    n_masks float64: mean_j[(sim0_ref_j - simk_ref_j) - (sim0_gal_j - simk_gal_j)], sim = 1 - 0.5 |p / |p| - g / |g||, in float64 from
+ *                 the fp32 embeddings
+ *   orig_dev      (may be NULL) n_refs + n_gal float64: the unmasked probe's similarities (original_probe_ref_scores, original_probe_gallery_scores)
+ * The sweep runs in batches of the engine's max_batch through xfr_forward; the unmasked probe rides along as image zero, and the last batch is
+ * padded with all-ones masks whose results are dropped, so one schedule serves every batch -- results depend on max_batch like those of xfr_forward.
+ * The masked probes of batch i + 1 are generated on a side stream while batch i is encoded.  The host blocks once, before the first launch, until
+ * the work already queued on `stream` has finished (the cell table is copied from pageable memory behind it); the call does not wait for its own
+ * launches. */
+xfr_status xfr_strise_score(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host, const int32_t* shifts_host,
+                            int32_t n_masks, const xfr_strise_geometry* geom, const float* refs_dev, int32_t n_refs, const float* gallery_dev,
+                            int32_t n_gal, int32_t encode_tensor, double* scores_dev, double* orig_dev, void* stream);
+
+/* blackbox.py:416-421 (combine_masks) and :434-441: sal_dev (H x W float64) = m - min(m), / max, with m = sign * (1 - sum_k w_k mask_k / n_selected);
+ * sign +1 is the positive_scores branch (:434), -1 the other (:438).  weights_dev: n_masks float64, the score of a selected mask and 0 for every
+ * other; n_selected: the count of selected masks (the divisor of .mean(axis=0)).  The cells of one mask must be distinct (they are drawn without
+ * replacement, :322), else XFR_INVALID_ARG.  Accumulates in float64 without atomics: bit-reproducible.  Synchronises `stream` once, before the launches. */
+xfr_status xfr_strise_combine(xfr_engine* e, const double* weights_dev, int32_t n_selected, const int32_t* cells_host, const int32_t* shifts_host,
+                              int32_t n_masks, const xfr_strise_geometry* geom, int32_t sign, double* sal_dev, void* stream);
+
+/* Parity hooks: masks [first, first + count) as float64 count x H x W (self.masks of :336), and their fp32 network input count x 3 x H x W (what
+ * xfr_strise_score feeds the forward).  count <= max_batch for the second. */
+xfr_status xfr_strise_debug_masks(xfr_engine* e, const int32_t* cells_host, const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom,
+                                  int32_t first, int32_t count, double* masks_dev, void* stream);
+xfr_status xfr_strise_debug_masked_probes(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host,
+                                          const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom, int32_t first, int32_t count,
+                                          float* out_nchw_dev, void* stream);
+
 /* Debug / parity: after an xfr_ebp call made while tracing is enabled, the per-firing trace
  * sum(P[i]) (what the golden fixtures store for every entry of Whitebox.P, whitebox.py:394).
  * xfr_engine_set_trace(e, 1) makes xfr_ebp record it (slower).  `sums` receives n_firings x S x N doubles

@@ -30,6 +30,10 @@ class SubtreeArgs(ctypes.Structure):
                 ('sweep_batch', ctypes.c_int32), ('order_fn', SUBTREE_ORDER_FN), ('order_user', ctypes.c_void_p)]
 
 
+class StriseGeometry(ctypes.Structure):
+    _fields_ = [('grid_h', ctypes.c_int32), ('grid_w', ctypes.c_int32), ('mask_scale', ctypes.c_int32), ('num_elements', ctypes.c_int32)]
+
+
 class XfrError(RuntimeError):
     def __init__(self, status, msg):
         RuntimeError.__init__(self, msg)
@@ -83,6 +87,10 @@ SYMBOLS = [
     ('xfr_layerwise_ebp', _I, [_P, _P, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_F), _P, _P, _P]),
     ('xfr_weighted_subtree_ebp', _I, [_P, _P, _I, _I, _P, ctypes.POINTER(SubtreeArgs), _P, _P, ctypes.POINTER(_F), ctypes.POINTER(_I),
                                       ctypes.POINTER(_I), _P]),
+    ('xfr_strise_score', _I, [_P, _P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _P, _I, _P, _I, _I, _P, _P, _P]),
+    ('xfr_strise_combine', _I, [_P, _P, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _P, _P]),
+    ('xfr_strise_debug_masks', _I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _I, _P, _P]),
+    ('xfr_strise_debug_masked_probes', _I, [_P, _P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _I, _P, _P]),
     ('xfr_ebp_store_firing', _I, [_P, _P, _I, _I, _P, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _P]),
     ('xfr_engine_set_trace', _I, [_P, _I]),
     ('xfr_engine_trace_size', _I, [_P, ctypes.POINTER(_I)]),

@@ -420,3 +420,36 @@ void launch_gather_rows(const float* src, float* dst, const int* pairs_dev, int 
 void launch_reverse_slots(float* store, const int* cnt_dev, int N, int topk, int HW, hipStream_t s);
 void launch_subtree_merge(const float* store, const SubtreeSlot* tab_dev, const int* cnt_dev, float* out, int N, int topk, int HW, int do_max,
                           int mode_u8, float eps, hipStream_t s);
+
+// ---- wavefront (64-lane) shuffle reductions of saliency.hip and strise.hip: the result is complete in lane 0 -------------------
+__device__ inline double wave_sum(double v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    return v;
+}
+
+// the float64 form of the minimum / maximum reduction of saliency.hip's subtree_merge_kernel
+__device__ inline void wave_min_max(double& mn, double& mx)
+{
+    for (int d = 32; d > 0; d >>= 1) { mn = fmin(mn, __shfl_down(mn, d)); mx = fmax(mx, __shfl_down(mx, d)); }
+}
+
+// ---- STRise blackbox saliency (strise.hip; python/xfr/models/blackbox.py:299-442) ----------------------------
+// geometry of the sparse masks: images H x W, a grid of gh x gw cells, masks resized to (H + scale) x (W + scale) and cropped at their shift,
+// n_elem drawn cells per mask.  cells [n][n_elem] (cell < 0: none -- the all-ones mask), shifts [n][2] = (row shift, column shift).
+constexpr int STRISE_MAX_CELLS = 4096;
+struct StriseGeom { int H, W, gh, gw, scale, n_elem; double ry, rx; };      // ry = gh / (H + scale), rx = gw / (W + scale)
+// out [n][3][H][W] = (float)(mask * u8 + (1 - mask) * fill - mean[c]) in float64; probe uint8 H x W x 3, fill float64 H x W x 3
+void launch_strise_masked(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, float* out, const StriseGeom& g,
+                          const double* mean, hipStream_t s);
+// out [n][H][W]: the float64 masks (parity hook)
+void launch_strise_masks(const int* cells, const int* shifts, int n, double* out, const StriseGeom& g, hipStream_t s);
+// orig [n_refs + n_gal] = similarity of emb0 to every reference / gallery embedding, ginv = 1 / |g| of each
+void launch_strise_orig(const float* emb0, const float* refs, int n_refs, const float* gal, int n_gal, int D, double* orig, double* ginv, hipStream_t s);
+// scores[i] = contrastive triplet similarity of embedding first + i, i < count
+void launch_strise_score(const float* emb, int first, int count, const float* refs, int n_refs, const float* gal, int n_gal, int D, const double* orig,
+                         const double* ginv, double* scores, hipStream_t s);
+// sal [H][W] = normalised sign * (1 - sum_k w_k mask_k / count); order / group_off: the mask indices grouped by shift (group = sx * scale + sy);
+// A [scale^2][gh * gw] and wsum [scale^2] are scratch
+void launch_strise_merge(const double* weights, const int* cells, const int* order, const int* group_off, double* A, double* wsum, double count, double sign,
+                         double* sal, const StriseGeom& g, hipStream_t s);

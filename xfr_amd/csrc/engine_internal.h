@@ -6,6 +6,7 @@
 //   backward.hip       chain resolution and the sweep executor
 //   engine.hip         the C ABI: create / destroy / weights / setters / forward / EBP / contrastive / triplet / uint8 / profiling
 //   subtree.hip        the C ABI: layerwise and weighted-subtree EBP
+//   strise_abi.hip     the C ABI: STRise blackbox saliency
 //   comm.hip           the C ABI: the RCCL binding
 //   plan_describe.hip  the C ABI: xfr_plan_describe
 #pragma once
@@ -248,6 +249,8 @@ struct xfr_engine {
     long last_gemm_launches = 0;
     double last_gemm_flops = 0.0;
 
+    struct StriseState* strise = nullptr;   // xfr_strise_*: buffers, side stream and events, built on first use (strise_abi.hip)
+
     float* t_bank = nullptr;       // when set, true activations live in this bank (gallery forward of a triplet step)
     float* ws_enc = nullptr;       // second bank of true activations (T region only), allocated on first use
     size_t t_region_floats = 0;
@@ -322,5 +325,8 @@ xfr_status check_run(xfr_engine* e, const void* x, int n);
 xfr_status fence_slot0(xfr_engine* e, hipStream_t s);
 xfr_status ebp_core(xfr_engine* e, const float* x_dev, int n, int S, int seed_tensor, const float* seed_dev, hipStream_t s);
 void presplit_weights(xfr_engine* e);
+
+// strise_abi.hip
+void strise_release(xfr_engine* e);
 
 }  // namespace xfr

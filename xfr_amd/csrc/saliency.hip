@@ -1,6 +1,6 @@
 // saliency.hip -- the tail of the hot path: channel pooling, per-sample normalisation, contrastive and truncated
 // contrastive combination (whitebox.py:499, :524-526, :547-557) and _mwp_to_saliency (whitebox.py:448-460,
-// ebp_ver 6 branch).  Wavefront (64-lane) shuffle reductions; fp64 accumulation for the normalisation sums.
+// ebp_ver 6 branch).  Wavefront (64-lane) shuffle reductions (common.h); fp64 accumulation for the normalisation sums.
 #include "common.h"
 #include <math.h>
 #include <string.h>
@@ -8,12 +8,6 @@
 namespace {
 
 constexpr int NT = 256;
-
-__device__ inline double wave_sum(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
 
 // pooled[sb][hw] = sum_c P[c][sb][hw]   (np.sum(axis=1), whitebox.py:499)
 __global__ __launch_bounds__(NT) void channel_pool_kernel(const float* __restrict__ P, float* __restrict__ pooled, int C,

@@ -1,0 +1,280 @@
+// strise.hip -- the device side of STRise blackbox saliency (python/xfr/models/blackbox.py:299-442): sparse masks, masked probes, triplet scores and the
+// weighted merge.  A mask is never stored on the sweep and merge paths: it is a function of its drawn cells and its shift, evaluated in float64 where
+// it is needed.  The mask law (blackbox.py:333, skimage.transform.resize(order=1, mode='reflect', anti_aliasing=False) of skimage >= 0.19, i.e.
+// scipy.ndimage.zoom(order=1, mode='mirror', grid_mode=True)), for output row r of a mask with shift (x, y):
+//     c  = (r + x + 0.5) * (gh / (H + s)) - 0.5,  i0 = floor(c),  f = c - i0      (columns alike with y, gw, W)
+//     rows i0 and i0 + 1 through the mirror map  i -> |i| mod 2 (gh - 1), folded at gh - 1
+//     mask = bilinear blend of the four grid values (1 everywhere, 0 at the drawn cells)
+// The host side (argument checks, batching, streams) is strise_abi.hip.
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int NT = 256;
+
+__device__ inline int mirror_index(int i, int g)
+{
+    if (g == 1) return 0;
+    const int p = 2 * (g - 1);
+    i = (i < 0 ? -i : i) % p;
+    return i > g - 1 ? p - i : i;
+}
+
+// the two taps and the weight of the second one for output coordinate o (shift included) of an axis with g cells; ratio = g / (size + scale), divided
+// once on the host -- the order in which scipy's zoom evaluates the coordinate
+__device__ inline void axis_taps(int o, int g, double ratio, int& i0, int& i1, double& f)
+{
+    const double c = __dsub_rn(__dmul_rn((double)o + 0.5, ratio), 0.5);
+    const double fl = floor(c);
+    f = c - fl;
+    i0 = mirror_index((int)fl, g);
+    i1 = mirror_index((int)fl + 1, g);
+}
+
+__device__ inline double blend(double v00, double v01, double v10, double v11, double fy, double fx)
+{
+    const double top = __dadd_rn(__dmul_rn(1.0 - fx, v00), __dmul_rn(fx, v01));
+    const double bot = __dadd_rn(__dmul_rn(1.0 - fx, v10), __dmul_rn(fx, v11));
+    return __dadd_rn(__dmul_rn(1.0 - fy, top), __dmul_rn(fy, bot));
+}
+
+// the grid of one mask in LDS: 1 everywhere, 0 at its cells (cell < 0: no cell -- the all-ones mask of the unmasked probe and of the padding)
+__device__ inline void build_grid(uint8_t* grid, const int* __restrict__ cells, int n_elem, int cells_total)
+{
+    for (int i = threadIdx.x; i < cells_total; i += blockDim.x) grid[i] = 1;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_elem; i += blockDim.x) {
+        const int c = cells[i];
+        if (c >= 0 && c < cells_total) grid[c] = 0;
+    }
+    __syncthreads();
+}
+
+// K_strise_masked: the fp32 network input of a batch of masked probes, NCHW, (float)(mask * u8 + (1 - mask) * fill - mean[c]) in float64
+// (blackbox.py:343 and resnet.py:32,37).  One thread: four pixels of a row, the mask once per pixel, three channels; float4 stores along W.  Eight waves per SIMD (64 VGPRs): the kernel runs
+// beside the forward of the batch before and must not take its occupancy.
+__global__ __launch_bounds__(NT, 8) void strise_masked_kernel(const uint8_t* __restrict__ probe, const double* __restrict__ fill, const int* __restrict__ cells,
+                                                           const int* __restrict__ shifts, float* __restrict__ out, StriseGeom g, double m0, double m1, double m2)
+{
+    __shared__ uint8_t grid[STRISE_MAX_CELLS];
+    const int k = blockIdx.y;
+    build_grid(grid, cells + (size_t)k * g.n_elem, g.n_elem, g.gh * g.gw);
+    const int W4 = (g.W + 3) >> 2;
+    const int q = blockIdx.x * NT + threadIdx.x;
+    if (q >= g.H * W4) return;
+    const int row = q / W4, x0 = (q - row * W4) * 4;
+    const int sx = shifts[2 * k], sy = shifts[2 * k + 1];
+    int r0, r1;
+    double fy;
+    axis_taps(row + sx, g.gh, g.ry, r0, r1, fy);
+    const uint8_t* g0 = grid + r0 * g.gw;
+    const uint8_t* g1 = grid + r1 * g.gw;
+    double m[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int c0, c1;
+        double fx;
+        axis_taps(min(x0 + j, g.W - 1) + sy, g.gw, g.rx, c0, c1, fx);
+        m[j] = blend((double)g0[c0], (double)g0[c1], (double)g1[c0], (double)g1[c1], fy, fx);
+    }
+    const double mean[3] = {m0, m1, m2};
+    const size_t plane = (size_t)g.H * g.W;
+    const size_t px = ((size_t)row * g.W + x0) * 3;
+    float* o = out + (size_t)k * 3 * plane + (size_t)row * g.W + x0;
+    const bool vec = (g.W & 3) == 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const size_t at = px + 3 * (vec ? j : min(j, g.W - 1 - x0)) + c;
+            const double blended = __dadd_rn(__dmul_rn(m[j], (double)probe[at]), __dmul_rn(__dsub_rn(1.0, m[j]), fill[at]));
+            v[j] = (float)__dsub_rn(blended, mean[c]);
+        }
+        if (vec) {
+            *reinterpret_cast<float4*>(o + c * plane) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+            for (int j = 0; j < 4 && x0 + j < g.W; ++j) o[c * plane + j] = v[j];
+        }
+    }
+}
+
+// parity hook: the float64 masks themselves, n x H x W
+__global__ __launch_bounds__(NT) void strise_masks_kernel(const int* __restrict__ cells, const int* __restrict__ shifts, double* __restrict__ out, StriseGeom g)
+{
+    __shared__ uint8_t grid[STRISE_MAX_CELLS];
+    const int k = blockIdx.y;
+    build_grid(grid, cells + (size_t)k * g.n_elem, g.n_elem, g.gh * g.gw);
+    const int q = blockIdx.x * NT + threadIdx.x;
+    if (q >= g.H * g.W) return;
+    const int row = q / g.W, x = q - row * g.W;
+    int r0, r1, c0, c1;
+    double fy, fx;
+    axis_taps(row + shifts[2 * k], g.gh, g.ry, r0, r1, fy);
+    axis_taps(x + shifts[2 * k + 1], g.gw, g.rx, c0, c1, fx);
+    out[(size_t)k * g.H * g.W + q] = blend((double)grid[r0 * g.gw + c0], (double)grid[r0 * g.gw + c1], (double)grid[r1 * g.gw + c0],
+                                           (double)grid[r1 * g.gw + c1], fy, fx);
+}
+
+// common.h's wavefront sum, handed to every lane
+__device__ inline double wave_sum_all(double v) { return __shfl(wave_sum(v), 0); }
+
+// 1 / |v| of a D-vector, by one wavefront (every lane returns it)
+__device__ inline double wave_inv_norm(const float* __restrict__ v, int D, int lane)
+{
+    double acc = 0.0;
+    for (int d = lane; d < D; d += 64) acc += (double)v[d] * (double)v[d];
+    return 1.0 / sqrt(wave_sum_all(acc));
+}
+
+// blackbox.py:385: 1 - 0.5 * | p / |p| - g / |g| |
+__device__ inline double wave_similarity(const float* __restrict__ p, double pinv, const float* __restrict__ gv, double ginv, int D, int lane)
+{
+    double acc = 0.0;
+    for (int d = lane; d < D; d += 64) {
+        const double t = (double)p[d] * pinv - (double)gv[d] * ginv;
+        acc += t * t;
+    }
+    return 1.0 - 0.5 * sqrt(wave_sum_all(acc));
+}
+
+// the unmasked probe against every reference and gallery embedding (blackbox.py:398,403), and 1 / |g| of each: one wavefront per vector
+__global__ __launch_bounds__(NT) void strise_orig_kernel(const float* __restrict__ emb0, const float* __restrict__ refs, int n_refs, const float* __restrict__ gal,
+                                                         int n_gal, int D, double* __restrict__ orig, double* __restrict__ ginv)
+{
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    if (j >= n_refs + n_gal) return;
+    const float* gv = j < n_refs ? refs + (size_t)j * D : gal + (size_t)(j - n_refs) * D;
+    const double gi = wave_inv_norm(gv, D, lane);
+    const double pinv = wave_inv_norm(emb0, D, lane);
+    const double sim = wave_similarity(emb0, pinv, gv, gi, D, lane);
+    if (lane == 0) { orig[j] = sim; ginv[j] = gi; }
+}
+
+// K_strise_score: contrastive triplet similarity (blackbox.py:390-394) of the images [first, first + count) of a batch, one wavefront per mask:
+// a wavefront reduction over D per (mask, reference | gallery image), then the mean over the broadcast pairs
+__global__ __launch_bounds__(NT) void strise_score_kernel(const float* __restrict__ emb, int first, int count, const float* __restrict__ refs, int n_refs,
+                                                          const float* __restrict__ gal, int n_gal, int D, const double* __restrict__ orig,
+                                                          const double* __restrict__ ginv, double* __restrict__ scores)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    if (i >= count) return;
+    const float* p = emb + (size_t)(first + i) * D;
+    const double pinv = wave_inv_norm(p, D, lane);
+    const int J = max(n_refs, n_gal);
+    // a lone reference or gallery image is broadcast over the other side (blackbox.py:391-393): its similarity is taken once
+    const bool one_ref = n_refs == 1 && J > 1, one_gal = n_gal == 1 && J > 1;
+    double sr = one_ref ? wave_similarity(p, pinv, refs, ginv[0], D, lane) : 0.0;
+    double sg = one_gal ? wave_similarity(p, pinv, gal, ginv[n_refs], D, lane) : 0.0;
+    double acc = 0.0;
+    for (int j = 0; j < J; ++j) {
+        const int jr = one_ref ? 0 : j, jg = one_gal ? 0 : j;
+        if (!one_ref) sr = wave_similarity(p, pinv, refs + (size_t)jr * D, ginv[jr], D, lane);
+        if (!one_gal) sg = wave_similarity(p, pinv, gal + (size_t)jg * D, ginv[n_refs + jg], D, lane);
+        acc += (orig[jr] - sr) - (orig[n_refs + jg] - sg);
+    }
+    if (lane == 0) scores[i] = acc / (double)J;
+}
+
+// Merge, step 1.  Masks that share a shift share their interpolation weights, and the blend is linear in the grid: per shift, the weighted sum of
+// the masks is the blend of  A[cell] = sum of w_k over the masks k that drew the cell  taken from the sum of their weights.  One workgroup per
+// shift walks its masks in index order; the cells of one mask are distinct (drawn without replacement), so the adds of one mask do not meet.
+__global__ __launch_bounds__(NT) void strise_merge_cells_kernel(const double* __restrict__ weights, const int* __restrict__ cells, const int* __restrict__ order,
+                                                                const int* __restrict__ group_off, double* __restrict__ A, double* __restrict__ wsum, StriseGeom g)
+{
+    __shared__ double acc[STRISE_MAX_CELLS];
+    const int grp = blockIdx.x, nc = g.gh * g.gw;
+    for (int i = threadIdx.x; i < nc; i += NT) acc[i] = 0.0;
+    double total = 0.0;
+    __syncthreads();
+    for (int m = group_off[grp]; m < group_off[grp + 1]; ++m) {
+        const int k = order[m];
+        const double w = weights[k];
+        if (w == 0.0) continue;
+        total += w;
+        for (int i = threadIdx.x; i < g.n_elem; i += NT) acc[cells[(size_t)k * g.n_elem + i]] += w;
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < nc; i += NT) A[(size_t)grp * nc + i] = acc[i];
+    if (threadIdx.x == 0) wsum[grp] = total;
+}
+
+// Merge, step 2: per pixel, sum over the shifts of (sum of weights - blend of A), then sign * (1 - sum / count)  (blackbox.py:416-438)
+__global__ __launch_bounds__(NT) void strise_merge_pixels_kernel(const double* __restrict__ A, const double* __restrict__ wsum, double count, double sign,
+                                                                 double* __restrict__ sal, StriseGeom g)
+{
+    const int q = blockIdx.x * NT + threadIdx.x;
+    if (q >= g.H * g.W) return;
+    const int row = q / g.W, x = q - row * g.W, nc = g.gh * g.gw;
+    double acc = 0.0;
+    for (int sx = 0; sx < g.scale; ++sx) {
+        int r0, r1;
+        double fy;
+        axis_taps(row + sx, g.gh, g.ry, r0, r1, fy);
+        for (int sy = 0; sy < g.scale; ++sy) {
+            const int grp = sx * g.scale + sy;
+            const double ws = wsum[grp];
+            if (ws == 0.0) continue;
+            int c0, c1;
+            double fx;
+            axis_taps(x + sy, g.gw, g.rx, c0, c1, fx);
+            const double* a = A + (size_t)grp * nc;
+            acc += ws - blend(a[r0 * g.gw + c0], a[r0 * g.gw + c1], a[r1 * g.gw + c0], a[r1 * g.gw + c1], fy, fx);
+        }
+    }
+    sal[q] = sign * (1.0 - acc / count);
+}
+
+// Merge, step 3: min-shift and max-normalise (blackbox.py:440-441), one workgroup, on the wavefront reductions of common.h
+__global__ __launch_bounds__(1024) void strise_normalize_kernel(double* __restrict__ sal, int n)
+{
+    __shared__ double s_mn[16], s_mx[16];
+    double mn = INFINITY, mx = -INFINITY;
+    for (int i = threadIdx.x; i < n; i += 1024) { const double v = sal[i]; mn = fmin(mn, v); mx = fmax(mx, v); }
+    wave_min_max(mn, mx);
+    if ((threadIdx.x & 63) == 0) { s_mn[threadIdx.x >> 6] = mn; s_mx[threadIdx.x >> 6] = mx; }
+    __syncthreads();
+    mn = s_mn[0]; mx = s_mx[0];
+    for (int i = 1; i < 16; ++i) { mn = fmin(mn, s_mn[i]); mx = fmax(mx, s_mx[i]); }
+    const double top = mx - mn;
+    for (int i = threadIdx.x; i < n; i += 1024) sal[i] = (sal[i] - mn) / top;
+}
+
+}  // namespace
+
+void launch_strise_masked(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, float* out, const StriseGeom& g,
+                          const double* mean, hipStream_t s)
+{
+    const int quads = g.H * ((g.W + 3) / 4);
+    hipLaunchKernelGGL(strise_masked_kernel, dim3((quads + NT - 1) / NT, n), dim3(NT), 0, s, probe, fill, cells, shifts, out, g, mean[0], mean[1], mean[2]);
+}
+
+void launch_strise_masks(const int* cells, const int* shifts, int n, double* out, const StriseGeom& g, hipStream_t s)
+{
+    hipLaunchKernelGGL(strise_masks_kernel, dim3((g.H * g.W + NT - 1) / NT, n), dim3(NT), 0, s, cells, shifts, out, g);
+}
+
+void launch_strise_orig(const float* emb0, const float* refs, int n_refs, const float* gal, int n_gal, int D, double* orig, double* ginv, hipStream_t s)
+{
+    const int per = NT / 64;
+    hipLaunchKernelGGL(strise_orig_kernel, dim3((n_refs + n_gal + per - 1) / per), dim3(NT), 0, s, emb0, refs, n_refs, gal, n_gal, D, orig, ginv);
+}
+
+void launch_strise_score(const float* emb, int first, int count, const float* refs, int n_refs, const float* gal, int n_gal, int D, const double* orig,
+                         const double* ginv, double* scores, hipStream_t s)
+{
+    if (count < 1) return;
+    const int per = NT / 64;
+    hipLaunchKernelGGL(strise_score_kernel, dim3((count + per - 1) / per), dim3(NT), 0, s, emb, first, count, refs, n_refs, gal, n_gal, D, orig, ginv, scores);
+}
+
+void launch_strise_merge(const double* weights, const int* cells, const int* order, const int* group_off, double* A, double* wsum, double count, double sign,
+                         double* sal, const StriseGeom& g, hipStream_t s)
+{
+    hipLaunchKernelGGL(strise_merge_cells_kernel, dim3(g.scale * g.scale), dim3(NT), 0, s, weights, cells, order, group_off, A, wsum, g);
+    hipLaunchKernelGGL(strise_merge_pixels_kernel, dim3((g.H * g.W + NT - 1) / NT), dim3(NT), 0, s, A, wsum, count, sign, sal, g);
+    hipLaunchKernelGGL(strise_normalize_kernel, dim3(1), dim3(1024), 0, s, sal, g.H * g.W);
+}

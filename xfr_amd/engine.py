@@ -492,6 +492,79 @@ class Engine(object):
                                                      out.data_ptr(), None, None, None, _stream_ptr(self.device)))
         return out
 
+    # -- STRise blackbox saliency (include/xfr_amd.h: xfr_strise_*) ---------------------------------------
+    @staticmethod
+    def _strise_tables(cells, shifts, grid, mask_scale):
+        """-> (cells int32 n x E, shifts int32 n x 2, StriseGeometry, their ctypes pointers)."""
+        cells = np.ascontiguousarray(np.asarray(cells, dtype=np.int32))
+        shifts = np.ascontiguousarray(np.asarray(shifts, dtype=np.int32))
+        if cells.ndim != 2 or shifts.shape != (cells.shape[0], 2):
+            raise ValueError('cells must be n_masks x num_elements and shifts n_masks x 2, got %s and %s' % (cells.shape, shifts.shape))
+        geom = _lib.StriseGeometry(int(grid[0]), int(grid[1]), int(mask_scale), int(cells.shape[1]))
+        ip = ctypes.POINTER(ctypes.c_int32)
+        return cells, shifts, geom, cells.ctypes.data_as(ip), shifts.ctypes.data_as(ip)
+
+    def _strise_images(self, probe_u8, fill):
+        c, h, w = self.program.in_shape
+        probe_u8 = torch.as_tensor(probe_u8)
+        fill = torch.as_tensor(fill)
+        if probe_u8.dtype != torch.uint8 or tuple(probe_u8.shape) != (h, w, 3) or tuple(fill.shape) != (h, w, 3):
+            raise ValueError('expected a uint8 probe and a fill image of %d x %d x 3, got %s %s and %s' % (h, w, probe_u8.dtype, tuple(probe_u8.shape),
+                                                                                                      tuple(fill.shape)))
+        return probe_u8.to(self.device).contiguous(), fill.to(self.device, torch.float64).contiguous()
+
+    def strise_score(self, probe_u8, fill, cells, shifts, grid, mask_scale, refs, gallery, encode_tensor):
+        """The whole STRise sweep of one probe (xfr_strise_score): probe uint8 H x W x 3, fill float64 H x W x 3, refs / gallery fp32 embeddings
+        (n x D).  -> (scores float64 [n_masks], orig float64 [n_refs + n_gal]: the unmasked probe's similarities), device tensors."""
+        cells, shifts, geom, cp, sp = self._strise_tables(cells, shifts, grid, mask_scale)
+        probe_u8, fill = self._strise_images(probe_u8, fill)
+        d = int(np.prod(self.tensor_shape(encode_tensor)))
+        refs = refs.detach().to(self.device, torch.float32).reshape(-1, d).contiguous()
+        gallery = gallery.detach().to(self.device, torch.float32).reshape(-1, d).contiguous()
+        scores = torch.empty(cells.shape[0], device=self.device, dtype=torch.float64)
+        orig = torch.empty(refs.shape[0] + gallery.shape[0], device=self.device, dtype=torch.float64)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.xfr_strise_score(self._h, probe_u8.data_ptr(), fill.data_ptr(), cp, sp, cells.shape[0], ctypes.byref(geom),
+                                                 refs.data_ptr(), refs.shape[0], gallery.data_ptr(), gallery.shape[0], int(encode_tensor),
+                                                 scores.data_ptr(), orig.data_ptr(), _stream_ptr(self.device)))
+        return scores, orig
+
+    def strise_combine(self, weights, n_selected, cells, shifts, grid, mask_scale, sign=1):
+        """xfr_strise_combine: weights float64 [n_masks] (0 for unselected masks) -> the normalised H x W float64 map (device tensor)."""
+        cells, shifts, geom, cp, sp = self._strise_tables(cells, shifts, grid, mask_scale)
+        weights = torch.as_tensor(weights).detach().to(self.device, torch.float64).contiguous()
+        if tuple(weights.shape) != (cells.shape[0],):
+            raise ValueError('weights must hold %d values, got %s' % (cells.shape[0], tuple(weights.shape)))
+        c, h, w = self.program.in_shape
+        sal = torch.empty((h, w), device=self.device, dtype=torch.float64)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.xfr_strise_combine(self._h, weights.data_ptr(), int(n_selected), cp, sp, cells.shape[0], ctypes.byref(geom), int(sign),
+                                                   sal.data_ptr(), _stream_ptr(self.device)))
+        return sal
+
+    def strise_masks(self, cells, shifts, grid, mask_scale, first=0, count=None):
+        """Parity hook: masks [first, first + count) as float64 count x H x W (device tensor)."""
+        cells, shifts, geom, cp, sp = self._strise_tables(cells, shifts, grid, mask_scale)
+        count = cells.shape[0] - first if count is None else int(count)
+        c, h, w = self.program.in_shape
+        out = torch.empty((max(count, 0), h, w), device=self.device, dtype=torch.float64)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.xfr_strise_debug_masks(self._h, cp, sp, cells.shape[0], ctypes.byref(geom), int(first), count, out.data_ptr(),
+                                                       _stream_ptr(self.device)))
+        return out
+
+    def strise_masked_probes(self, probe_u8, fill, cells, shifts, grid, mask_scale, first=0, count=None):
+        """Parity hook: the fp32 network input (count x 3 x H x W) of masks [first, first + count), count <= max_batch."""
+        cells, shifts, geom, cp, sp = self._strise_tables(cells, shifts, grid, mask_scale)
+        probe_u8, fill = self._strise_images(probe_u8, fill)
+        count = cells.shape[0] - first if count is None else int(count)
+        c, h, w = self.program.in_shape
+        out = torch.empty((max(count, 0), 3, h, w), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.xfr_strise_debug_masked_probes(self._h, probe_u8.data_ptr(), fill.data_ptr(), cp, sp, cells.shape[0], ctypes.byref(geom),
+                                                               int(first), count, out.data_ptr(), _stream_ptr(self.device)))
+        return out
+
     # ------------------------------------------------------------------------------------------------
     def set_trace(self, on):
         _lib.check(self.lib.xfr_engine_set_trace(self._h, 1 if on else 0))
