@@ -550,6 +550,15 @@ xfr_status xfr_engine_profile_csv(xfr_engine* e, const char* path);
  * launch ran there; tests/test_gpu_entry.py asserts interpreted == 0 for the benchmarked entry point on the BASELINE backbones. */
 xfr_status xfr_chain_epilogue_stats(int64_t* compiled_launches, int64_t* interpreted_launches, int32_t* n_signatures);
 
+/* Process-wide launch counts of the kernel variants that the pool, normalize, direct-stem and hook-chain launchers choose between by shape and
+ * pointer alignment (the scalar kernels, the float4 ones, the row-pair max-pools, the fused pool pair, the global average pool; the chain kernels
+ * by interpreter and by chain head).  Counted on the host where a kernel is enqueued: the planner and the dry run of the lean schedule count
+ * nothing.  xfr_elementwise_variant_name(i) names variant i, NULL beyond the last; `counts` receives min(capacity, n_variants) values in that
+ * order and `n_variants` (may be NULL) their number.  No device needed.  tests/test_gpu_layer_parity.py proves with them that each variant ran
+ * under a float64 comparison. */
+xfr_status xfr_elementwise_launch_stats(int64_t* counts, int32_t capacity, int32_t* n_variants);
+const char* xfr_elementwise_variant_name(int32_t i);
+
 /* The planner without a device: the fused forward-only and backward schedules of a layer program for one subtree mode and
  * seed tensor, as text (one launch per line; GEMM lines carry the signature of their fused chain and the index of its
  * compiled epilogue, -1 if it would be interpreted).  Makes no HIP call, so it also runs where no GPU is visible:

@@ -23,7 +23,7 @@ class _TapeBuilder(object):
         self.x = x
         self.calibrate = calibrate          # dict to receive BatchNorm running statistics (calibration pass), else None
         self.marks = {}
-        tape.pool_args = {}                 # max-pool output tensor -> (kernel, stride, pad), for pool_windows_clear
+        tape.pool_args = {}                 # max-pool output tensor -> (kernel, stride, pad, ceil_mode), for pool_windows_clear
 
     def conv(self, x, prefix, cout, k, stride=1, pad=0, bias=True):
         return self.t.conv(x, prefix, stride=stride, pad=pad)
@@ -43,7 +43,7 @@ class _TapeBuilder(object):
 
     def maxpool(self, x, k, stride, pad=0, ceil_mode=False):
         out = self.t.maxpool(x, k, stride, pad, ceil_mode)
-        self.t.pool_args[out] = (k, stride, pad)
+        self.t.pool_args[out] = (k, stride, pad, bool(ceil_mode))
         return out
 
     def avgpool(self, x, k, stride):
@@ -113,21 +113,6 @@ def _projection(p):
     return p.mark('classify', p.linear(t, 'fc', 5, (8, 7)))
 
 
-def _avg_shortcut(p):
-    """An STR-ResNet down-sampling block (AvgPool2d(2) + ConcatChannels shortcut, resnet.py:210-213) on an 18 x 14 map -> 9 x 7."""
-    t = p.conv(0, 'conv1', 64, 3, stride=1, pad=1, bias=False)
-    t = p.relu_(p.batchnorm(t, 'bn1'))
-    o = p.conv(t, 'b.conv1', 32, 1, stride=2, bias=False)
-    o = p.relu_(p.batchnorm(o, 'b.bn1'))
-    o = p.conv(o, 'b.conv2', 32, 3, stride=1, pad=1, bias=False)
-    o = p.relu_(p.batchnorm(o, 'b.bn2'))
-    o = p.conv(o, 'b.conv3', 128, 1, bias=False)
-    o = p.batchnorm(o, 'b.bn3')
-    r = p.concat_channels(p.avgpool(t, 2, 2), 1)
-    t = p.relu_(p.add(o, r))
-    return p.mark('classify', p.linear(t, 'fc', 5, (9, 7)))
-
-
 def _bf16x6(p):
     """3x3 128 -> 128 layers (K = 1152: covered by the bf16x6 kernel, staged as a patch) around a residual add at 15 x 17 (ragged M), then
     a 1x1 128 -> 256 -> 128 pair (K = 256 on the second: the shallowest 1x1 the bf16x6 kernel takes)."""
@@ -157,15 +142,6 @@ def _halo(w):
     return fwd
 
 
-def _mfm(p):
-    """Light-CNN's direct stem (5x5, one channel, pad 2) with MaxFeatureMap 16 -> 8 at 37 x 31, the pool pair max + avg (odd sizes floor to
-    18 x 15), a MaxFeatureMap 3x3 (co_pair rows), a Linear head."""
-    t = p.g_maxhalves(p.split(p.conv(0, 'conv1', 16, 5, stride=1, pad=2)))
-    t = p.g_add(p.maxpool(t, 2, 2), p.avgpool(t, 2, 2))
-    t = p.g_maxhalves(p.split(p.conv(t, 'conv2', 16, 3, stride=1, pad=1)))
-    return p.mark('classify', p.linear(t, 'fc', 5, (18, 15)))
-
-
 def _classifier(p):
     """A 512 x 4 x 5 map into a Linear 10240 -> 1037: very deep K over a few tiles (K-parts), ragged Cout, forward and backward."""
     t = p.conv(0, 'conv1', 512, 1, bias=False)
@@ -193,6 +169,79 @@ def _strided(p):
     t = p.conv(t, 'conv1', 48, 1, stride=3, bias=True)
     t = p.relu_(p.batchnorm(t, 'bn1'))
     return p.mark('classify', p.linear(t, 'fc', 5, (4, 3)))
+
+
+def _stem_pool(pad, ceil_mode, hw):
+    def fwd(p):
+        """The ResNet stems on a map with W = 2 OW, W %% 8 == 0 (the row-pair max-pool kernels): 7x7 s2 p3 on three channels, max-pool 3/2/%d%s
+        -> %d x %d, a 3x3 64 -> 40, a Linear head."""
+        t = p.conv(0, 'conv1', 64, 7, stride=2, pad=3, bias=False)
+        t = p.relu_(p.batchnorm(t, 'bn1'))
+        t = p.maxpool(t, 3, 2, pad, ceil_mode=ceil_mode)
+        t = p.conv(t, 'conv2', 40, 3, stride=1, pad=1, bias=False)
+        t = p.relu_(p.batchnorm(t, 'bn2'))
+        return p.mark('classify', p.linear(t, 'fc', 5, hw))
+    fwd.__doc__ = fwd.__doc__ % ((pad, ' ceil_mode' if ceil_mode else '') + tuple(hw))
+    return fwd
+
+
+def _pooled(pool, k, stride, hw):
+    def fwd(p):
+        """conv3x3 32, BN, ReLU, a %s-pool %d/%d without padding -> %d x %d, conv3x3 16, BN, ReLU, a Linear head."""
+        t = p.conv(0, 'conv1', 32, 3, stride=1, pad=1, bias=False)
+        t = p.relu_(p.batchnorm(t, 'bn1'))
+        t = p.maxpool(t, k, stride) if pool == 'max' else p.avgpool(t, k, stride)
+        t = p.conv(t, 'conv2', 16, 3, stride=1, pad=1, bias=False)
+        t = p.relu_(p.batchnorm(t, 'bn2'))
+        return p.mark('classify', p.linear(t, 'fc', 5, hw))
+    fwd.__doc__ = fwd.__doc__ % ((pool, k, stride) + tuple(hw))
+    return fwd
+
+
+def _mfm(hw):
+    def fwd(p):
+        """Light-CNN's direct stem (5x5, one channel, pad 2) with MaxFeatureMap 16 -> 8, the pool pair max + avg (odd sizes floor) -> %d x %d,
+        a MaxFeatureMap 3x3 (co_pair rows), a Linear head."""
+        t = p.g_maxhalves(p.split(p.conv(0, 'conv1', 16, 5, stride=1, pad=2)))
+        t = p.g_add(p.maxpool(t, 2, 2), p.avgpool(t, 2, 2))
+        t = p.g_maxhalves(p.split(p.conv(t, 'conv2', 16, 3, stride=1, pad=1)))
+        return p.mark('classify', p.linear(t, 'fc', 5, hw))
+    fwd.__doc__ = fwd.__doc__ % tuple(hw)
+    return fwd
+
+
+def _avg_shortcut(hw):
+    def fwd(p):
+        """An STR-ResNet down-sampling block (AvgPool2d(2) + ConcatChannels shortcut, resnet.py:210-213) -> %d x %d."""
+        t = p.conv(0, 'conv1', 64, 3, stride=1, pad=1, bias=False)
+        t = p.relu_(p.batchnorm(t, 'bn1'))
+        o = p.conv(t, 'b.conv1', 32, 1, stride=2, bias=False)
+        o = p.relu_(p.batchnorm(o, 'b.bn1'))
+        o = p.conv(o, 'b.conv2', 32, 3, stride=1, pad=1, bias=False)
+        o = p.relu_(p.batchnorm(o, 'b.bn2'))
+        o = p.conv(o, 'b.conv3', 128, 1, bias=False)
+        o = p.batchnorm(o, 'b.bn3')
+        r = p.concat_channels(p.avgpool(t, 2, 2), 1)
+        t = p.relu_(p.add(o, r))
+        return p.mark('classify', p.linear(t, 'fc', 5, hw))
+    fwd.__doc__ = fwd.__doc__ % tuple(hw)
+    return fwd
+
+
+def _global_tail(cout, k, normalize, relu=True):
+    def fwd(p):
+        """conv3x3 %d, BN%s, a global average pool %d x %d%s, a Linear head on the 1 x 1 map."""
+        t = p.conv(0, 'conv1', cout, 3, stride=1, pad=1, bias=False)
+        t = p.batchnorm(t, 'bn1')
+        if relu:
+            t = p.relu_(t)
+        t = p.avgpool(t, k, k)
+        if normalize:
+            t = p.multiply(p.g_normalize(t), 50.0)
+        return p.mark('classify', p.linear(t, 'fc', 5, (1, 1)))
+    fwd.__doc__ = fwd.__doc__ % (cout, ', ReLU' if relu else ' (no ReLU: the pooled map is signed)', k, k,
+                                 ', the STR-ResNet encode tail F.normalize and Multiply(50)' if normalize else '')
+    return fwd
 
 
 class NetCase(object):
@@ -269,16 +318,68 @@ class NetCase(object):
 CASES = [
     NetCase('stem', (3, 37, 29), _stem, 'tap4 stem, P[-1] gather at odd sizes, ragged Cout, max-pool edges', 1),
     NetCase('projection', (64, 15, 13), _projection, 'stride-2 scatter onto an odd map, projection side branch (fusion bit 7)', 2),
-    NetCase('avg_shortcut', (64, 18, 14), _avg_shortcut, 'compact as_strided + EW_AVGUP_IN (fusion bit 6)', 3),
+    NetCase('avg_shortcut', (64, 18, 14), _avg_shortcut((9, 7)), 'compact as_strided + EW_AVGUP_IN (fusion bit 6)', 3),
     NetCase('bf16x6', (128, 15, 17), _bf16x6, 'patch staging, ragged M, forward and backward bf16x6', 4),
     NetCase('halo64', (128, 9, 63), _halo(63), 'halo 64: the bf16x6 patch', 5),
     NetCase('halo65', (128, 9, 64), _halo(64), 'halo 65: the bf16x6 slab', 6),
-    NetCase('mfm', (1, 37, 31), _mfm, 'direct stem, co_pair rows, EW_POOL2_IN', 7),
+    NetCase('mfm', (1, 37, 31), _mfm((18, 15)), 'co_pair rows and EW_MAXHALF_IN at odd sizes (W % 4 != 0: no direct stem, no pool-pair fusion): the scalar pools and their separate VJPs', 7),
     NetCase('classifier', (512, 4, 5), _classifier, 'deep-K K-parts over few tiles, ragged Cout', 8),
     NetCase('valid_wide', (24, 11, 11), _valid_wide, 'Cin % 16 != 0 (ci-major K), backward padding k - 1 - p = 0', 9),
     NetCase('strided', (32, 10, 7), _strided, 'stride-3 1x1 scatter, M % 4 != 0', 10),
+    # the float4 / row-pair / fused forms of the pooling and tail kernels (xfr_amd/csrc/elementwise.hip), at the smallest shapes that reach them
+    NetCase('stem_rows', (3, 25, 32), _stem_pool(1, False, (7, 8)), 'maxpool_fwd_rows<3,1> (left column in and out, last window row clipped), maxpool_bwd_v4<3,2>', 11),
+    NetCase('ceil_rows', (3, 23, 32), _stem_pool(0, True, (6, 8)), 'maxpool_fwd_rows<3,0> under ceil_mode (right column in and out, bottom row out of range)', 20),      # (seed 12 leaves near-tie windows: pool_windows_clear)
+    NetCase('pool_generic', (16, 12, 12), _pooled('max', 3, 3, (4, 4)), 'maxpool_fwd_v4<0,0>, maxpool_bwd_v4<0,0>', 13),
+    NetCase('pool_odd17', (8, 10, 17), _pooled('max', 2, 2, (5, 8)), 'maxpool_fwd_v4<2,2> without the row-pair form (W = 2 OW + 1), scalar VJP', 14),
+    NetCase('mfm_pool2', (1, 20, 24), _mfm((10, 12)), 'stem5_mfm, pool2_fwd, float4 EW_POOL2_IN; un-fused: rows<2,0> and the 2/2 float4 pools and VJPs', 15),
+    NetCase('avg_shortcut_v4', (64, 16, 24), _avg_shortcut((8, 12)), 'avgpool_fwd_v4<2,2> with zero planes, float4 EW_AVGUP_IN; un-fused: avgpool_bwd_v4<2,2>', 16),
+    NetCase('encode_tail', (32, 5, 5), _global_tail(80, 5, True), 'global average pool (partial last block of 128 planes) and its VJP, normalize forward / VJP, Multiply', 17),
+    NetCase('global_big', (16, 12, 12), _global_tail(48, 12, False), 'a global pool whose 128 planes outgrow 64 KB of LDS: generic forward, global VJP', 18),
+    NetCase('avg_generic', (16, 12, 12), _pooled('avg', 3, 3, (4, 4)), 'avgpool_fwd_v4<0,0>, avgpool_bwd_v4<0,0>', 19),
+    NetCase('signed_tail', (32, 5, 5), _global_tail(80, 5, False, relu=False), 'the global average pool of a signed map: its positive pass clamps the input (relu_in = 1), partial last block of 128 planes', 21),
 ]
 BY_NAME = {c.name: c for c in CASES}
+
+# The kernel variants each net must launch, keyed by where.  The names are those of xfr_elementwise_variant_name.
+# 'firing' means during test_gpu_layer_parity.test_every_firing_matches_float64, whose observing sweeps run with the default fusion.
+# A schedule tag means during that entry of the schedule matrix.
+# 'all' stands for 'firing', 'fusion0' and 'fusion_separate'.  It does not apply under the 'default' tag: see required_variants.
+# A variant that the default schedule must launch as well is therefore named under 'default' again, as in avg_shortcut_v4.
+# No counter separates relu_in = 1 from relu_in = 0 launches.  That signed_tail takes the clamped path of the global pool is proven by its
+# values: the float64 comparison fails without the clamp.
+_UNFUSED_PAIR = ['maxpool_fwd_rows<2,0>', 'avgpool_fwd_v4<2,2>', 'maxpool_bwd_v4<2,2>', 'avgpool_bwd_v4<2,2>']
+REQUIRED_VARIANTS = {
+    'stem': {'firing': ['maxpool_fwd_v4<3,2>', 'maxpool_bwd']},
+    'mfm': {'firing': ['maxpool_fwd', 'avgpool_fwd', 'maxpool_bwd', 'avgpool_bwd']},
+    'avg_shortcut': {'firing': ['avgpool_fwd']},
+    'stem_rows': {'all': ['maxpool_fwd_rows<3,1>', 'maxpool_bwd_v4<3,2>']},
+    'ceil_rows': {'all': ['maxpool_fwd_rows<3,0>', 'maxpool_bwd_v4<3,2>']},
+    'pool_generic': {'all': ['maxpool_fwd_v4<0,0>', 'maxpool_bwd_v4<0,0>']},
+    'pool_odd17': {'all': ['maxpool_fwd_v4<2,2>', 'maxpool_bwd']},
+    'mfm_pool2': {'firing': ['stem5_mfm', 'pool2_fwd', 'ew_chain_v4/pool2_in'], 'default': ['stem5_mfm', 'pool2_fwd', 'ew_chain_v4/pool2_in'],
+                  'fusion0': _UNFUSED_PAIR, 'fusion_separate': _UNFUSED_PAIR},
+    'avg_shortcut_v4': {'all': ['avgpool_fwd_v4<2,2>'], 'default': ['avgpool_fwd_v4<2,2>', 'ew_chain_v4/avgup_in'],
+                        'fusion0': ['avgpool_bwd_v4<2,2>'], 'fusion_separate': ['avgpool_bwd_v4<2,2>']},
+    'encode_tail': {'all': ['avgpool_global_fwd', 'avgpool_global_bwd', 'normalize_fwd', 'normalize_bwd']},
+    'global_big': {'all': ['avgpool_fwd', 'avgpool_global_bwd']},
+    'avg_generic': {'all': ['avgpool_fwd_v4<0,0>', 'avgpool_bwd_v4<0,0>']},
+    'signed_tail': {'all': ['avgpool_global_fwd', 'avgpool_global_bwd']},
+}
+
+
+def required_variants(name, where):
+    """Sorted names of the variants net `name` must launch during `where`."""
+    r = REQUIRED_VARIANTS.get(name, {})
+    return sorted(set(r.get(where, [])) | set(r.get('all', []) if where in ('firing', 'fusion0', 'fusion_separate') else []))
+
+
+def pool_window_columns(v, k, s, p, out_hw):
+    """The max-pool windows of v (N x C x H x W) as columns, N x C x (k k) x (OH OW), padding as -inf.  out_hw is the pool's output size: under
+    ceil_mode the window grid reaches past the right / bottom edge, and what lies there is padding like the rest."""
+    eb = max((out_hw[0] - 1) * s + k - (v.shape[2] + 2 * p), 0)
+    er = max((out_hw[1] - 1) * s + k - (v.shape[3] + 2 * p), 0)
+    cols = F.unfold(F.pad(v, (p, p + er, p, p + eb), value=float('-inf')), k, stride=s)        # N x (C k k) x L
+    return cols.view(v.shape[0], v.shape[1], k * k, -1)
 
 
 def pool_windows_clear(tape64, rel_gap=1e-6):
@@ -290,9 +391,8 @@ def pool_windows_clear(tape64, rel_gap=1e-6):
         v = tape64.T[c.ins[0]]
         scale = float(v.abs().max())
         if c.name == 'MaxPool2d':
-            k, s, p = tape64.pool_args[c.out]
-            cols = F.unfold(F.pad(v, (p, p, p, p), value=float('-inf')), k, stride=s)        # N x (C k k) x L
-            cols = cols.view(v.shape[0], v.shape[1], k * k, -1)
+            k, s, p, _ = tape64.pool_args[c.out]            # ceil_mode shows in the output's shape, which sets the window grid
+            cols = pool_window_columns(v, k, s, p, tape64.T[c.out].shape[2:])
             top2 = cols.topk(2, dim=2).values
             gap = top2[:, :, 0] - top2[:, :, 1]
             assert gap.numel() == tape64.T[c.out].numel()

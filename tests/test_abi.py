@@ -29,6 +29,23 @@ def test_library_exports_every_declared_symbol():
     assert lib.xfr_abi_version() == _lib.ABI_VERSION
 
 
+def test_elementwise_launch_stats_need_no_device():
+    """xfr_elementwise_launch_stats / xfr_elementwise_variant_name: a name per counter, NULL beyond the last, short and missing buffers."""
+    lib = _lib.load()
+    n = ctypes.c_int32(-1)
+    assert lib.xfr_elementwise_launch_stats(None, 0, ctypes.byref(n)) == _lib.XFR_OK and n.value > 0
+    names = _lib.elementwise_variant_names()
+    assert len(names) == n.value == len(set(names))
+    assert lib.xfr_elementwise_variant_name(n.value) is None and lib.xfr_elementwise_variant_name(-1) is None
+    two = (ctypes.c_int64 * 3)(-7, -7, -7)
+    assert lib.xfr_elementwise_launch_stats(two, 2, None) == _lib.XFR_OK
+    assert two[0] >= 0 and two[1] >= 0 and two[2] == -7
+    assert lib.xfr_elementwise_launch_stats(None, 2, None) == _lib.XFR_INVALID_ARG
+    assert lib.xfr_elementwise_launch_stats(two, -1, None) == _lib.XFR_INVALID_ARG
+    stats = _lib.elementwise_launch_stats()
+    assert sorted(stats) == sorted(names) and all(v >= 0 for v in stats.values())
+
+
 def test_opdesc_layout():
     assert ctypes.sizeof(OpDesc) == 16 * 4
     assert OpDesc.fparam.offset == 11 * 4 and OpDesc.w_var.offset == 15 * 4

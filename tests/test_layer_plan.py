@@ -60,6 +60,17 @@ EXPECT = {
                     r'^bwd CONV_BWD src 7 dst 4 acc 0 \[32 x 7 x 7\] K 144 SIG',             # 3x3 pad 2: backward padding 0
                     r'^bwd CONV_BWD src 4 dst 1 acc 0 \[24 x 11 x 11\] K 800 SIG'], 1),       # 'valid' 5x5: backward padding 4; Cin 24: no lean form
     'strided': ([r'^bwd ZERO src -1 dst 3 .* \[32 x 10 x 7\]$', r'^bwd CONV_BWD src 4 dst 3 acc 1 \[32 x 10 x 7\] K 48$'], 1),
+    'stem_rows': ([r'^bwd MAXPOOL_BWD .* \[64 x 13 x 16\]$'], 1),
+    'ceil_rows': ([r'^bwd MAXPOOL_BWD .* \[64 x 12 x 16\]$'], 1),
+    'pool_generic': ([r'^bwd MAXPOOL_BWD .* \[32 x 12 x 12\]$'], 1),
+    'pool_odd17': ([r'^bwd MAXPOOL_BWD .* \[32 x 10 x 17\]$'], 1),
+    'mfm_pool2': ([r'^bwd EW src 6 dst 1 acc 0 \[8 x 20 x 24\] steps 5$'], 0),                  # the EW_POOL2_IN head: no separate pool VJPs (below)
+    'avg_shortcut_v4': ([r'^bwd EW src 13 dst 1 acc 0 \[64 x 16 x 24\] steps 7$'], 3),
+    'encode_tail': ([r'^bwd NORMALIZE_BWD src 5 dst 4 acc 0 \[80 x 1 x 1\]$', r'^bwd AVGPOOL_BWD src 4 dst 3 acc 0 \[80 x 5 x 5\]$'], 0),
+    'global_big': ([r'^bwd AVGPOOL_BWD src 4 dst 3 acc 0 \[48 x 12 x 12\]$'], 0),
+    'avg_generic': ([r'^bwd AVGPOOL_BWD .* \[32 x 12 x 12\]$'], 1),
+    'signed_tail': ([r'^bwd CONV_BWD src 4 dst 3 acc 0 \[80 x 1 x 1\] K 5 SIG',                 # the Linear head divides by the pool's positive value
+                     r'^bwd AVGPOOL_BWD src 3 dst 2 acc 0 \[80 x 5 x 5\]$'], 0),
 }
 
 
@@ -90,7 +101,7 @@ def test_plan_routes_the_net_to_its_launch_form(name):
         kinds = [OpKind(prog.ops[k].kind) for k in ops]
         want = [{'Conv2d': OpKind.CONV, 'BatchNorm2d': OpKind.BATCHNORM, 'ReLU': OpKind.RELU, 'MaxPool2d': OpKind.MAXPOOL,
                  'AvgPool2d': OpKind.AVGPOOL, 'Add': OpKind.ADD, 'ConcatChannels': OpKind.CONCAT, 'Linear': OpKind.LINEAR,
-                 'Split': OpKind.SPLIT}[n] for n in names[:-1]]
+                 'Split': OpKind.SPLIT, 'Multiply': OpKind.MULTIPLY}[n] for n in names[:-1]]
         assert kinds == want, (name, mode)
 
 
@@ -104,6 +115,44 @@ def test_fusion_switches_change_the_launch_forms():
     n_default = len(_bwd(_describe(proj)))
     assert len(_bwd(_describe(proj, fusion=131))) > n_default                 # bit 7 off: the main path's chain as its own launch
     assert len(_bwd(_describe(proj, fusion=0))) > n_default                   # everything un-fused
+    # the pool pair: one chain launch with the EW_POOL2_IN head by default, its two VJPs at fusion 0 -- and always at odd sizes (`mfm`)
+    pool_vjps = lambda text: sorted(k for k in (ln.split()[1] for ln in _bwd(text)) if k in ('AVGPOOL_BWD', 'MAXPOOL_BWD'))
+    pair = L.BY_NAME['mfm_pool2']
+    assert pool_vjps(_describe(pair)) == []
+    assert pool_vjps(_describe(pair, fusion=0)) == ['AVGPOOL_BWD', 'MAXPOOL_BWD']
+    assert pool_vjps(_describe(L.BY_NAME['mfm'])) == ['AVGPOOL_BWD', 'MAXPOOL_BWD']
+    # a global pool keeps its VJP launch under both settings
+    for fusion in (None, 0):
+        assert _has(_bwd(_describe(L.BY_NAME['global_big'], fusion=fusion)), r'^bwd AVGPOOL_BWD src 4 dst 3 acc 0 \[48 x 12 x 12\]$')
+
+
+def test_required_variants_cover_every_pool_normalize_and_stem_kernel():
+    """layer_nets.REQUIRED_VARIANTS (what tests/test_gpu_layer_parity.py proves with the launch counters) names every pooling, normalize and direct-stem
+    variant the library can launch, and nothing it cannot: a variant added later cannot go without a float64 comparison silently."""
+    from xfr_amd import _lib
+    names = _lib.elementwise_variant_names()
+    assert len(names) == len(set(names)) and _lib.load().xfr_elementwise_variant_name(len(names)) is None
+    required = set(v for by_where in L.REQUIRED_VARIANTS.values() for vs in by_where.values() for v in vs)
+    assert required <= set(names), required - set(names)
+    assert set(L.REQUIRED_VARIANTS) <= set(L.BY_NAME)
+    kernels = set(n for n in names if not n.startswith('ew_chain'))
+    assert set(v for v in required if not v.startswith('ew_chain')) == kernels, kernels - required
+    assert set(v for v in required if v.startswith('ew_chain')) == {'ew_chain_v4/pool2_in', 'ew_chain_v4/avgup_in'}
+
+
+def test_signed_tail_pools_a_signed_map():
+    """`signed_tail` exists for the clamp in the positive pass of the global average pool (the engine sets relu_in where the pooled map is not provably
+    >= 0): its pooled map has values of both signs in every image, so avg(relu(x)) -- the x the Linear head divides by -- is far from avg(x)."""
+    case = L.BY_NAME['signed_tail']
+    tape64, _ = case.tape(case.inputs(3), torch.float64)
+    pool = [c for c in tape64.calls if c.name == 'AvgPool2d']
+    assert len(pool) == 1 and not any(c.name == 'ReLU' for c in tape64.calls)
+    v = tape64.T[pool[0].ins[0]]
+    assert tuple(v.shape[1:]) == (80, 5, 5)
+    neg = (v < 0).double().mean(dim=(1, 2, 3))
+    assert float(neg.min()) > 0.25 and float(neg.max()) < 0.75, neg
+    clamped, plain = torch.relu(v).mean(dim=(2, 3)), v.mean(dim=(2, 3))
+    assert float((clamped - plain).abs().max()) > 0.1 * float(clamped.abs().max())
 
 
 @pytest.mark.parametrize('name', sorted(L.BY_NAME))

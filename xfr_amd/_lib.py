@@ -105,6 +105,8 @@ SYMBOLS = [
     ('xfr_engine_get_profile_by_kernel', _I, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]),
     ('xfr_engine_profile_csv', _I, [_P, ctypes.c_char_p]),
     ('xfr_chain_epilogue_stats', _I, [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_I)]),
+    ('xfr_elementwise_launch_stats', _I, [ctypes.POINTER(ctypes.c_int64), _I, ctypes.POINTER(_I)]),
+    ('xfr_elementwise_variant_name', ctypes.c_char_p, [_I]),
     ('xfr_plan_describe', _I, [ctypes.POINTER(OpDesc), _I, _I, _I, _I, _I, _I, _I, _I, ctypes.c_char_p, ctypes.c_size_t,
                                ctypes.POINTER(ctypes.c_size_t)]),
 ]
@@ -146,3 +148,22 @@ def check(status):
     if status == XFR_OOM:
         raise MemoryError(msg)
     raise XfrError(status, msg)
+
+
+def elementwise_variant_names():
+    """Names of the kernel variants xfr_elementwise_launch_stats counts, in its order (no device needed)."""
+    lib = load()
+    names = []
+    while True:
+        name = lib.xfr_elementwise_variant_name(len(names))
+        if name is None:
+            return names
+        names.append(name.decode())
+
+
+def elementwise_launch_stats():
+    """{variant name: launches so far in this process}."""
+    names = elementwise_variant_names()
+    counts = (ctypes.c_int64 * len(names))()
+    check(load().xfr_elementwise_launch_stats(counts, len(names), None))
+    return dict(zip(names, counts))

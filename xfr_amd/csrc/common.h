@@ -236,6 +236,10 @@ inline int ew_chain_codes(const EwChain& ch, uint16_t codes[XFR_MAX_EW_STEPS])
 int conv_gemm_chain_sig(const EwChain& planned_chain);
 int conv_gemm_num_chain_sigs();
 void conv_gemm_chain_launch_counts(long* compiled, long* interpreted);
+// elementwise.hip: launches per kernel variant of the pools, the normalize pair, the direct stem and the hook-chain kernels (process-wide)
+int elementwise_num_variants();
+const char* elementwise_variant_name(int i);
+long elementwise_variant_launches(int i);
 
 // ---- implicit-GEMM convolution -------------------------------------------------------------------------------
 struct ConvParams {

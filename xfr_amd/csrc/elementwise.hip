@@ -8,6 +8,7 @@
 // read and written once between two GEMMs.
 #include "common.h"
 #include "ew_interp.h"
+#include <atomic>
 #include <cstring>
 
 namespace {
@@ -21,6 +22,32 @@ inline int grid_for(long n, int per_thread = 1)
     if (b > 256L * 32) b = 256L * 32;   // 32 workgroups per CU, grid-stride beyond
     return (int)b;
 }
+
+// Host-side launch counters, one per kernel variant the launchers below choose between by shape and pointer alignment
+// (xfr_elementwise_launch_stats): process-global like g_conv_chain_launches, bumped where the kernel is enqueued, so a
+// dry run of the forward -- which launches nothing -- counts nothing.  The order is the ABI's (xfr_elementwise_variant_name).
+enum EwVariant {
+    V_MAXPOOL_FWD, V_MAXPOOL_FWD_V4_32, V_MAXPOOL_FWD_V4_22, V_MAXPOOL_FWD_V4_00, V_MAXPOOL_FWD_ROWS_31, V_MAXPOOL_FWD_ROWS_30, V_MAXPOOL_FWD_ROWS_20,
+    V_POOL2_FWD,
+    V_MAXPOOL_BWD, V_MAXPOOL_BWD_V4_32, V_MAXPOOL_BWD_V4_22, V_MAXPOOL_BWD_V4_00,
+    V_AVGPOOL_FWD, V_AVGPOOL_FWD_V4_22, V_AVGPOOL_FWD_V4_00, V_AVGPOOL_FWD_GLOBAL,
+    V_AVGPOOL_BWD, V_AVGPOOL_BWD_V4_22, V_AVGPOOL_BWD_V4_00, V_AVGPOOL_BWD_GLOBAL,
+    V_NORMALIZE_FWD, V_NORMALIZE_BWD, V_STEM5_MFM,
+    V_EW_CHAIN,                         // + 4 * (float4 interpreter) + head: 0 none, 1 EW_MAXHALF_IN, 2 EW_POOL2_IN, 3 EW_AVGUP_IN
+    V_COUNT = V_EW_CHAIN + 8
+};
+const char* const kVariantNames[V_COUNT] = {
+    "maxpool_fwd", "maxpool_fwd_v4<3,2>", "maxpool_fwd_v4<2,2>", "maxpool_fwd_v4<0,0>", "maxpool_fwd_rows<3,1>", "maxpool_fwd_rows<3,0>", "maxpool_fwd_rows<2,0>",
+    "pool2_fwd",
+    "maxpool_bwd", "maxpool_bwd_v4<3,2>", "maxpool_bwd_v4<2,2>", "maxpool_bwd_v4<0,0>",
+    "avgpool_fwd", "avgpool_fwd_v4<2,2>", "avgpool_fwd_v4<0,0>", "avgpool_global_fwd",
+    "avgpool_bwd", "avgpool_bwd_v4<2,2>", "avgpool_bwd_v4<0,0>", "avgpool_global_bwd",
+    "normalize_fwd", "normalize_bwd", "stem5_mfm",
+    "ew_chain", "ew_chain/maxhalf_in", "ew_chain/pool2_in", "ew_chain/avgup_in",
+    "ew_chain_v4", "ew_chain_v4/maxhalf_in", "ew_chain_v4/pool2_in", "ew_chain_v4/avgup_in",
+};
+std::atomic<long> g_variant_launches[V_COUNT];
+inline void count(int v) { g_variant_launches[v].fetch_add(1, std::memory_order_relaxed); }
 
 // ---------------------------------------------------------------------------------------------------------
 // The tensor hooks of whitebox.py:381-430 (+ ReLU / BatchNorm / Multiply VJPs), fused.
@@ -987,6 +1014,10 @@ constexpr int STAT_CHUNKS = 16;
 
 }  // namespace
 
+int elementwise_num_variants() { return V_COUNT; }
+const char* elementwise_variant_name(int i) { return i >= 0 && i < V_COUNT ? kVariantNames[i] : nullptr; }
+long elementwise_variant_launches(int i) { return i >= 0 && i < V_COUNT ? g_variant_launches[i].load(std::memory_order_relaxed) : 0; }
+
 size_t subtree_stats_scratch_bytes(int N, int n_tensors) { return sizeof(StatPartial) * (size_t)N * STAT_CHUNKS * (size_t)n_tensors; }
 
 void launch_subtree_stats(const StatDesc* desc_dev, int n_tensors, const int* f2u_dev, int n_firings, float* vmax, int* vidx,
@@ -1010,6 +1041,7 @@ void launch_ew_chain(const float* src, float* dst, int accumulate, const EwChain
         if (chain.s[i].prior_elem || chain.s[i].prior_dense || chain.s[i].cap_dst) prior = true;
     }
     const long total = (long)C * SB * HW;
+    const int head = chain.n == 0 ? 0 : (chain.s[0].type == EW_MAXHALF_IN ? 1 : (chain.s[0].type == EW_POOL2_IN ? 2 : (chain.s[0].type == EW_AVGUP_IN ? 3 : 0)));
     for (int i = 0; i < chain.n; ++i)
         if (accumulate && chain.s[i].pstore == dst) special = true;   // the float4 kernel reads dst before the chain runs
     // (a chain with a fan-out -- EW_MAXHALF_OUT behind a pool-pair head -- only exists in the float4 interpreter; the planner creates it
@@ -1024,6 +1056,7 @@ void launch_ew_chain(const float* src, float* dst, int accumulate, const EwChain
         const int S = SB / B, Sa = (SBa + B - 1) / B;                    // streams, streams with live samples
         const long per_ca4 = (long)B * HW / 4;
         const unsigned gx = (unsigned)((per_ca4 + NT - 1) / NT);
+        count(V_EW_CHAIN + 4 + head);
         auto go = [&](auto kern, int sg) {
             hipLaunchKernelGGL(kern, dim3(gx, C, (unsigned)((Sa + sg - 1) / sg)), dim3(NT), 0, s, reinterpret_cast<const float4*>(src),
                                reinterpret_cast<float4*>(dst), accumulate, planned, ld, C, SB, B, HW / 4, eps, SBa, (int)per_ca4);
@@ -1031,9 +1064,11 @@ void launch_ew_chain(const float* src, float* dst, int accumulate, const EwChain
         if (S == 1) { if (prior) go(ew_chain_kernel_v4<true, 1>, 1); else go(ew_chain_kernel_v4<false, 1>, 1); }
         else { if (prior) go(ew_chain_kernel_v4<true, 2>, 2); else go(ew_chain_kernel_v4<false, 2>, 2); }
     } else if (trace) {
+        count(V_EW_CHAIN + head);
         hipLaunchKernelGGL(ew_chain_kernel<true>, dim3(grid_for(total)), dim3(NT), 0, s, src, dst, accumulate, chain, C, SB,
                            B, HW, eps);
     } else {
+        count(V_EW_CHAIN + head);
         hipLaunchKernelGGL(ew_chain_kernel<false>, dim3(grid_for(total)), dim3(NT), 0, s, src, dst, accumulate, chain, C, SB,
                            B, HW, eps);
     }
@@ -1099,6 +1134,8 @@ void launch_maxpool_fwd(const float* in, float* out, uint8_t* idx, int CN, int H
         float4* out4 = reinterpret_cast<float4*>(out);
         uint32_t* idx4 = reinterpret_cast<uint32_t*>(idx);
         const bool rows = stride == 2 && W == 2 * OW && (W & 7) == 0 && (((uintptr_t)in) & 15) == 0 && ((k == 3 && pad <= 1) || (k == 2 && pad == 0));
+        count(rows ? (k == 3 ? (pad == 1 ? V_MAXPOOL_FWD_ROWS_31 : V_MAXPOOL_FWD_ROWS_30) : V_MAXPOOL_FWD_ROWS_20)
+                   : (stride == 2 && k == 3 ? V_MAXPOOL_FWD_V4_32 : (stride == 2 && k == 2 ? V_MAXPOOL_FWD_V4_22 : V_MAXPOOL_FWD_V4_00)));
         if (rows && k == 3 && pad == 1) hipLaunchKernelGGL((maxpool_fwd_kernel_rows<3, 1>), g, dim3(NT), 0, s, in, out4, idx4, H, W, OH, OW);
         else if (rows && k == 3) hipLaunchKernelGGL((maxpool_fwd_kernel_rows<3, 0>), g, dim3(NT), 0, s, in, out4, idx4, H, W, OH, OW);
         else if (rows) hipLaunchKernelGGL((maxpool_fwd_kernel_rows<2, 0>), g, dim3(NT), 0, s, in, out4, idx4, H, W, OH, OW);
@@ -1107,6 +1144,7 @@ void launch_maxpool_fwd(const float* in, float* out, uint8_t* idx, int CN, int H
         else hipLaunchKernelGGL((maxpool_fwd_kernel_v4<0, 0>), g, dim3(NT), 0, s, in, out4, idx4, H, W, OH, OW, k, stride, pad);
         return;
     }
+    count(V_MAXPOOL_FWD);
     hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for((long)CN * OH * OW)), dim3(NT), 0, s, in, out, idx, CN, H, W, OH, OW,
                        k, stride, pad);
 }
@@ -1227,12 +1265,14 @@ bool stem5_mfm_ok(const float* in, int NB, int H, int W)
 }
 void launch_stem5_mfm(const float* in, const float* wp, int ldw, const float* bias, float* raw, float* omax, int Co, int NB, int H, int W, hipStream_t s)
 {
+    count(V_STEM5_MFM);
     hipLaunchKernelGGL(stem5_mfm_kernel, dim3((H * (W / 4) + NT - 1) / NT, NB), dim3(NT), 0, s, in, wp, ldw, bias, raw, omax, Co, NB, H, W);
 }
 void launch_pool2_fwd(const float* in, float* out_sum, uint8_t* idx, float* out_pos, int CN, int H, int W, int OH, int OW, int relu_max_pos,
                       int pos_avg_mode, hipStream_t s)
 {
     const dim3 g((OH * (OW / 4) + NT - 1) / NT, CN);
+    count(V_POOL2_FWD);
     hipLaunchKernelGGL(pool2_fwd_kernel, g, dim3(NT), 0, s, in, reinterpret_cast<float4*>(out_sum), reinterpret_cast<uint32_t*>(idx),
                        reinterpret_cast<float4*>(out_pos), H, W, OH, OW, relu_max_pos, pos_avg_mode);
 }
@@ -1242,11 +1282,13 @@ void launch_maxpool_bwd(const float* gout, const uint8_t* idx, float* gin, int a
     if ((W & 3) == 0 && (long)C * SB <= 65535) {
         const dim3 g((H * (W / 4) + NT - 1) / NT, C * SB);
         float4* gin4 = reinterpret_cast<float4*>(gin);
+        count(stride == 2 && k == 3 ? V_MAXPOOL_BWD_V4_32 : (stride == 2 && k == 2 ? V_MAXPOOL_BWD_V4_22 : V_MAXPOOL_BWD_V4_00));
         if (k == 3 && stride == 2) hipLaunchKernelGGL((maxpool_bwd_kernel_v4<3, 2>), g, dim3(NT), 0, s, gout, idx, gin4, accumulate, SB, B, H, W, OH, OW, k, stride, pad);
         else if (k == 2 && stride == 2) hipLaunchKernelGGL((maxpool_bwd_kernel_v4<2, 2>), g, dim3(NT), 0, s, gout, idx, gin4, accumulate, SB, B, H, W, OH, OW, k, stride, pad);
         else hipLaunchKernelGGL((maxpool_bwd_kernel_v4<0, 0>), g, dim3(NT), 0, s, gout, idx, gin4, accumulate, SB, B, H, W, OH, OW, k, stride, pad);
         return;
     }
+    count(V_MAXPOOL_BWD);
     hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for((long)C * SB * H * W)), dim3(NT), 0, s, gout, idx, gin, accumulate,
                        C, SB, B, H, W, OH, OW, k, stride, pad);
 }
@@ -1254,16 +1296,19 @@ void launch_avgpool_fwd(const float* in, float* out, int CN, int H, int W, int O
                         hipStream_t s, int zero_planes)
 {
     if (zero_planes == 0 && OH == 1 && OW == 1 && k == H && k == W && (size_t)GP * H * W * sizeof(float) <= 64 * 1024) {
+        count(V_AVGPOOL_FWD_GLOBAL);
         hipLaunchKernelGGL(avgpool_global_fwd_kernel, dim3((CN + GP - 1) / GP), dim3(NT), (size_t)GP * H * W * sizeof(float), s, in, out, CN, H * W, relu_in);
         return;
     }
     if ((OW & 3) == 0 && CN + zero_planes <= 65535) {
         const dim3 g((OH * (OW / 4) + NT - 1) / NT, CN + zero_planes);
         float4* out4 = reinterpret_cast<float4*>(out);
+        count(k == 2 && stride == 2 ? V_AVGPOOL_FWD_V4_22 : V_AVGPOOL_FWD_V4_00);
         if (k == 2 && stride == 2) hipLaunchKernelGGL((avgpool_fwd_kernel_v4<2, 2>), g, dim3(NT), 0, s, in, out4, H, W, OH, OW, k, stride, relu_in, CN);
         else hipLaunchKernelGGL((avgpool_fwd_kernel_v4<0, 0>), g, dim3(NT), 0, s, in, out4, H, W, OH, OW, k, stride, relu_in, CN);
         return;
     }
+    count(V_AVGPOOL_FWD);
     hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(grid_for((long)(CN + zero_planes) * OH * OW)), dim3(NT), 0, s, in, out, CN, H, W, OH, OW, k,
                        stride, relu_in, zero_planes);
 }
@@ -1272,16 +1317,19 @@ void launch_avgpool_bwd(const float* gout, float* gin, int accumulate, int CN, i
 {
     if (OH == 1 && OW == 1 && k == H && k == W) {
         const long total = (long)CN * H * W;
+        count(V_AVGPOOL_BWD_GLOBAL);
         hipLaunchKernelGGL(avgpool_global_bwd_kernel, dim3(grid_for(total)), dim3(NT), 0, s, gout, gin, accumulate, total, H * W);
         return;
     }
     if ((W & 3) == 0 && CN <= 65535) {
         const dim3 g((H * (W / 4) + NT - 1) / NT, CN);
         float4* gin4 = reinterpret_cast<float4*>(gin);
+        count(k == 2 && stride == 2 ? V_AVGPOOL_BWD_V4_22 : V_AVGPOOL_BWD_V4_00);
         if (k == 2 && stride == 2) hipLaunchKernelGGL((avgpool_bwd_kernel_v4<2, 2>), g, dim3(NT), 0, s, gout, gin4, accumulate, H, W, OH, OW, k, stride);
         else hipLaunchKernelGGL((avgpool_bwd_kernel_v4<0, 0>), g, dim3(NT), 0, s, gout, gin4, accumulate, H, W, OH, OW, k, stride);
         return;
     }
+    count(V_AVGPOOL_BWD);
     hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for((long)CN * H * W)), dim3(NT), 0, s, gout, gin, accumulate, CN, H, W,
                        OH, OW, k, stride);
 }
@@ -1297,11 +1345,13 @@ void launch_maxhalves_bwd(const float* gout, const float* tin, float* gin, int a
 }
 void launch_normalize_fwd(const float* in, float* out, float* norms, int C, int NB, int relu_in, hipStream_t s)
 {
+    count(V_NORMALIZE_FWD);
     hipLaunchKernelGGL(normalize_fwd_kernel, dim3(NB), dim3(64), 0, s, in, out, norms, C, NB, relu_in);
 }
 void launch_normalize_bwd(const float* gout, const float* tin, const float* norms, float* gin, int accumulate, int C, int SB,
                           int B, hipStream_t s)
 {
+    count(V_NORMALIZE_BWD);
     hipLaunchKernelGGL(normalize_bwd_kernel, dim3(SB), dim3(64), 0, s, gout, tin, norms, gin, accumulate, C, SB, B);
 }
 void launch_seed_to_cnhw(const float* seed, float* g, int SB, int C, int HW, hipStream_t s)

@@ -1052,6 +1052,17 @@ xfr_status xfr_chain_epilogue_stats(int64_t* compiled_launches, int64_t* interpr
     return XFR_OK;
 }
 
+xfr_status xfr_elementwise_launch_stats(int64_t* counts, int32_t capacity, int32_t* n_variants)
+{
+    const int n = elementwise_num_variants();
+    if (n_variants) *n_variants = n;
+    if (capacity < 0 || (capacity > 0 && !counts)) return fail(XFR_INVALID_ARG, "xfr_elementwise_launch_stats: bad arguments");
+    for (int i = 0; i < n && i < capacity; ++i) counts[i] = elementwise_variant_launches(i);
+    return XFR_OK;
+}
+
+const char* xfr_elementwise_variant_name(int32_t i) { return elementwise_variant_name(i); }
+
 xfr_status xfr_engine_memory(xfr_engine* e, size_t* weight_bytes, size_t* workspace_bytes)
 {
     if (!e) return fail(XFR_INVALID_ARG, "null engine");
