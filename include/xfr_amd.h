@@ -493,6 +493,54 @@ xfr_status xfr_strise_debug_masked_probes(xfr_engine* e, const uint8_t* probe_u8
                                           const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom, int32_t first, int32_t count,
                                           float* out_nchw_dev, void* stream);
 
+/* ---- Inpainting-game scoring (python/xfr/inpainting_game/inpainting_game.py:12-197).  Additive entry points, ABI version 7. ----------------
+ * The reference thresholds a saliency map at n_levels levels (create_threshold_masks, :12-77), switches the probe to its inpainted twin under each
+ * mask (:114-129), embeds the hybrids (:134) and asks which gallery mean each one is nearer to (:135-140), all on the host.  Here every step runs
+ * on the device.  The mask arguments, shared by the four entry points:
+ *   sal_dev       n_maps x H x W float64 maps with a positive sum; every map of a call goes through one launch
+ *   noise_dev     H x W float64, np.random.rand(H, W) after np.random.seed(seed) (:26,37), shared by all maps, or NULL for none
+ *   max_noise     :18;  include_zero: include_zero_elements (:27-32)
+ *   method        XFR_INPAINT_PERCENT_DENSITY (:43-56): levels_host are percentiles in [0, 100], non-decreasing; mask l is cdf / max(cdf) > 1 - p_l / 100
+ *                 (0 for a last percentile of 100), cdf the running sum of s = v / sum(v), v = sal + nz * noise * max_noise, in ascending order of v.
+ *                 EQUAL VALUES ARE ORDERED BY FLAT INDEX (numpy's argsort leaves their order unspecified).
+ *                 XFR_INPAINT_THRESHOLDS (:57,65, the 'mass-threshold' use): levels_host are thresholds, non-increasing; mask l is s > thr_l.
+ *   levels_host   n_levels float64 on the HOST, 1 <= n_levels <= 255
+ * The masks of one map are nested (the thresholds fall as the level rises), and are kept as one byte per pixel: first_on, the first level at which
+ * the pixel is on, n_levels where it never is; mask l is first_on <= l.  All arithmetic is float64 without floating-point atomics: results are
+ * bit-reproducible from run to run.  Every call returns XFR_INVALID_ARG, before anything is launched, for a null pointer, n_maps < 1, n_levels
+ * outside [1, 255], levels that are unsorted or (percentiles) outside [0, 100], and an unknown method. */
+typedef enum { XFR_INPAINT_PERCENT_DENSITY = 0, XFR_INPAINT_THRESHOLDS = 1 } xfr_inpaint_method;
+
+/* classified_as_inpainted_twin (:80-146) for n_maps maps of one probe.  H x W is the engine's input size.
+ *   orig_dev, inpaint_dev   in_c x H x W fp32, network format (in_c = 3, or 1 for Light-CNN): hybrid (map, l) is mask_l ? inpaint : orig, which is
+ *                           what (1 - m) * a + m * b in float64 followed by .float() gives for 0/1 masks (:124-129, whitebox.py:762), written by the
+ *                           device straight into the forward's input
+ *   gal_orig_dev, gal_inp_dev   D fp32 (D = C * H * W of encode_tensor): original_gal_embed and inpaint_gal_embed
+ *   pg_dev, pr_dev          n_maps x n_levels float64: |e / |e| - gal_inp| and |e / |e| - gal_orig| in float64 from the fp32 embedding e (:135-138)
+ *   cls_dev                 n_maps x n_levels uint8: pg < pr (:140)
+ * The n_maps * n_levels hybrids run through xfr_forward in batches of the engine's max_batch; the last batch is padded with copies of the original
+ * whose results are dropped, so one schedule serves every batch.  The hybrids of batch i + 1 are built on a side stream while batch i is encoded.
+ * The call does not block the host. */
+xfr_status xfr_inpaint_score(xfr_engine* e, const double* sal_dev, int32_t n_maps, const double* noise_dev, double max_noise, int32_t include_zero,
+                             int32_t method, const double* levels_host, int32_t n_levels, const float* orig_dev, const float* inpaint_dev,
+                             const float* gal_orig_dev, const float* gal_inp_dev, int32_t encode_tensor, double* pg_dev, double* pr_dev,
+                             uint8_t* cls_dev, void* stream);
+
+/* intersect_over_union_thresholded_saliency (:149-197) as integer counts: gt_dev H x W uint8 (non-zero: inside the ground truth), counts_dev
+ * n_maps x n_levels x 3 int64 = |gt & mask|, |gt | mask|, |~gt & mask| (:178-192).  H x W is the engine's input size. */
+xfr_status xfr_inpaint_iou(xfr_engine* e, const double* sal_dev, int32_t n_maps, const double* noise_dev, double max_noise, int32_t include_zero,
+                           int32_t method, const double* levels_host, int32_t n_levels, const uint8_t* gt_dev, int64_t* counts_dev, void* stream);
+
+/* Parity hooks.  xfr_inpaint_debug_masks: the masks of :12-65 for maps of any size h x w (h * w <= 2^24): first_on_dev n_maps x h x w uint8 and
+ * (cdf_dev may be NULL) the float64 value each pixel was compared by, cdf / max(cdf) or s.  xfr_inpaint_debug_blends: the fp32 hybrids
+ * [first, first + count) of the n_maps * n_levels list (:127-129), count x in_c x H x W, at the engine's input size. */
+xfr_status xfr_inpaint_debug_masks(xfr_engine* e, const double* sal_dev, int32_t n_maps, int32_t h, int32_t w, const double* noise_dev, double max_noise,
+                                   int32_t include_zero, int32_t method, const double* levels_host, int32_t n_levels, uint8_t* first_on_dev,
+                                   double* cdf_dev, void* stream);
+xfr_status xfr_inpaint_debug_blends(xfr_engine* e, const double* sal_dev, int32_t n_maps, const double* noise_dev, double max_noise, int32_t include_zero,
+                                    int32_t method, const double* levels_host, int32_t n_levels, const float* orig_dev, const float* inpaint_dev,
+                                    int32_t first, int32_t count, float* out_dev, void* stream);
+
 /* Debug / parity: after an xfr_ebp call made while tracing is enabled, the per-firing trace
  * sum(P[i]) (what the golden fixtures store for every entry of Whitebox.P, whitebox.py:394).
  * xfr_engine_set_trace(e, 1) makes xfr_ebp record it (slower).  `sums` receives n_firings x S x N doubles

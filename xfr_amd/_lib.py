@@ -23,6 +23,7 @@ class U8Preprocess(ctypes.Structure):
 SUBTREE_ORDER_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_int32,
                                     ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p)
 SUBTREE_MWP, SUBTREE_SALIENCY, SUBTREE_UINT8 = range(3)
+INPAINT_PERCENT_DENSITY, INPAINT_THRESHOLDS = range(2)      # xfr_inpaint_method
 
 
 class SubtreeArgs(ctypes.Structure):
@@ -44,6 +45,7 @@ class XfrError(RuntimeError):
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
 _F = ctypes.c_float
+_D = ctypes.c_double
 SYMBOLS = [
     ('xfr_abi_version', _I, []),
     ('xfr_last_error', ctypes.c_char_p, []),
@@ -91,6 +93,10 @@ SYMBOLS = [
     ('xfr_strise_combine', _I, [_P, _P, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _P, _P]),
     ('xfr_strise_debug_masks', _I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _I, _P, _P]),
     ('xfr_strise_debug_masked_probes', _I, [_P, _P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _I, _P, _P]),
+    ('xfr_inpaint_score', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    ('xfr_inpaint_iou', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _P]),
+    ('xfr_inpaint_debug_masks', _I, [_P, _P, _I, _I, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _P]),
+    ('xfr_inpaint_debug_blends', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _I, _I, _P, _P]),
     ('xfr_ebp_store_firing', _I, [_P, _P, _I, _I, _P, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _P]),
     ('xfr_engine_set_trace', _I, [_P, _I]),
     ('xfr_engine_trace_size', _I, [_P, ctypes.POINTER(_I)]),

@@ -457,3 +457,22 @@ void launch_strise_score(const float* emb, int first, int count, const float* re
 // A [scale^2][gh * gw] and wsum [scale^2] are scratch
 void launch_strise_merge(const double* weights, const int* cells, const int* order, const int* group_off, double* A, double* wsum, double count, double sign,
                          double* sal, const StriseGeom& g, hipStream_t s);
+
+// ---- inpainting-game scoring (inpaint.hip; python/xfr/inpainting_game/inpainting_game.py:12-197) ----------------------------
+// Nested threshold masks are stored as one byte per pixel, first_on: the first level at which the pixel is on, n_levels where it never is; mask l
+// is first_on <= l.  A level table travels as a kernel argument: thr[l] is the threshold of level l (non-increasing in l).
+constexpr int INPAINT_MAX_LEVELS = 255;
+constexpr long INPAINT_MAX_PIXELS = 1L << 24;
+struct InpaintLevels { int n; double thr[INPAINT_MAX_LEVELS]; };
+constexpr size_t inpaint_scratch_bytes(long n) { return (size_t)n * 32; }      // per map: two key arrays, two index arrays, the running sums
+// first_on [n_maps][n] (and cdf [n_maps][n], may be null: the value each pixel is compared by) of float64 maps sal [n_maps][n]; noise [n] or null;
+// density != 0: percent-density (the cumulative sum in ascending order, normalised), else s / sum(s) itself.  One workgroup per map.
+void launch_inpaint_masks(const double* sal, const double* noise, double max_noise, int include_zero, int density, const InpaintLevels& lv, int n_maps, long n,
+                          void* scratch, uint8_t* first_on, double* cdf, hipStream_t s);
+// out [rows][C][HW]: hybrid first + r of the list (map-major, n_levels per map) = mask ? inpaint : orig; hybrids beyond `total` are the original
+void launch_inpaint_blend(const uint8_t* first_on, const float* orig, const float* inpaint, float* out, int C, long HW, long first, int rows, long total,
+                          int n_levels, hipStream_t s);
+// per embedding i < count: pr = |e / |e| - g_orig|, pg = |e / |e| - g_inp| in float64, cls = pg < pr
+void launch_inpaint_dist(const float* emb, int count, const float* g_orig, const float* g_inp, int D, double* pg, double* pr, uint8_t* cls, hipStream_t s);
+// counts [n_maps][n_levels][3] = |gt & mask|, |gt | mask|, |~gt & mask|
+void launch_inpaint_iou(const uint8_t* first_on, const uint8_t* gt, long n, int n_maps, int n_levels, long long* counts, hipStream_t s);

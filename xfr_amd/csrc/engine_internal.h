@@ -7,6 +7,7 @@
 //   engine.hip         the C ABI: create / destroy / weights / setters / forward / EBP / contrastive / triplet / uint8 / profiling
 //   subtree.hip        the C ABI: layerwise and weighted-subtree EBP
 //   strise_abi.hip     the C ABI: STRise blackbox saliency
+//   inpaint_abi.hip    the C ABI: inpainting-game scoring
 //   comm.hip           the C ABI: the RCCL binding
 //   plan_describe.hip  the C ABI: xfr_plan_describe
 #pragma once
@@ -250,6 +251,7 @@ struct xfr_engine {
     double last_gemm_flops = 0.0;
 
     struct StriseState* strise = nullptr;   // xfr_strise_*: buffers, side stream and events, built on first use (strise_abi.hip)
+    struct InpaintState* inpaint = nullptr; // xfr_inpaint_*: the same for inpainting-game scoring (inpaint_abi.hip)
 
     float* t_bank = nullptr;       // when set, true activations live in this bank (gallery forward of a triplet step)
     float* ws_enc = nullptr;       // second bank of true activations (T region only), allocated on first use
@@ -328,5 +330,8 @@ void presplit_weights(xfr_engine* e);
 
 // strise_abi.hip
 void strise_release(xfr_engine* e);
+
+// inpaint_abi.hip
+void inpaint_release(xfr_engine* e);
 
 }  // namespace xfr

@@ -565,6 +565,96 @@ class Engine(object):
                                                                int(first), count, out.data_ptr(), _stream_ptr(self.device)))
         return out
 
+    # -- inpainting-game scoring (include/xfr_amd.h: xfr_inpaint_*) -----------------------------------------
+    def _inpaint_masks_args(self, sal, noise, levels, method, size=None):
+        """-> (sal float64 n_maps x H x W on the device, noise or None, levels float64 host array, its ctypes pointer, method id)."""
+        sal = torch.as_tensor(sal)
+        if sal.dim() == 2:
+            sal = sal.unsqueeze(0)
+        c, h, w = self.program.in_shape
+        if sal.dim() != 3 or (size is None and tuple(sal.shape[1:]) != (h, w)):
+            raise ValueError('expected saliency maps n_maps x %d x %d (the engine input size), got %s' % (h, w, tuple(sal.shape)))
+        sal = sal.detach().to(self.device, torch.float64).contiguous()
+        if noise is not None:
+            noise = torch.as_tensor(noise)
+            if tuple(noise.shape) != tuple(sal.shape[1:]):
+                raise ValueError('expected noise of %s, got %s' % (tuple(sal.shape[1:]), tuple(noise.shape)))
+            noise = noise.detach().to(self.device, torch.float64).contiguous()
+        levels = np.ascontiguousarray(np.asarray(levels, dtype=np.float64).ravel())
+        if method not in (_lib.INPAINT_PERCENT_DENSITY, _lib.INPAINT_THRESHOLDS):
+            method = {'percent-density': _lib.INPAINT_PERCENT_DENSITY, 'thresholds': _lib.INPAINT_THRESHOLDS}.get(method, -1 if isinstance(method, str) else method)
+        return sal, noise, levels, levels.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(method)
+
+    def _inpaint_images(self, orig, inpaint):
+        shape = tuple(self.program.in_shape)
+        orig, inpaint = torch.as_tensor(orig), torch.as_tensor(inpaint)
+        if tuple(orig.shape) != shape or tuple(inpaint.shape) != shape:
+            raise ValueError('expected the original and its inpainted twin in network format %s, got %s and %s' % (shape, tuple(orig.shape), tuple(inpaint.shape)))
+        return orig.detach().to(self.device, torch.float32).contiguous(), inpaint.detach().to(self.device, torch.float32).contiguous()
+
+    def inpaint_score(self, sal, levels, orig, inpaint, gal_orig, gal_inp, encode_tensor, method='percent-density', noise=None, max_noise=1e-9,
+                      include_zero=True):
+        """xfr_inpaint_score: the inpainting game of n_maps maps of one probe.  sal n_maps x H x W float64, levels percentiles (or thresholds), orig /
+        inpaint in_c x H x W fp32 network tensors, gal_orig / gal_inp D-vectors.  -> (cls uint8, pg float64, pr float64), n_maps x n_levels device tensors."""
+        sal, noise, levels, lp, method = self._inpaint_masks_args(sal, noise, levels, method)
+        orig, inpaint = self._inpaint_images(orig, inpaint)
+        try:
+            d = int(np.prod(self.tensor_shape(encode_tensor)))
+        except ValueError:
+            d = None          # xfr_inpaint_score refuses the tensor id itself, naming it
+        gals = [torch.as_tensor(g).detach().to(self.device, torch.float32).reshape(-1).contiguous() for g in (gal_orig, gal_inp)]
+        if d is not None and (gals[0].numel() != d or gals[1].numel() != d):
+            raise ValueError('expected gallery embeddings of %d values, got %d and %d' % (d, gals[0].numel(), gals[1].numel()))
+        shape = (sal.shape[0], max(len(levels), 1))
+        pg = torch.empty(shape, device=self.device, dtype=torch.float64)
+        pr = torch.empty(shape, device=self.device, dtype=torch.float64)
+        cls = torch.empty(shape, device=self.device, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.xfr_inpaint_score(self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None, float(max_noise),
+                                                  1 if include_zero else 0, method, lp, len(levels), orig.data_ptr(), inpaint.data_ptr(),
+                                                  gals[0].data_ptr(), gals[1].data_ptr(), int(encode_tensor), pg.data_ptr(), pr.data_ptr(), cls.data_ptr(),
+                                                  _stream_ptr(self.device)))
+        return cls, pg, pr
+
+    def inpaint_iou(self, sal, levels, ground_truth, method='percent-density', noise=None, max_noise=1e-9, include_zero=True):
+        """xfr_inpaint_iou: -> int64 n_maps x n_levels x 3 (device tensor): |gt & mask|, |gt | mask|, |~gt & mask|."""
+        sal, noise, levels, lp, method = self._inpaint_masks_args(sal, noise, levels, method)
+        gt = torch.as_tensor(ground_truth)
+        if tuple(gt.shape) != tuple(sal.shape[1:]):
+            raise ValueError('expected a ground truth of %s, got %s' % (tuple(sal.shape[1:]), tuple(gt.shape)))
+        gt = (gt != 0).to(self.device, torch.uint8).contiguous()
+        counts = torch.empty((sal.shape[0], max(len(levels), 1), 3), device=self.device, dtype=torch.int64)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.xfr_inpaint_iou(self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None, float(max_noise),
+                                                1 if include_zero else 0, method, lp, len(levels), gt.data_ptr(), counts.data_ptr(),
+                                                _stream_ptr(self.device)))
+        return counts
+
+    def inpaint_masks(self, sal, levels, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, want_cdf=False):
+        """Parity hook (xfr_inpaint_debug_masks), maps of any size: -> first_on uint8 n_maps x h x w (mask l is first_on <= l), and with want_cdf the
+        float64 value every pixel was compared by."""
+        sal, noise, levels, lp, method = self._inpaint_masks_args(sal, noise, levels, method, size='any')
+        first_on = torch.empty(tuple(sal.shape), device=self.device, dtype=torch.uint8)
+        cdf = torch.empty(tuple(sal.shape), device=self.device, dtype=torch.float64) if want_cdf else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.xfr_inpaint_debug_masks(self._h, sal.data_ptr(), sal.shape[0], sal.shape[1], sal.shape[2],
+                                                        noise.data_ptr() if noise is not None else None, float(max_noise), 1 if include_zero else 0, method,
+                                                        lp, len(levels), first_on.data_ptr(), cdf.data_ptr() if want_cdf else None,
+                                                        _stream_ptr(self.device)))
+        return (first_on, cdf) if want_cdf else first_on
+
+    def inpaint_blends(self, sal, levels, orig, inpaint, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, first=0, count=None):
+        """Parity hook (xfr_inpaint_debug_blends): the fp32 hybrids [first, first + count) of the n_maps * n_levels list, count x in_c x H x W."""
+        sal, noise, levels, lp, method = self._inpaint_masks_args(sal, noise, levels, method)
+        orig, inpaint = self._inpaint_images(orig, inpaint)
+        count = sal.shape[0] * len(levels) - first if count is None else int(count)
+        out = torch.empty((max(count, 0),) + tuple(self.program.in_shape), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.xfr_inpaint_debug_blends(self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None,
+                                                         float(max_noise), 1 if include_zero else 0, method, lp, len(levels), orig.data_ptr(),
+                                                         inpaint.data_ptr(), int(first), count, out.data_ptr(), _stream_ptr(self.device)))
+        return out
+
     # ------------------------------------------------------------------------------------------------
     def set_trace(self, on):
         _lib.check(self.lib.xfr_engine_set_trace(self._h, 1 if on else 0))
