@@ -452,7 +452,8 @@ xfr_status xfr_ebp_store_firing(xfr_engine* e, const float* x_dev, int32_t n, in
  * which is skimage.transform.resize(order=1, mode='reflect', anti_aliasing=False) of skimage >= 0.19 cropped at [x : x + H, y : y + W] (:333).
  * H x W is the engine's input size.  cells_host: n_masks x num_elements int32, shifts_host: n_masks x 2 int32, both HOST arrays.  Every call
  * returns XFR_INVALID_ARG, before anything is launched, for a cell index outside [0, gh * gw), a shift outside [0, mask_scale),
- * mask_scale > min(H, W) or gh * gw > 4096. */
+ * mask_scale > min(H, W) or gh * gw > 4096.  The xfr_strise_* and xfr_inpaint_* calls on one engine share its sweep buffers and are ordered one
+ * behind another on the device, whatever streams they are given. */
 typedef struct {
     int32_t grid_h, grid_w;     /* gh, gw: ceil(H / mask_scale), ceil(W / mask_scale) in the reference (:302) */
     int32_t mask_scale;
@@ -508,7 +509,8 @@ xfr_status xfr_strise_debug_masked_probes(xfr_engine* e, const uint8_t* probe_u8
  * The masks of one map are nested (the thresholds fall as the level rises), and are kept as one byte per pixel: first_on, the first level at which
  * the pixel is on, n_levels where it never is; mask l is first_on <= l.  All arithmetic is float64 without floating-point atomics: results are
  * bit-reproducible from run to run.  Every call returns XFR_INVALID_ARG, before anything is launched, for a null pointer, n_maps < 1, n_levels
- * outside [1, 255], levels that are unsorted or (percentiles) outside [0, 100], and an unknown method. */
+ * outside [1, 255], levels that are unsorted or (percentiles) outside [0, 100], and an unknown method.  On one engine these calls and the
+ * xfr_strise_* calls are ordered one behind another on the device, whatever streams they are given. */
 typedef enum { XFR_INPAINT_PERCENT_DENSITY = 0, XFR_INPAINT_THRESHOLDS = 1 } xfr_inpaint_method;
 
 /* classified_as_inpainted_twin (:80-146) for n_maps maps of one probe.  H x W is the engine's input size.

@@ -207,6 +207,11 @@ def test_partial_batches_are_padded_and_dropped(mini32, mini48):
         _check_scores('mini/zero_on', tag, *_score(wb, 'mini/zero_on'))
 
 
+def test_thirteen_batches_reuse_both_buffers(gpu_device):
+    """101 hybrids on an engine of 8: thirteen batches, the last of five, so each of the two input buffers goes back to the side stream six times."""
+    _check_scores('mini/zero_on', '/batch8', *_score(_whitebox('stresnet_mini', 8, gpu_device), 'mini/zero_on'))
+
+
 @pytest.mark.parametrize('name', ['mini/zero_on', 'mini/zero_off', 'mini/thresholds', 'mini/two_maps', 'lcnn/zero_on'])
 def test_iou_counts_are_exact(mini48, lcnn, name):
     c = _case(name)

@@ -294,6 +294,36 @@ def test_partial_batch_is_padded_and_dropped(mini32, mini48, images):
         assert np.abs(orig - lone).max() <= 1e-4
 
 
+def test_seven_batches_reuse_both_buffers(gpu_device, images):
+    """48 masks + the probe = 49 images on an engine of 8: seven batches, so each of the two input buffers is handed back to the side stream
+    (ev_free) several times; the last batch holds one real image and seven paddings."""
+    case = 'mini/e1'
+    st = _strise(case, images, _whitebox('stresnet_mini', 8, gpu_device, 5))
+    st.score_masks()
+    err, r = _score_error(case, st.mask_scores)
+    REPORT['scores/%s/batch8' % case] = {'rel_err_vs_ref64': float(err), 'r_ref32_vs_ref64': float(r), 'bar': float(4 * r)}
+    print('%s batch8 scores: %.3e (bar %.3e)' % (case, err, 4 * r))
+    assert st.mask_scores.shape == (48,) and np.isfinite(st.mask_scores).all()
+    assert err <= 4 * r
+
+
+def test_single_batch_runs_no_second_generate(mini32, images):
+    """The first 31 masks of the case + the probe = 32 images: exactly one batch of the engine of 32, straight through Engine.strise_score."""
+    case = 'mini/e1'
+    st = _strise(case, images, mini32)
+    eng, enc = st._engine()
+    cells, shifts, grid, scale = st._mask_args()
+    scores, _ = eng.strise_score(torch.from_numpy(st.probe), torch.from_numpy(st.fill_image), cells[:31], shifts[:31], grid, scale, st._embed(st.refs),
+                                 st._embed(st.gallery), enc)
+    scores = scores.cpu().numpy()
+    s64 = GOLD[case + '/scores64'][:31]
+    err, r = np.abs(scores - s64).max() / np.abs(s64).max(), _score_error(case, GOLD[case + '/scores64'])[1]
+    REPORT['scores/%s/first31' % case] = {'rel_err_vs_ref64': float(err), 'r_ref32_vs_ref64': float(r), 'bar': float(4 * r)}
+    print('%s first 31 masks, one batch: %.3e (bar %.3e)' % (case, err, 4 * r))
+    assert scores.shape == (31,) and np.isfinite(scores).all()
+    assert err <= 4 * r
+
+
 # ---- error paths -----------------------------------------------------------------------------------------------------------------------
 def test_bad_arguments_are_refused_before_any_launch(mini48, lcnn, images):
     eng = mini48._engine(48)

@@ -6,6 +6,7 @@
 //   backward.hip       chain resolution and the sweep executor
 //   engine.hip         the C ABI: create / destroy / weights / setters / forward / EBP / contrastive / triplet / uint8 / profiling
 //   subtree.hip        the C ABI: layerwise and weighted-subtree EBP
+//   probe_sweep.hip    the batched sweep with its side stream that the next two share (ProbeSweep)
 //   strise_abi.hip     the C ABI: STRise blackbox saliency
 //   inpaint_abi.hip    the C ABI: inpainting-game scoring
 //   comm.hip           the C ABI: the RCCL binding
@@ -21,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -120,6 +122,17 @@ struct BwdPlan {
 
 }  // namespace xfr
 using namespace xfr;
+
+// xfr_strise_* and xfr_inpaint_*: what their sweeps share, one per engine (probe_sweep.hip)
+struct ProbeSweep {
+    hipStream_t s_gen = nullptr;                       // the images of batch i + 1 are built here while batch i encodes
+    hipEvent_t ev_in = nullptr, ev_ready[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
+    hipEvent_t ev_done = nullptr;                      // the end of the previous call of either family, on that call's stream
+    bool done_recorded = false;
+    float* xbuf[2] = {nullptr, nullptr};               // two batches of network input, max_batch x in_c x in_h x in_w
+    float* emb = nullptr;                              // max_batch x D embeddings of the running batch
+    size_t emb_floats = 0;
+};
 
 struct xfr_engine {
     int device = 0;
@@ -250,7 +263,8 @@ struct xfr_engine {
     long last_gemm_launches = 0;
     double last_gemm_flops = 0.0;
 
-    struct StriseState* strise = nullptr;   // xfr_strise_*: buffers, side stream and events, built on first use (strise_abi.hip)
+    ProbeSweep* sweep = nullptr;            // xfr_strise_* and xfr_inpaint_*: side stream, events, input and embedding buffers, built on first use
+    struct StriseState* strise = nullptr;   // xfr_strise_*: the family's own buffers, built on first use (strise_abi.hip)
     struct InpaintState* inpaint = nullptr; // xfr_inpaint_*: the same for inpainting-game scoring (inpaint_abi.hip)
 
     float* t_bank = nullptr;       // when set, true activations live in this bank (gallery forward of a triplet step)
@@ -327,6 +341,36 @@ xfr_status check_run(xfr_engine* e, const void* x, int n);
 xfr_status fence_slot0(xfr_engine* e, hipStream_t s);
 xfr_status ebp_core(xfr_engine* e, const float* x_dev, int n, int S, int seed_tensor, const float* seed_dev, hipStream_t s);
 void presplit_weights(xfr_engine* e);
+
+// probe_sweep.hip.  Every xfr_strise_* / xfr_inpaint_* entry point that touches device state runs between sweep_enter, after its argument checks,
+// and sweep_leave (SweepCall does the latter on every way out), so calls on one engine are ordered one behind another whatever their streams.
+xfr_status sweep_enter(xfr_engine* e, hipStream_t s, ProbeSweep** sw);      // hipSetDevice; `s` waits for the side stream's tail and the previous call's end
+void sweep_leave(ProbeSweep* sw, hipStream_t s);                            // records the end of this call on `s`
+struct SweepCall {
+    ProbeSweep* sw = nullptr;
+    hipStream_t s = nullptr;
+    xfr_status enter(xfr_engine* e, hipStream_t stream) { s = stream; return sweep_enter(e, s, &sw); }
+    ~SweepCall() { if (sw) sweep_leave(sw, s); }
+};
+xfr_status sweep_side_follows(ProbeSweep* sw, hipStream_t s);               // the side stream waits for what `s` holds now
+// the batch loop over ceil(n_images / max_batch) batches: generate(i, xbuf, side stream) launches the max_batch images of batch i (padding included),
+// consume(i, emb, s) what reads their embeddings; the buffer hand-over, xfr_forward and the join of the side stream on an error are the loop's
+using SweepGenerate = std::function<void(long, float*, hipStream_t)>;
+using SweepConsume = std::function<void(long, const float*, hipStream_t)>;
+xfr_status run_sweep(xfr_engine* e, ProbeSweep* sw, long n_images, int encode_tensor, hipStream_t s, const SweepGenerate& generate,
+                     const SweepConsume& consume);
+void sweep_release(xfr_engine* e);
+
+// a device buffer of at least `need` elements; growing frees the old one behind a device synchronisation
+template <class T>
+xfr_status grow(T** p, size_t* cap, size_t need)
+{
+    if (*cap >= need) return XFR_OK;
+    if (*p) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    HIP_TRY(hipMalloc(p, need * sizeof(T)));
+    *cap = need;
+    return XFR_OK;
+}
 
 // strise_abi.hip
 void strise_release(xfr_engine* e);

@@ -1,13 +1,8 @@
 // strise_abi.hip -- the C ABI of STRise blackbox saliency (include/xfr_amd.h: xfr_strise_*; python/xfr/models/blackbox.py:299-442): argument checks,
-// the batched sweep with its side stream, the grouping of the masks by shift for the merge.  The kernels are strise.hip.
+// the two ends of the batched sweep (probe_sweep.hip), the grouping of the masks by shift for the merge.  The kernels are strise.hip.
 #include "engine_internal.h"
 
 struct StriseState {
-    hipStream_t s_gen = nullptr;                       // the masked probes of batch i + 1 are built here while batch i encodes
-    hipEvent_t ev_in = nullptr, ev_ready[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
-    float* xbuf[2] = {nullptr, nullptr};               // two batches of network input, max_batch x 3 x H x W
-    float* emb = nullptr;                              // max_batch x D embeddings of the running batch
-    size_t emb_floats = 0;
     double* orig = nullptr;                            // n_refs + n_gal similarities of the unmasked probe, then as many 1 / |g|
     size_t orig_cap = 0;
     int* tab = nullptr;                                // cells, shifts, shift order and group offsets of the current call
@@ -22,14 +17,6 @@ void strise_release(xfr_engine* e)
 {
     StriseState* st = e->strise;
     if (!st) return;
-    for (int k = 0; k < 2; ++k) {
-        if (st->xbuf[k]) (void)hipFree(st->xbuf[k]);
-        if (st->ev_ready[k]) (void)hipEventDestroy(st->ev_ready[k]);
-        if (st->ev_free[k]) (void)hipEventDestroy(st->ev_free[k]);
-    }
-    if (st->ev_in) (void)hipEventDestroy(st->ev_in);
-    if (st->s_gen) (void)hipStreamDestroy(st->s_gen);
-    if (st->emb) (void)hipFree(st->emb);
     if (st->orig) (void)hipFree(st->orig);
     if (st->tab) (void)hipFree(st->tab);
     if (st->merge_ws) (void)hipFree(st->merge_ws);
@@ -41,30 +28,10 @@ void strise_release(xfr_engine* e)
 
 namespace {
 
-xfr_status strise_state(xfr_engine* e, StriseState** out)
+StriseState* strise_state(xfr_engine* e)
 {
     if (!e->strise) e->strise = new StriseState();
-    StriseState* st = e->strise;
-    if (!st->s_gen) {
-        HIP_TRY(hipStreamCreateWithFlags(&st->s_gen, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&st->ev_in, hipEventDisableTiming));
-        for (int k = 0; k < 2; ++k) {
-            HIP_TRY(hipEventCreateWithFlags(&st->ev_ready[k], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&st->ev_free[k], hipEventDisableTiming));
-        }
-    }
-    *out = st;
-    return XFR_OK;
-}
-
-template <class T>
-xfr_status grow(T** p, size_t* cap, size_t need)
-{
-    if (*cap >= need) return XFR_OK;
-    if (*p) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    HIP_TRY(hipMalloc(p, need * sizeof(T)));
-    *cap = need;
-    return XFR_OK;
+    return e->strise;
 }
 
 // what every entry point checks before anything is launched
@@ -101,11 +68,22 @@ xfr_status check_u8(xfr_engine* e)
     return XFR_OK;
 }
 
-// rows [first, first + count) of the sweep's image list -- image 0 is the unmasked probe, images 1 .. n_masks the masks, anything beyond is padding
-// (all-ones masks: cell -1, shift 0) -- as one host table: count x n_elem cells, then count x 2 shifts
-void fill_rows(std::vector<int>& tab, const int32_t* cells, const int32_t* shifts, int n_masks, int n_elem, long first, long count, bool with_probe)
+// a host table into the state's `tab` on `s`; the host waits for the copy there: the table is pageable and local to the call
+xfr_status upload_table(StriseState* st, const std::vector<int>& tab, hipStream_t s)
 {
-    tab.assign((size_t)count * (n_elem + 2), -1);
+    xfr_status rc = grow(&st->tab, &st->tab_cap, tab.size());
+    if (rc != XFR_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(st->tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return XFR_OK;
+}
+
+// rows [first, first + count) of the sweep's image list -- image 0 is the unmasked probe, images 1 .. n_masks the masks, anything beyond is padding
+// (all-ones masks: cell -1, shift 0) -- as one table on the device: count x n_elem cells, then count x 2 shifts
+xfr_status upload_rows(StriseState* st, const int32_t* cells, const int32_t* shifts, int n_masks, int n_elem, long first, long count, bool with_probe,
+                       hipStream_t s)
+{
+    std::vector<int> tab((size_t)count * (n_elem + 2), -1);
     int* sh = tab.data() + (size_t)count * n_elem;
     for (long r = 0; r < count; ++r) {
         const long k = first + r - (with_probe ? 1 : 0);
@@ -117,6 +95,7 @@ void fill_rows(std::vector<int>& tab, const int32_t* cells, const int32_t* shift
             sh[2 * r] = sh[2 * r + 1] = 0;
         }
     }
+    return upload_table(st, tab, s);
 }
 
 }  // namespace
@@ -137,69 +116,39 @@ xfr_status xfr_strise_score(xfr_engine* e, const uint8_t* probe_u8_dev, const do
         return fail(XFR_INVALID_ARG, "strise: %d references against %d gallery images do not broadcast (equal counts, or one of them 1)", n_refs, n_gal);
     if (encode_tensor < 1 || encode_tensor >= (int)e->tens.size()) return fail(XFR_INVALID_ARG, "bad tensor id");
     if (!e->weights_loaded) return fail(XFR_STATE_ERROR, "weights not loaded");
-    HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    StriseState* st = nullptr;
-    rc = strise_state(e, &st);
+    SweepCall call;
+    rc = call.enter(e, s);
     if (rc != XFR_OK) return rc;
-    const int B = e->max_batch;
-    const size_t D = (size_t)e->tens[encode_tensor].per_n();
-    const size_t in_floats = (size_t)B * 3 * g.H * g.W;
-    for (int k = 0; k < 2; ++k)
-        if (!st->xbuf[k]) HIP_TRY(hipMalloc(&st->xbuf[k], in_floats * sizeof(float)));
-    rc = grow(&st->emb, &st->emb_floats, (size_t)B * D);
-    if (rc != XFR_OK) return rc;
+    ProbeSweep* sw = call.sw;
+    StriseState* st = strise_state(e);
+    const int B = e->max_batch, D = (int)e->tens[encode_tensor].per_n();
     const int nrg = n_refs + n_gal;
     rc = grow(&st->orig, &st->orig_cap, (size_t)2 * nrg);
     if (rc != XFR_OK) return rc;
     const long total = (long)n_masks + 1;
-    const long n_batches = (total + B - 1) / B;
-    const long rows = n_batches * B;
-    rc = grow(&st->tab, &st->tab_cap, (size_t)rows * (g.n_elem + 2));
+    const long rows = (total + B - 1) / B * B;
+    // the whole sweep's cells and shifts go to the device once (6500 masks of 40 cells: 1 MB), on the side stream behind the caller's: the probe and
+    // the fill may still be in flight there.  This is the sweep's one host wait
+    rc = sweep_side_follows(sw, s);
     if (rc != XFR_OK) return rc;
-    // the whole sweep's cells and shifts go to the device once (6500 masks of 40 cells: 1 MB), behind whatever an earlier call left on the side stream
-    std::vector<int> tab;
-    fill_rows(tab, cells_host, shifts_host, n_masks, g.n_elem, 0, rows, true);
-    HIP_TRY(hipEventRecord(st->ev_in, s));                 // the probe and the fill may still be in flight on the caller's stream
-    HIP_TRY(hipStreamWaitEvent(st->s_gen, st->ev_in, 0));
-    HIP_TRY(hipMemcpyAsync(st->tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st->s_gen));
-    HIP_TRY(hipStreamSynchronize(st->s_gen));              // `tab` is pageable and local: the host waits here for what the caller's stream held
+    rc = upload_rows(st, cells_host, shifts_host, n_masks, g.n_elem, 0, rows, true, sw->s_gen);
+    if (rc != XFR_OK) return rc;
     const int* cells_d = st->tab;
     const int* shifts_d = st->tab + (size_t)rows * g.n_elem;
     double* orig = st->orig;
     double* ginv = st->orig + nrg;
-    bool used[2] = {false, false};
-    auto generate = [&](long i) -> xfr_status {
-        const int k = (int)(i & 1);
-        if (used[k]) HIP_TRY(hipStreamWaitEvent(st->s_gen, st->ev_free[k], 0));      // the forward that last read this buffer
-        launch_strise_masked(probe_u8_dev, fill_dev, cells_d + (size_t)i * B * g.n_elem, shifts_d + (size_t)i * B * 2, B, st->xbuf[k], g, e->u8_pre.mean,
-                             st->s_gen);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(st->ev_ready[k], st->s_gen));
-        return XFR_OK;
-    };
-    // whatever happens, the caller's stream ends up ordered behind the side stream: nothing of this call outlives what the caller enqueues next
-    auto join = [&]() { if (hipEventRecord(st->ev_in, st->s_gen) == hipSuccess) (void)hipStreamWaitEvent(s, st->ev_in, 0); };
-    rc = generate(0);
-    for (long i = 0; rc == XFR_OK && i < n_batches; ++i) {
-        const int k = (int)(i & 1);
-        if (i + 1 < n_batches) {
-            rc = generate(i + 1);
-            if (rc != XFR_OK) break;
-        }
-        hipError_t he = hipStreamWaitEvent(s, st->ev_ready[k], 0);
-        if (he != hipSuccess) { rc = fail(XFR_HIP_ERROR, "hipStreamWaitEvent failed: %s", hipGetErrorString(he)); break; }
-        rc = xfr_forward(e, st->xbuf[k], B, encode_tensor, st->emb, s);
-        if (rc != XFR_OK) break;
-        he = hipEventRecord(st->ev_free[k], s);
-        if (he != hipSuccess) { rc = fail(XFR_HIP_ERROR, "hipEventRecord failed: %s", hipGetErrorString(he)); break; }
-        used[k] = true;
-        if (i == 0) launch_strise_orig(st->emb, refs_dev, n_refs, gallery_dev, n_gal, (int)D, orig, ginv, s);      // image 0: the unmasked probe
-        // images [i B, i B + B) of the list; image 0 is the probe, images beyond n_masks are padding
-        const long lo = std::max(1L, i * B), hi = std::min(total, (i + 1) * B);
-        launch_strise_score(st->emb, (int)(lo - i * B), (int)(hi - lo), refs_dev, n_refs, gallery_dev, n_gal, (int)D, orig, ginv, scores_dev + (lo - 1), s);
-    }
-    if (rc != XFR_OK) { const std::string why = g_err; join(); g_err = why; return rc; }
+    rc = run_sweep(e, sw, total, encode_tensor, s,
+        [&](long i, float* x, hipStream_t side) {
+            launch_strise_masked(probe_u8_dev, fill_dev, cells_d + (size_t)i * B * g.n_elem, shifts_d + (size_t)i * B * 2, B, x, g, e->u8_pre.mean, side);
+        },
+        [&](long i, const float* emb, hipStream_t) {
+            if (i == 0) launch_strise_orig(emb, refs_dev, n_refs, gallery_dev, n_gal, D, orig, ginv, s);      // image 0: the unmasked probe
+            // images [i B, i B + B) of the list; image 0 is the probe, images beyond n_masks are padding
+            const long lo = std::max(1L, i * B), hi = std::min(total, (i + 1) * B);
+            launch_strise_score(emb, (int)(lo - i * B), (int)(hi - lo), refs_dev, n_refs, gallery_dev, n_gal, D, orig, ginv, scores_dev + (lo - 1), s);
+        });
+    if (rc != XFR_OK) return rc;
     if (orig_dev) HIP_TRY(hipMemcpyAsync(orig_dev, orig, nrg * sizeof(double), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipGetLastError());
     return XFR_OK;
@@ -236,20 +185,15 @@ xfr_status xfr_strise_combine(xfr_engine* e, const double* weights_dev, int32_t 
         std::vector<int> at(off, off + ng);
         for (int k = 0; k < n_masks; ++k) order[at[shifts_host[2 * k] * g.scale + shifts_host[2 * k + 1]]++] = k;      // index order inside a group
     }
-    HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    StriseState* st = nullptr;
-    rc = strise_state(e, &st);
+    SweepCall call;      // the table may still be read by the side stream of an earlier xfr_strise_score: this call starts behind it
+    rc = call.enter(e, s);
     if (rc != XFR_OK) return rc;
-    // the table may still be read by the side stream of an earlier xfr_strise_score: order this call behind it
-    HIP_TRY(hipEventRecord(st->ev_in, st->s_gen));
-    HIP_TRY(hipStreamWaitEvent(s, st->ev_in, 0));
-    rc = grow(&st->tab, &st->tab_cap, tab.size());
-    if (rc != XFR_OK) return rc;
+    StriseState* st = strise_state(e);
     rc = grow(&st->merge_ws, &st->merge_cap, (size_t)ng * nc + ng);
     if (rc != XFR_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(st->tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));                      // `tab` is pageable and local
+    rc = upload_table(st, tab, s);
+    if (rc != XFR_OK) return rc;
     const int* order_d = st->tab + (size_t)n_masks * g.n_elem;
     launch_strise_merge(weights_dev, st->tab, order_d, order_d + n_masks, st->merge_ws, st->merge_ws + (size_t)ng * nc, (double)n_selected, (double)sign,
                         sal_dev, g, s);
@@ -265,19 +209,13 @@ xfr_status xfr_strise_debug_masks(xfr_engine* e, const int32_t* cells_host, cons
     if (rc != XFR_OK) return rc;
     if (!masks_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
     if (first < 0 || count < 1 || (long)first + count > n_masks) return fail(XFR_INVALID_ARG, "strise: masks [%d, %d + %d) of %d", first, first, count, n_masks);
-    HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    StriseState* st = nullptr;
-    rc = strise_state(e, &st);
+    SweepCall call;
+    rc = call.enter(e, s);
     if (rc != XFR_OK) return rc;
-    HIP_TRY(hipEventRecord(st->ev_in, st->s_gen));
-    HIP_TRY(hipStreamWaitEvent(s, st->ev_in, 0));
-    rc = grow(&st->tab, &st->tab_cap, (size_t)count * (g.n_elem + 2));
+    StriseState* st = strise_state(e);
+    rc = upload_rows(st, cells_host, shifts_host, n_masks, g.n_elem, first, count, false, s);
     if (rc != XFR_OK) return rc;
-    std::vector<int> tab;
-    fill_rows(tab, cells_host, shifts_host, n_masks, g.n_elem, first, count, false);
-    HIP_TRY(hipMemcpyAsync(st->tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
     launch_strise_masks(st->tab, st->tab + (size_t)count * g.n_elem, count, masks_dev, g, s);
     HIP_TRY(hipGetLastError());
     return XFR_OK;
@@ -295,19 +233,13 @@ xfr_status xfr_strise_debug_masked_probes(xfr_engine* e, const uint8_t* probe_u8
     if (rc != XFR_OK) return rc;
     if (first < 0 || count < 1 || (long)first + count > n_masks || count > e->max_batch)
         return fail(XFR_INVALID_ARG, "strise: masks [%d, %d + %d) of %d, at most %d per call", first, first, count, n_masks, e->max_batch);
-    HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    StriseState* st = nullptr;
-    rc = strise_state(e, &st);
+    SweepCall call;
+    rc = call.enter(e, s);
     if (rc != XFR_OK) return rc;
-    HIP_TRY(hipEventRecord(st->ev_in, st->s_gen));
-    HIP_TRY(hipStreamWaitEvent(s, st->ev_in, 0));
-    rc = grow(&st->tab, &st->tab_cap, (size_t)count * (g.n_elem + 2));
+    StriseState* st = strise_state(e);
+    rc = upload_rows(st, cells_host, shifts_host, n_masks, g.n_elem, first, count, false, s);
     if (rc != XFR_OK) return rc;
-    std::vector<int> tab;
-    fill_rows(tab, cells_host, shifts_host, n_masks, g.n_elem, first, count, false);
-    HIP_TRY(hipMemcpyAsync(st->tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
     launch_strise_masked(probe_u8_dev, fill_dev, st->tab, st->tab + (size_t)count * g.n_elem, count, out_nchw_dev, g, e->u8_pre.mean, s);
     HIP_TRY(hipGetLastError());
     return XFR_OK;
