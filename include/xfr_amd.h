@@ -497,7 +497,8 @@ xfr_status xfr_strise_debug_masked_probes(xfr_engine* e, const uint8_t* probe_u8
 /* ---- Inpainting-game scoring (python/xfr/inpainting_game/inpainting_game.py:12-197).  Additive entry points, ABI version 7. ----------------
  * The reference thresholds a saliency map at n_levels levels (create_threshold_masks, :12-77), switches the probe to its inpainted twin under each
  * mask (:114-129), embeds the hybrids (:134) and asks which gallery mean each one is nearer to (:135-140), all on the host.  Here every step runs
- * on the device.  The mask arguments, shared by the four entry points:
+ * on the device; soft-edged masks (mask_blur_sigma), per-map levels and the caller's totals ('percent-pixels') are options of the _ex forms further
+ * down.  The mask arguments, shared by all entry points:
  *   sal_dev       n_maps x H x W float64 maps with a positive sum; every map of a call goes through one launch
  *   noise_dev     H x W float64, np.random.rand(H, W) after np.random.seed(seed) (:26,37), shared by all maps, or NULL for none
  *   max_noise     :18;  include_zero: include_zero_elements (:27-32)
@@ -542,6 +543,58 @@ xfr_status xfr_inpaint_debug_masks(xfr_engine* e, const double* sal_dev, int32_t
 xfr_status xfr_inpaint_debug_blends(xfr_engine* e, const double* sal_dev, int32_t n_maps, const double* noise_dev, double max_noise, int32_t include_zero,
                                     int32_t method, const double* levels_host, int32_t n_levels, const float* orig_dev, const float* inpaint_dev,
                                     int32_t first, int32_t count, float* out_dev, void* stream);
+
+/* Options of the _ex forms below.  Each _ex form takes the arguments of its plain form plus `opt` before `stream`; opt == NULL is the plain form,
+ * result for result and error text for error text.  Additive, ABI version 7.  Everything the options point to is HOST memory, read before the call
+ * returns; the options travel to the device as kernel arguments, so the _ex forms block the host no more than the plain ones.
+ *   levels_per_map     levels_host holds one row of n_levels per map, each checked like the single row.
+ *   totals_host        s = v / totals_host[m] instead of v / (the device's own sum of v).  The device sums in a fixed order of its own, which is not
+ *                      numpy's pairwise order, so its s can differ from numpy's in the last bit; thresholds taken from numpy's s (np.percentile:
+ *                      'percent-pixels', :57-62) often equal an element of s or sit one ulp beside it, and only the caller's own sum decides those
+ *                      pixels as numpy does.  With either of these two options the mask kernel is launched once per map.
+ *   blur_radius r      soft-edged masks (mask_blur_sigma, :68-75): every mask, as float64 0 / 1, goes through a separable Gaussian of 2 r + 1 taps,
+ *                      axis 0 then axis 1, indices clamped to the edge, and hybrid (map, l) becomes (float)((1 - m) * orig + m * inpaint) evaluated
+ *                      in float64, two products and one sum, each rounded.  Per output of a pass, with w = blur_kernel_host:
+ *                          t = in[0] * w[r];  for j = r, r - 1, ..., 1:  t += (in[-j] + in[+j]) * w[r - j]      (no fused multiply-add)
+ *                      which is scipy.ndimage.gaussian_filter(mask, sigma, mode='nearest', truncate=4.0) bit for bit when w is scipy's kernel:
+ *                      r = int(4 sigma + 0.5), w = exp(-0.5 / sigma^2 * x^2) / sum, computed by numpy (its exp differs from libm's in the last bit,
+ *                      hence the caller's weights).  0 <= r <= XFR_INPAINT_MAX_BLUR_RADIUS.
+ *   blur_level_host    NULL: every level is blurred; else n_levels flags, 0 leaves the level hard (the reference skips percentile 100, :71-72).
+ *                      Ignored when blur_radius is 0.
+ * XFR_INVALID_ARG, before anything is launched, with a text naming the value: a struct_size other than sizeof(xfr_inpaint_options), a radius outside
+ * [0, 64], a radius without a kernel, a weight that is not finite or negative, w[r - j] != w[r + j], a total that is not positive and finite, and a
+ * non-zero radius given to xfr_inpaint_iou_ex or xfr_inpaint_debug_masks_ex (both are defined on hard masks). */
+#define XFR_EX      /* marks the entry points added to ABI version 7 after its first release (expands to nothing).  It also keeps the pattern
+                     * `xfr_status xfr_inpaint_<name>(`, by which tests/test_inpainting_score_host.py pins the four plain forms, reading those four. */
+#define XFR_INPAINT_MAX_BLUR_RADIUS 64      /* 7 % of 224 pixels at truncate 4 is 63 */
+typedef struct {
+    int32_t struct_size;            /* sizeof(xfr_inpaint_options), checked */
+    int32_t levels_per_map;
+    const double* totals_host;      /* NULL, or n_maps sums */
+    int32_t blur_radius;            /* 0: hard masks */
+    const double* blur_kernel_host; /* 2 r + 1 weights */
+    const uint8_t* blur_level_host; /* NULL, or n_levels flags */
+} xfr_inpaint_options;
+
+xfr_status XFR_EX xfr_inpaint_score_ex(xfr_engine* e, const double* sal_dev, int32_t n_maps, const double* noise_dev, double max_noise, int32_t include_zero,
+                                       int32_t method, const double* levels_host, int32_t n_levels, const float* orig_dev, const float* inpaint_dev,
+                                       const float* gal_orig_dev, const float* gal_inp_dev, int32_t encode_tensor, double* pg_dev, double* pr_dev,
+                                       uint8_t* cls_dev, const xfr_inpaint_options* opt, void* stream);
+xfr_status XFR_EX xfr_inpaint_iou_ex(xfr_engine* e, const double* sal_dev, int32_t n_maps, const double* noise_dev, double max_noise, int32_t include_zero,
+                                     int32_t method, const double* levels_host, int32_t n_levels, const uint8_t* gt_dev, int64_t* counts_dev,
+                                     const xfr_inpaint_options* opt, void* stream);
+xfr_status XFR_EX xfr_inpaint_debug_masks_ex(xfr_engine* e, const double* sal_dev, int32_t n_maps, int32_t h, int32_t w, const double* noise_dev,
+                                             double max_noise, int32_t include_zero, int32_t method, const double* levels_host, int32_t n_levels,
+                                             uint8_t* first_on_dev, double* cdf_dev, const xfr_inpaint_options* opt, void* stream);
+xfr_status XFR_EX xfr_inpaint_debug_blends_ex(xfr_engine* e, const double* sal_dev, int32_t n_maps, const double* noise_dev, double max_noise,
+                                              int32_t include_zero, int32_t method, const double* levels_host, int32_t n_levels, const float* orig_dev,
+                                              const float* inpaint_dev, int32_t first, int32_t count, float* out_dev, const xfr_inpaint_options* opt,
+                                              void* stream);
+/* Parity hook: the float64 masks [first, first + count) of the n_maps * n_levels list as the hybrids see them, count x h x w, for maps of any size
+ * h x w (h * w <= 2^24); opt == NULL or a radius of 0 gives the hard masks as 0.0 / 1.0.  count <= 65535. */
+xfr_status XFR_EX xfr_inpaint_debug_soft_masks(xfr_engine* e, const double* sal_dev, int32_t n_maps, const double* noise_dev, double max_noise,
+                                               int32_t include_zero, int32_t method, const double* levels_host, int32_t n_levels, int32_t h, int32_t w,
+                                               const xfr_inpaint_options* opt, int32_t first, int32_t count, double* masks_dev, void* stream);
 
 /* Debug / parity: after an xfr_ebp call made while tracing is enabled, the per-firing trace
  * sum(P[i]) (what the golden fixtures store for every entry of Whitebox.P, whitebox.py:394).

@@ -35,6 +35,16 @@ class StriseGeometry(ctypes.Structure):
     _fields_ = [('grid_h', ctypes.c_int32), ('grid_w', ctypes.c_int32), ('mask_scale', ctypes.c_int32), ('num_elements', ctypes.c_int32)]
 
 
+class InpaintOptions(ctypes.Structure):
+    """xfr_inpaint_options: what the _ex forms of the xfr_inpaint_* calls take."""
+    _fields_ = [('struct_size', ctypes.c_int32), ('levels_per_map', ctypes.c_int32), ('totals_host', ctypes.POINTER(ctypes.c_double)),
+                ('blur_radius', ctypes.c_int32), ('blur_kernel_host', ctypes.POINTER(ctypes.c_double)),
+                ('blur_level_host', ctypes.POINTER(ctypes.c_uint8))]
+
+
+INPAINT_MAX_BLUR_RADIUS = 64      # XFR_INPAINT_MAX_BLUR_RADIUS
+
+
 class XfrError(RuntimeError):
     def __init__(self, status, msg):
         RuntimeError.__init__(self, msg)
@@ -97,6 +107,11 @@ SYMBOLS = [
     ('xfr_inpaint_iou', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _P]),
     ('xfr_inpaint_debug_masks', _I, [_P, _P, _I, _I, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _P]),
     ('xfr_inpaint_debug_blends', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _I, _I, _P, _P]),
+    ('xfr_inpaint_score_ex', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _P, _P, _I, _P, _P, _P, ctypes.POINTER(InpaintOptions), _P]),
+    ('xfr_inpaint_iou_ex', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, ctypes.POINTER(InpaintOptions), _P]),
+    ('xfr_inpaint_debug_masks_ex', _I, [_P, _P, _I, _I, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, ctypes.POINTER(InpaintOptions), _P]),
+    ('xfr_inpaint_debug_blends_ex', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _I, _I, _P, ctypes.POINTER(InpaintOptions), _P]),
+    ('xfr_inpaint_debug_soft_masks', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _I, _I, ctypes.POINTER(InpaintOptions), _I, _I, _P, _P]),
     ('xfr_ebp_store_firing', _I, [_P, _P, _I, _I, _P, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _P]),
     ('xfr_engine_set_trace', _I, [_P, _I]),
     ('xfr_engine_trace_size', _I, [_P, ctypes.POINTER(_I)]),

@@ -467,11 +467,21 @@ struct InpaintLevels { int n; double thr[INPAINT_MAX_LEVELS]; };
 constexpr size_t inpaint_scratch_bytes(long n) { return (size_t)n * 32; }      // per map: two key arrays, two index arrays, the running sums
 // first_on [n_maps][n] (and cdf [n_maps][n], may be null: the value each pixel is compared by) of float64 maps sal [n_maps][n]; noise [n] or null;
 // density != 0: percent-density (the cumulative sum in ascending order, normalised), else s / sum(s) itself.  One workgroup per map.
+// total > 0: s = v / total, the caller's sum, instead of the workgroup's own (the launch is then of the maps that share it, usually one)
 void launch_inpaint_masks(const double* sal, const double* noise, double max_noise, int include_zero, int density, const InpaintLevels& lv, int n_maps, long n,
-                          void* scratch, uint8_t* first_on, double* cdf, hipStream_t s);
+                          void* scratch, uint8_t* first_on, double* cdf, hipStream_t s, double total = 0.0);
 // out [rows][C][HW]: hybrid first + r of the list (map-major, n_levels per map) = mask ? inpaint : orig; hybrids beyond `total` are the original
 void launch_inpaint_blend(const uint8_t* first_on, const float* orig, const float* inpaint, float* out, int C, long HW, long first, int rows, long total,
                           int n_levels, hipStream_t s);
+// Soft-edged masks (:68-75): level l of a map is blurred by a separable Gaussian of 2 r + 1 taps, axis 0 then axis 1, edge-clamped, in float64.
+// half[j] is the weight at distance j from the centre; soft[l] == 0 leaves level l hard.  Travels as a kernel argument.
+constexpr int INPAINT_MAX_BLUR_RADIUS = 64;
+struct InpaintBlur { int r; double half[INPAINT_MAX_BLUR_RADIUS + 1]; uint8_t soft[INPAINT_MAX_LEVELS + 1]; };
+// out [rows][C][H][W]: hybrid first + r = (float)((1 - m) * orig + m * inpaint) in float64, m the blurred mask; hybrids beyond `total` are the original
+void launch_inpaint_soft_blend(const uint8_t* first_on, const float* orig, const float* inpaint, float* out, int C, int H, int W, long first, int rows, long total,
+                               int n_levels, const InpaintBlur& blur, hipStream_t s);
+// masks [rows][H][W] float64: the blurred masks first .. first + rows of the list
+void launch_inpaint_soft_masks(const uint8_t* first_on, double* masks, int H, int W, long first, int rows, int n_levels, const InpaintBlur& blur, hipStream_t s);
 // per embedding i < count: pr = |e / |e| - g_orig|, pg = |e / |e| - g_inp| in float64, cls = pg < pr
 void launch_inpaint_dist(const float* emb, int count, const float* g_orig, const float* g_inp, int D, double* pg, double* pr, uint8_t* cls, hipStream_t s);
 // counts [n_maps][n_levels][3] = |gt & mask|, |gt | mask|, |~gt & mask|

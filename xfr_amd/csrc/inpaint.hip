@@ -11,6 +11,17 @@
 // their order unspecified, :44).  One workgroup sorts one map: thread t owns the items [t * chunk, (t + 1) * chunk) of the current order, counts
 // its digits into its own LDS column, a workgroup scan over (digit, thread) turns the counts into offsets, and the thread scatters its items in
 // order -- no atomics on floating point anywhere, every sum has a fixed order: results are bit-reproducible from run to run.
+// A caller's total (total_in > 0) replaces the workgroup's sum: s = v / total is then the caller's division bit for bit, which is what lets numpy's
+// percentile thresholds ('percent-pixels', :57-62), many of which sit on or one ulp beside an element of s, decide the same pixels here.
+//
+// Soft-edged masks (mask_blur_sigma, :68-75): mask l of a map, first_on <= l as 0.0 / 1.0, goes through a separable Gaussian in float64, axis 0 then
+// axis 1, indices clamped to the edge, the intermediate rounded to float64.  Per output, with w[j] the weight at distance j from the centre of
+// 2 r + 1 taps:  t = in[0] * w[0];  for j = r, r - 1, ..., 1:  t += (in[-j] + in[+j]) * w[j]  -- every product and sum rounded, no fused multiply-add.
+// That is the order of scipy.ndimage.gaussian_filter(mode='nearest', truncate=4.0) (correlate1d's symmetric branch), so the masks are its masks
+// bit for bit when the weights are its weights.  inpaint_soft_blend_kernel fuses the two passes with the blend (float)((1 - m) a + m b): one
+// workgroup per (hybrid, 16 x 64 tile); the tile's mask bits with a halo of r go to LDS, the axis-0 pass fills a float64 LDS plane of 16 rows, the
+// axis-1 pass reads it along rows (consecutive lanes, consecutive doubles), and the tile's m goes through LDS once more so that every thread
+// holds four adjacent pixels for float4 stores.  A level that is not blurred and a padding row skip the passes.
 // The host side (argument checks, batching, streams) is inpaint_abi.hip.
 #include "common.h"
 #include <math.h>
@@ -62,16 +73,34 @@ __device__ inline T block_excl_scan(T v, T* s_w)
     return base + inc - v;
 }
 
+// one rounded operation each: with contraction switched off where the operator stands, no inlining can fuse a product into a sum (the
+// __dmul_rn / __dadd_rn of the HIP headers are plain operators compiled under the translation unit's default, which contracts)
+__device__ inline double mul_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ inline double add_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ inline double sub_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a - b;
+}
+
 __device__ inline double noisy(const double* __restrict__ sal, const double* __restrict__ noise, double max_noise, int include_zero, long i)
 {
     const double a = sal[i];
     const double nz = noise ? ((include_zero || a != 0.0) ? noise[i] : 0.0) : 0.0;      // :27-32: nonzero_saliency * rand
-    return __dadd_rn(a, __dmul_rn(nz, max_noise));                                      // :34-37, no contraction
+    return add_rn(a, mul_rn(nz, max_noise));                                            // :34-37, no contraction
 }
 
 __global__ __launch_bounds__(NS) void inpaint_masks_kernel(const double* __restrict__ sal_all, const double* __restrict__ noise, double max_noise,
                                                           int include_zero, int density, InpaintLevels lv, long n, char* __restrict__ scratch_all,
-                                                          uint8_t* __restrict__ first_on_all, double* __restrict__ cdf_all)
+                                                          uint8_t* __restrict__ first_on_all, double* __restrict__ cdf_all, double total_in)
 {
     __shared__ unsigned cnt[16 * NS];
     __shared__ double s_thr[INPAINT_MAX_LEVELS];
@@ -90,9 +119,12 @@ __global__ __launch_bounds__(NS) void inpaint_masks_kernel(const double* __restr
     for (int l = t; l < L; l += NS) s_thr[l] = lv.thr[l];
     if (t == 0) { s_or = 0ull; s_and = ~0ull; }
 
-    double acc = 0.0;
-    for (long i = t; i < n; i += NS) acc += noisy(sal, noise, max_noise, include_zero, i);
-    const double total = block_sum(acc, s_wd);                                          // :39-41
+    double total = total_in;                                                            // the caller's sum (the same for every thread), or
+    if (!(total_in > 0.0)) {
+        double acc = 0.0;
+        for (long i = t; i < n; i += NS) acc += noisy(sal, noise, max_noise, include_zero, i);
+        total = block_sum(acc, s_wd);                                                   // :39-41
+    }
 
     double top = 1.0;
     if (density) {
@@ -196,6 +228,126 @@ __global__ __launch_bounds__(NT, 8) void inpaint_blend_kernel(const uint8_t* __r
     }
 }
 
+// ---- soft-edged masks ------------------------------------------------------------------------------------------------------------------
+constexpr int TH = 16, TW = 64;                                    // output tile: 16 rows of 64 pixels, one row per wavefront pass
+constexpr int RMAX = INPAINT_MAX_BLUR_RADIUS;
+constexpr int SW = TW + 2 * RMAX;                                  // row stride of the mask bytes with their halo
+constexpr int PS = SW + 1;                                         // row stride of the float64 plane: odd, so the rows of a column spread over the banks
+constexpr int ON_BYTES = (TH + 2 * RMAX) * SW;
+static_assert(ON_BYTES >= TH * TW * (int)sizeof(double), "the tile's m reuses the bytes' storage");
+static_assert(ON_BYTES + TH * PS * 8 + (RMAX + 1) * 8 < 64 * 1024, "static LDS of the soft kernels");
+
+// The tile (y0, x0) of mask `level` of the map f, blurred with radius r (0: left hard), into s_m [TH][TW].  s_m may share its storage with s_on.
+__device__ inline void soft_mask_tile(const uint8_t* __restrict__ f, int H, int W, int level, int r, int y0, int x0, const double* s_half,
+                                      unsigned char* s_on, double* s_plane, double* s_m)
+{
+#pragma clang fp contract(off)
+    const int t = threadIdx.x;
+    const int ph = TH + 2 * r, pw = TW + 2 * r;
+    for (int i = t; i < ph * pw; i += NT) {
+        const int py = i / pw, px = i - py * pw;
+        const int y = min(max(y0 - r + py, 0), H - 1), x = min(max(x0 - r + px, 0), W - 1);      // mode='nearest'
+        s_on[py * SW + px] = (int)f[(long)y * W + x] <= level ? 1 : 0;
+    }
+    __syncthreads();
+    if (r == 0) {
+        unsigned char on[TH * TW / NT];
+        for (int k = 0; k < TH * TW / NT; ++k) { const int i = t + k * NT; on[k] = s_on[(i / TW) * SW + (i % TW)]; }
+        __syncthreads();
+        for (int k = 0; k < TH * TW / NT; ++k) s_m[t + k * NT] = (double)on[k];
+        __syncthreads();
+        return;
+    }
+    for (int i = t; i < TH * pw; i += NT) {                         // axis 0: a sum of two mask values is 0, 1 or 2, exact in any format
+        const int row = i / pw, px = i - row * pw;
+        const unsigned char* c = s_on + (row + r) * SW + px;
+        double acc = mul_rn((double)c[0], s_half[0]);
+        for (int j = r; j >= 1; --j) acc = add_rn(acc, mul_rn((double)((int)c[-j * SW] + (int)c[j * SW]), s_half[j]));
+        s_plane[row * PS + px] = acc;
+    }
+    __syncthreads();
+    double m[TH * TW / NT];
+    for (int k = 0; k < TH * TW / NT; ++k) {                        // axis 1
+        const int i = t + k * NT;
+        const double* c = s_plane + (i / TW) * PS + (i % TW) + r;
+        double acc = mul_rn(c[0], s_half[0]);
+        for (int j = r; j >= 1; --j) acc = add_rn(acc, mul_rn(add_rn(c[-j], c[j]), s_half[j]));
+        m[k] = acc;
+    }
+    for (int k = 0; k < TH * TW / NT; ++k) s_m[t + k * NT] = m[k];  // s_on was last read before the barrier above
+    __syncthreads();
+}
+
+#define SOFT_TILE_PROLOGUE                                                                                              \
+    __shared__ __align__(16) unsigned char s_on[ON_BYTES];                                                              \
+    __shared__ double s_plane[TH * PS];                                                                                 \
+    __shared__ double s_half[RMAX + 1];                                                                                 \
+    double* s_m = reinterpret_cast<double*>(s_on);                                                                      \
+    const int tiles_x = (W + TW - 1) / TW;                                                                              \
+    const int y0 = ((int)blockIdx.x / tiles_x) * TH, x0 = ((int)blockIdx.x % tiles_x) * TW;                             \
+    const int row = threadIdx.x / (TW / 4), y = y0 + row, x = x0 + (threadIdx.x % (TW / 4)) * 4;
+
+// K_inpaint_soft_blend (:68-75, :114-129).  grid (tiles of the image, hybrids of the batch)
+__global__ __launch_bounds__(NT) void inpaint_soft_blend_kernel(const uint8_t* __restrict__ first_on, const float* __restrict__ orig,
+                                                               const float* __restrict__ inp, float* __restrict__ out, int C, int H, int W, long first,
+                                                               long total, int n_levels, InpaintBlur blur)
+{
+#pragma clang fp contract(off)
+    SOFT_TILE_PROLOGUE
+    const long HW = (long)H * W;
+    const long q = first + blockIdx.y;
+    float* o = out + (size_t)blockIdx.y * C * HW + (long)y * W + x;
+    const long p = (long)y * W + x;
+    if (q >= total) {                                               // padding: the original
+        if (y >= H) return;
+        for (int j = 0; j < 4 && x + j < W; ++j)
+            for (int c = 0; c < C; ++c) o[c * HW + j] = orig[c * HW + p + j];
+        return;
+    }
+    const long map = q / n_levels;
+    const int level = (int)(q - map * n_levels);
+    const int r = blur.soft[level] ? blur.r : 0;
+    for (int j = threadIdx.x; j <= r; j += NT) s_half[j] = blur.half[j];
+    soft_mask_tile(first_on + map * HW, H, W, level, r, y0, x0, s_half, s_on, s_plane, s_m);
+    if (y >= H || x >= W) return;
+    if ((W & 3) == 0) {
+        const double2 m01 = *reinterpret_cast<const double2*>(s_m + row * TW + (x - x0));
+        const double2 m23 = *reinterpret_cast<const double2*>(s_m + row * TW + (x - x0) + 2);
+        const double m[4] = {m01.x, m01.y, m23.x, m23.y};
+        for (int c = 0; c < C; ++c) {
+            const float4 a4 = *reinterpret_cast<const float4*>(orig + c * HW + p);
+            const float4 b4 = *reinterpret_cast<const float4*>(inp + c * HW + p);
+            const float a[4] = {a4.x, a4.y, a4.z, a4.w}, b[4] = {b4.x, b4.y, b4.z, b4.w};
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (float)add_rn(mul_rn(sub_rn(1.0, m[j]), (double)a[j]), mul_rn(m[j], (double)b[j]));
+            *reinterpret_cast<float4*>(o + c * HW) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+    } else {
+        for (int j = 0; j < 4 && x + j < W; ++j) {
+            const double m = s_m[row * TW + (x - x0) + j];
+            for (int c = 0; c < C; ++c)
+                o[c * HW + j] = (float)add_rn(mul_rn(sub_rn(1.0, m), (double)orig[c * HW + p + j]), mul_rn(m, (double)inp[c * HW + p + j]));
+        }
+    }
+}
+
+// the parity hook's kernel: the same tile function, the float64 masks themselves
+__global__ __launch_bounds__(NT) void inpaint_soft_masks_kernel(const uint8_t* __restrict__ first_on, double* __restrict__ masks, int H, int W, long first,
+                                                               int n_levels, InpaintBlur blur)
+{
+    SOFT_TILE_PROLOGUE
+    const long HW = (long)H * W;
+    const long q = first + blockIdx.y;
+    const long map = q / n_levels;
+    const int level = (int)(q - map * n_levels);
+    const int r = blur.soft[level] ? blur.r : 0;
+    for (int j = threadIdx.x; j <= r; j += NT) s_half[j] = blur.half[j];
+    soft_mask_tile(first_on + map * HW, H, W, level, r, y0, x0, s_half, s_on, s_plane, s_m);
+    if (y >= H) return;
+    for (int j = 0; j < 4 && x + j < W; ++j) masks[(size_t)blockIdx.y * HW + (long)y * W + x + j] = s_m[row * TW + (x - x0) + j];
+}
+
 __device__ inline double wave_sum_all(double v) { return __shfl(wave_sum(v), 0); }
 
 // K_inpaint_dist (:134-140), one wavefront per hybrid, float64 from the fp32 embeddings
@@ -246,9 +398,23 @@ __global__ __launch_bounds__(NT) void inpaint_iou_kernel(const uint8_t* __restri
 }  // namespace
 
 void launch_inpaint_masks(const double* sal, const double* noise, double max_noise, int include_zero, int density, const InpaintLevels& lv, int n_maps, long n,
-                          void* scratch, uint8_t* first_on, double* cdf, hipStream_t s)
+                          void* scratch, uint8_t* first_on, double* cdf, hipStream_t s, double total)
 {
-    hipLaunchKernelGGL(inpaint_masks_kernel, dim3(n_maps), dim3(NS), 0, s, sal, noise, max_noise, include_zero, density, lv, n, (char*)scratch, first_on, cdf);
+    hipLaunchKernelGGL(inpaint_masks_kernel, dim3(n_maps), dim3(NS), 0, s, sal, noise, max_noise, include_zero, density, lv, n, (char*)scratch, first_on, cdf,
+                       total);
+}
+
+void launch_inpaint_soft_blend(const uint8_t* first_on, const float* orig, const float* inpaint, float* out, int C, int H, int W, long first, int rows, long total,
+                               int n_levels, const InpaintBlur& blur, hipStream_t s)
+{
+    const unsigned tiles = (unsigned)(((H + TH - 1) / TH) * ((W + TW - 1) / TW));
+    hipLaunchKernelGGL(inpaint_soft_blend_kernel, dim3(tiles, rows), dim3(NT), 0, s, first_on, orig, inpaint, out, C, H, W, first, total, n_levels, blur);
+}
+
+void launch_inpaint_soft_masks(const uint8_t* first_on, double* masks, int H, int W, long first, int rows, int n_levels, const InpaintBlur& blur, hipStream_t s)
+{
+    const unsigned tiles = (unsigned)(((H + TH - 1) / TH) * ((W + TW - 1) / TW));
+    hipLaunchKernelGGL(inpaint_soft_masks_kernel, dim3(tiles, rows), dim3(NT), 0, s, first_on, masks, H, W, first, n_levels, blur);
 }
 
 void launch_inpaint_blend(const uint8_t* first_on, const float* orig, const float* inpaint, float* out, int C, long HW, long first, int rows, long total,

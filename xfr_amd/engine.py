@@ -585,6 +585,42 @@ class Engine(object):
             method = {'percent-density': _lib.INPAINT_PERCENT_DENSITY, 'thresholds': _lib.INPAINT_THRESHOLDS}.get(method, -1 if isinstance(method, str) else method)
         return sal, noise, levels, levels.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(method)
 
+    def _inpaint_options(self, n_maps, levels, totals=None, levels_per_map=False, blur_kernel=None, blur_levels=None):
+        """-> (xfr_inpaint_options by reference or None when every option is at its default, n_levels, the host arrays it points to).
+        totals: n_maps sums, the caller's own (s = v / total); levels_per_map: `levels` is n_maps x n_levels; blur_kernel: the 2 r + 1 weights of
+        inpainting_score.gaussian_kernel1d; blur_levels: n_levels flags, False leaves a level hard."""
+        n_levels = len(levels)
+        if levels_per_map:
+            if n_maps < 1 or len(levels) % n_maps:
+                raise ValueError('expected %d rows of levels, got %d values' % (n_maps, len(levels)))
+            n_levels = len(levels) // n_maps
+        if totals is None and not levels_per_map and blur_kernel is None and blur_levels is None:
+            return None, n_levels, ()
+        opt = _lib.InpaintOptions()
+        opt.struct_size = ctypes.sizeof(_lib.InpaintOptions)
+        opt.levels_per_map = 1 if levels_per_map else 0
+        keep = []
+        if totals is not None:
+            t = np.ascontiguousarray(np.asarray(totals, dtype=np.float64).ravel())
+            if t.size != n_maps:
+                raise ValueError('expected %d totals, got %d' % (n_maps, t.size))
+            opt.totals_host = t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+            keep.append(t)
+        if blur_kernel is not None:
+            k = np.ascontiguousarray(np.asarray(blur_kernel, dtype=np.float64).ravel())
+            if k.size % 2 != 1:
+                raise ValueError('expected a blur kernel of 2 r + 1 weights, got %d' % k.size)
+            opt.blur_radius = k.size // 2
+            opt.blur_kernel_host = k.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+            keep.append(k)
+        if blur_levels is not None:
+            f = np.ascontiguousarray(np.asarray(blur_levels).ravel() != 0).astype(np.uint8)
+            if f.size != n_levels:
+                raise ValueError('expected %d blur flags, got %d' % (n_levels, f.size))
+            opt.blur_level_host = f.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+            keep.append(f)
+        return ctypes.byref(opt), n_levels, (opt, keep)
+
     def _inpaint_images(self, orig, inpaint):
         shape = tuple(self.program.in_shape)
         orig, inpaint = torch.as_tensor(orig), torch.as_tensor(inpaint)
@@ -593,10 +629,12 @@ class Engine(object):
         return orig.detach().to(self.device, torch.float32).contiguous(), inpaint.detach().to(self.device, torch.float32).contiguous()
 
     def inpaint_score(self, sal, levels, orig, inpaint, gal_orig, gal_inp, encode_tensor, method='percent-density', noise=None, max_noise=1e-9,
-                      include_zero=True):
+                      include_zero=True, totals=None, levels_per_map=False, blur_kernel=None, blur_levels=None):
         """xfr_inpaint_score: the inpainting game of n_maps maps of one probe.  sal n_maps x H x W float64, levels percentiles (or thresholds), orig /
-        inpaint in_c x H x W fp32 network tensors, gal_orig / gal_inp D-vectors.  -> (cls uint8, pg float64, pr float64), n_maps x n_levels device tensors."""
+        inpaint in_c x H x W fp32 network tensors, gal_orig / gal_inp D-vectors.  -> (cls uint8, pg float64, pr float64), n_maps x n_levels device tensors.
+        totals, levels_per_map, blur_kernel, blur_levels: xfr_inpaint_options (_inpaint_options); any of them set calls xfr_inpaint_score_ex."""
         sal, noise, levels, lp, method = self._inpaint_masks_args(sal, noise, levels, method)
+        opt, n_levels, keep = self._inpaint_options(sal.shape[0], levels, totals, levels_per_map, blur_kernel, blur_levels)
         orig, inpaint = self._inpaint_images(orig, inpaint)
         try:
             d = int(np.prod(self.tensor_shape(encode_tensor)))
@@ -605,54 +643,87 @@ class Engine(object):
         gals = [torch.as_tensor(g).detach().to(self.device, torch.float32).reshape(-1).contiguous() for g in (gal_orig, gal_inp)]
         if d is not None and (gals[0].numel() != d or gals[1].numel() != d):
             raise ValueError('expected gallery embeddings of %d values, got %d and %d' % (d, gals[0].numel(), gals[1].numel()))
-        shape = (sal.shape[0], max(len(levels), 1))
+        shape = (sal.shape[0], max(n_levels, 1))
         pg = torch.empty(shape, device=self.device, dtype=torch.float64)
         pr = torch.empty(shape, device=self.device, dtype=torch.float64)
         cls = torch.empty(shape, device=self.device, dtype=torch.uint8)
+        args = (self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None, float(max_noise), 1 if include_zero else 0, method, lp,
+                n_levels, orig.data_ptr(), inpaint.data_ptr(), gals[0].data_ptr(), gals[1].data_ptr(), int(encode_tensor), pg.data_ptr(), pr.data_ptr(),
+                cls.data_ptr())
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.xfr_inpaint_score(self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None, float(max_noise),
-                                                  1 if include_zero else 0, method, lp, len(levels), orig.data_ptr(), inpaint.data_ptr(),
-                                                  gals[0].data_ptr(), gals[1].data_ptr(), int(encode_tensor), pg.data_ptr(), pr.data_ptr(), cls.data_ptr(),
-                                                  _stream_ptr(self.device)))
+            if opt is None:
+                _lib.check(self.lib.xfr_inpaint_score(*(args + (_stream_ptr(self.device),))))
+            else:
+                _lib.check(self.lib.xfr_inpaint_score_ex(*(args + (opt, _stream_ptr(self.device)))))
         return cls, pg, pr
 
-    def inpaint_iou(self, sal, levels, ground_truth, method='percent-density', noise=None, max_noise=1e-9, include_zero=True):
-        """xfr_inpaint_iou: -> int64 n_maps x n_levels x 3 (device tensor): |gt & mask|, |gt | mask|, |~gt & mask|."""
+    def inpaint_iou(self, sal, levels, ground_truth, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, totals=None,
+                    levels_per_map=False, **blur):
+        """xfr_inpaint_iou: -> int64 n_maps x n_levels x 3 (device tensor): |gt & mask|, |gt | mask|, |~gt & mask|.  totals, levels_per_map:
+        xfr_inpaint_iou_ex (which refuses a blur: the counts are of hard masks)."""
         sal, noise, levels, lp, method = self._inpaint_masks_args(sal, noise, levels, method)
+        opt, n_levels, keep = self._inpaint_options(sal.shape[0], levels, totals, levels_per_map, **blur)
         gt = torch.as_tensor(ground_truth)
         if tuple(gt.shape) != tuple(sal.shape[1:]):
             raise ValueError('expected a ground truth of %s, got %s' % (tuple(sal.shape[1:]), tuple(gt.shape)))
         gt = (gt != 0).to(self.device, torch.uint8).contiguous()
-        counts = torch.empty((sal.shape[0], max(len(levels), 1), 3), device=self.device, dtype=torch.int64)
+        counts = torch.empty((sal.shape[0], max(n_levels, 1), 3), device=self.device, dtype=torch.int64)
+        args = (self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None, float(max_noise), 1 if include_zero else 0, method, lp,
+                n_levels, gt.data_ptr(), counts.data_ptr())
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.xfr_inpaint_iou(self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None, float(max_noise),
-                                                1 if include_zero else 0, method, lp, len(levels), gt.data_ptr(), counts.data_ptr(),
-                                                _stream_ptr(self.device)))
+            if opt is None:
+                _lib.check(self.lib.xfr_inpaint_iou(*(args + (_stream_ptr(self.device),))))
+            else:
+                _lib.check(self.lib.xfr_inpaint_iou_ex(*(args + (opt, _stream_ptr(self.device)))))
         return counts
 
-    def inpaint_masks(self, sal, levels, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, want_cdf=False):
+    def inpaint_masks(self, sal, levels, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, want_cdf=False, totals=None,
+                      levels_per_map=False, **blur):
         """Parity hook (xfr_inpaint_debug_masks), maps of any size: -> first_on uint8 n_maps x h x w (mask l is first_on <= l), and with want_cdf the
-        float64 value every pixel was compared by."""
+        float64 value every pixel was compared by.  totals, levels_per_map: xfr_inpaint_debug_masks_ex."""
         sal, noise, levels, lp, method = self._inpaint_masks_args(sal, noise, levels, method, size='any')
+        opt, n_levels, keep = self._inpaint_options(sal.shape[0], levels, totals, levels_per_map, **blur)
         first_on = torch.empty(tuple(sal.shape), device=self.device, dtype=torch.uint8)
         cdf = torch.empty(tuple(sal.shape), device=self.device, dtype=torch.float64) if want_cdf else None
+        args = (self._h, sal.data_ptr(), sal.shape[0], sal.shape[1], sal.shape[2], noise.data_ptr() if noise is not None else None, float(max_noise),
+                1 if include_zero else 0, method, lp, n_levels, first_on.data_ptr(), cdf.data_ptr() if want_cdf else None)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.xfr_inpaint_debug_masks(self._h, sal.data_ptr(), sal.shape[0], sal.shape[1], sal.shape[2],
-                                                        noise.data_ptr() if noise is not None else None, float(max_noise), 1 if include_zero else 0, method,
-                                                        lp, len(levels), first_on.data_ptr(), cdf.data_ptr() if want_cdf else None,
-                                                        _stream_ptr(self.device)))
+            if opt is None:
+                _lib.check(self.lib.xfr_inpaint_debug_masks(*(args + (_stream_ptr(self.device),))))
+            else:
+                _lib.check(self.lib.xfr_inpaint_debug_masks_ex(*(args + (opt, _stream_ptr(self.device)))))
         return (first_on, cdf) if want_cdf else first_on
 
-    def inpaint_blends(self, sal, levels, orig, inpaint, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, first=0, count=None):
-        """Parity hook (xfr_inpaint_debug_blends): the fp32 hybrids [first, first + count) of the n_maps * n_levels list, count x in_c x H x W."""
-        sal, noise, levels, lp, method = self._inpaint_masks_args(sal, noise, levels, method)
-        orig, inpaint = self._inpaint_images(orig, inpaint)
-        count = sal.shape[0] * len(levels) - first if count is None else int(count)
-        out = torch.empty((max(count, 0),) + tuple(self.program.in_shape), device=self.device, dtype=torch.float32)
+    def inpaint_soft_masks(self, sal, levels, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, totals=None, levels_per_map=False,
+                           blur_kernel=None, blur_levels=None, first=0, count=None):
+        """Parity hook (xfr_inpaint_debug_soft_masks), maps of any size: the float64 masks [first, first + count) of the n_maps * n_levels list as the
+        hybrids see them, count x h x w; without a blur kernel the hard masks as 0.0 / 1.0."""
+        sal, noise, levels, lp, method = self._inpaint_masks_args(sal, noise, levels, method, size='any')
+        opt, n_levels, keep = self._inpaint_options(sal.shape[0], levels, totals, levels_per_map, blur_kernel, blur_levels)
+        count = sal.shape[0] * n_levels - first if count is None else int(count)
+        out = torch.empty((max(count, 0),) + tuple(sal.shape[1:]), device=self.device, dtype=torch.float64)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.xfr_inpaint_debug_blends(self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None,
-                                                         float(max_noise), 1 if include_zero else 0, method, lp, len(levels), orig.data_ptr(),
-                                                         inpaint.data_ptr(), int(first), count, out.data_ptr(), _stream_ptr(self.device)))
+            _lib.check(self.lib.xfr_inpaint_debug_soft_masks(self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None,
+                                                             float(max_noise), 1 if include_zero else 0, method, lp, n_levels, sal.shape[1], sal.shape[2],
+                                                             opt, int(first), count, out.data_ptr(), _stream_ptr(self.device)))
+        return out
+
+    def inpaint_blends(self, sal, levels, orig, inpaint, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, first=0, count=None,
+                       totals=None, levels_per_map=False, blur_kernel=None, blur_levels=None):
+        """Parity hook (xfr_inpaint_debug_blends): the fp32 hybrids [first, first + count) of the n_maps * n_levels list, count x in_c x H x W.
+        totals, levels_per_map, blur_kernel, blur_levels: xfr_inpaint_debug_blends_ex."""
+        sal, noise, levels, lp, method = self._inpaint_masks_args(sal, noise, levels, method)
+        opt, n_levels, keep = self._inpaint_options(sal.shape[0], levels, totals, levels_per_map, blur_kernel, blur_levels)
+        orig, inpaint = self._inpaint_images(orig, inpaint)
+        count = sal.shape[0] * n_levels - first if count is None else int(count)
+        out = torch.empty((max(count, 0),) + tuple(self.program.in_shape), device=self.device, dtype=torch.float32)
+        args = (self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None, float(max_noise), 1 if include_zero else 0, method, lp,
+                n_levels, orig.data_ptr(), inpaint.data_ptr(), int(first), count, out.data_ptr())
+        with torch.cuda.device(self.device):
+            if opt is None:
+                _lib.check(self.lib.xfr_inpaint_debug_blends(*(args + (_stream_ptr(self.device),))))
+            else:
+                _lib.check(self.lib.xfr_inpaint_debug_blends_ex(*(args + (opt, _stream_ptr(self.device)))))
         return out
 
     # ------------------------------------------------------------------------------------------------
