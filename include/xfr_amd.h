@@ -596,6 +596,61 @@ xfr_status XFR_EX xfr_inpaint_debug_soft_masks(xfr_engine* e, const double* sal_
                                                int32_t include_zero, int32_t method, const double* levels_host, int32_t n_levels, int32_t h, int32_t w,
                                                const xfr_inpaint_options* opt, int32_t first, int32_t count, double* masks_dev, void* stream);
 
+/* ---- STRise for the generator's black box (eval/generate_inpaintinggame_bb_saliency_maps_multigpu.py:69-113,
+ * python/xfr/inpainting_game/generate_blackbox_saliency.py:48-73).  Additive entry points, ABI version 7. -----------------------------------
+ * The reference's own evaluation never uses the named black box: its bb_fn (:73-101) sends every masked probe v = mask * probe + (1 - mask) * fill
+ * (blackbox.py:343) through Whitebox.convert_from_numpy (whitebox.py:787-806) of whichever network create_wbnet returned:
+ *     q = uint8((v / 255) * 255)                         (:794-795,803; the conversion truncates; the resize of :802 is the identity at 224 x 224)
+ *     XFR_U8_SUB_MEAN   (float)((double)q - mean[c])     (ResNet-101: whitebox.py:108-110, resnet.py:25-37; ResNet-50-128d: whitebox.py:235-258)
+ *     XFR_U8_LUMINANCE  PIL's bilinear Resize + CenterCrop of q, then (float)((r/255) w0 + (g/255) w1 + (b/255) w2)     (Light-CNN: lightcnn.py:19-31)
+ * quantize = 1 selects that chain.  Truncation makes q depend on the last bit of the mask, so under quantize = 1 (and `exact` of the mask hook) the
+ * mask is scipy.ndimage.zoom(order=1, mode='mirror', grid_mode=True) TO THE BIT, every operation rounded to float64 and none contracted:
+ *     cc = ((o + 0.5) * ratio) - 0.5, ratio = g / (n + mask_scale);  c = cc < 0 ? -cc : cc;  st = floor(c);  w0 = 1 - (c - st);  w1 = 1 - w0;
+ *     taps st and st + 1, the second folded at g - 1 (g == 1: tap 0 with weight 1);  mask = (((0 + (G00 wy0) wx0) + (G01 wy0) wx1) + (G10 wy1) wx0) + (G11 wy1) wx1
+ * Image zero of the sweep (the unmasked probe) and the padding rows take q = probe: uint8((k / 255) * 255) == k for every level, and an all-ones
+ * grid under the exact law is not 1 everywhere.
+ * PIL's 8-bit bilinear resize (Pillow 12, Resample.c) is two integer passes, the horizontal one first, each output clip8((2^21 + sum_t pixel[first + t] *
+ * coef[t]) >> 22); the caller supplies the tap tables of the rows and columns THE CROP KEEPS (xfr_amd.models.blackbox.pil_bilinear_tables). */
+#define XFR_STRISE_MAX_TAPS 8
+typedef struct {
+    int32_t first, count;               /* pixels [first, first + count) of the probe's axis; 1 <= count <= XFR_STRISE_MAX_TAPS */
+    int32_t coef[XFR_STRISE_MAX_TAPS];  /* weights in 2^-22, each >= 0; 255 * their sum + 2^21 must fit in int32 */
+} xfr_strise_tap;
+
+typedef struct {
+    int32_t struct_size;                /* sizeof(xfr_strise_options), checked */
+    int32_t probe_h, probe_w;           /* size of the probe, the fill and the masks (no longer the engine's input size) */
+    int32_t quantize;                   /* 0: the arithmetic of xfr_strise_score; 1: the chain above */
+    const xfr_strise_tap* row_tab;      /* HOST, in_h entries; XFR_U8_LUMINANCE engines under quantize = 1 only, else may be NULL */
+    const xfr_strise_tap* col_tab;      /* HOST, in_w entries */
+} xfr_strise_options;
+
+/* The calls above with options; opt == NULL is the call above itself (the engine's input size, quantize 0, the closed-form mask law): the same
+ * code path, results equal to the bit.  XFR_INVALID_ARG before anything is launched, with a text naming the cause, for: a struct_size other than
+ * sizeof(xfr_strise_options); quantize outside {0, 1}; quantize = 1 on an engine without xfr_engine_set_u8_preprocess; an XFR_U8_SUB_MEAN engine
+ * (or quantize = 0) whose input size is not probe_h x probe_w; an XFR_U8_LUMINANCE engine without tables; a table entry with count outside
+ * [1, XFR_STRISE_MAX_TAPS], a window outside the probe, a negative coefficient or a coefficient sum that overflows int32; a band of 16 output rows whose
+ * probe rows do not fit the kernel's 60 KB of LDS; and everything the calls above refuse, against probe_h x probe_w.
+ * xfr_strise_combine_ex keeps the closed-form law (the map's bar is 1e-6, the laws differ by 2e-16): options only free it from the engine's input size. */
+xfr_status XFR_EX xfr_strise_score_ex(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host, const int32_t* shifts_host,
+                               int32_t n_masks, const xfr_strise_geometry* geom, const float* refs_dev, int32_t n_refs, const float* gallery_dev,
+                               int32_t n_gal, int32_t encode_tensor, double* scores_dev, double* orig_dev, const xfr_strise_options* opt, void* stream);
+xfr_status XFR_EX xfr_strise_combine_ex(xfr_engine* e, const double* weights_dev, int32_t n_selected, const int32_t* cells_host, const int32_t* shifts_host,
+                                 int32_t n_masks, const xfr_strise_geometry* geom, int32_t sign, double* sal_dev, const xfr_strise_options* opt, void* stream);
+/* exact = 1: the masks under scipy's law above; 0: the closed form */
+xfr_status XFR_EX xfr_strise_debug_masks_ex(xfr_engine* e, const int32_t* cells_host, const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom,
+                                     int32_t first, int32_t count, int32_t exact, double* masks_dev, const xfr_strise_options* opt, void* stream);
+/* the network input of masks [first, first + count): count x in_c x in_h x in_w fp32, what xfr_strise_score_ex feeds the forward.  first == -1 is
+ * image zero of the sweep, the unmasked probe (then masks [0, count - 1) follow it), and up to max_batch rows behind mask n_masks - 1 are the
+ * padding of the sweep's last batch */
+xfr_status XFR_EX xfr_strise_debug_masked_probes_ex(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host,
+                                             const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom, int32_t first, int32_t count,
+                                             float* out_dev, const xfr_strise_options* opt, void* stream);
+/* q itself, count x probe_h x probe_w x 3 uint8, for any engine (opt required; quantize and the tables are not read); first == -1 as above */
+xfr_status XFR_EX xfr_strise_debug_quantized(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host,
+                                      const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom, int32_t first, int32_t count,
+                                      uint8_t* q_dev, const xfr_strise_options* opt, void* stream);
+
 /* Debug / parity: after an xfr_ebp call made while tracing is enabled, the per-firing trace
  * sum(P[i]) (what the golden fixtures store for every entry of Whitebox.P, whitebox.py:394).
  * xfr_engine_set_trace(e, 1) makes xfr_ebp record it (slower).  `sums` receives n_firings x S x N doubles

@@ -35,6 +35,20 @@ class StriseGeometry(ctypes.Structure):
     _fields_ = [('grid_h', ctypes.c_int32), ('grid_w', ctypes.c_int32), ('mask_scale', ctypes.c_int32), ('num_elements', ctypes.c_int32)]
 
 
+STRISE_MAX_TAPS = 8      # XFR_STRISE_MAX_TAPS
+
+
+class StriseTap(ctypes.Structure):
+    """xfr_strise_tap: one output row or column of PIL's 8-bit bilinear resize."""
+    _fields_ = [('first', ctypes.c_int32), ('count', ctypes.c_int32), ('coef', ctypes.c_int32 * STRISE_MAX_TAPS)]
+
+
+class StriseOptions(ctypes.Structure):
+    """xfr_strise_options: what the _ex forms of the xfr_strise_* calls take."""
+    _fields_ = [('struct_size', ctypes.c_int32), ('probe_h', ctypes.c_int32), ('probe_w', ctypes.c_int32), ('quantize', ctypes.c_int32),
+                ('row_tab', ctypes.POINTER(StriseTap)), ('col_tab', ctypes.POINTER(StriseTap))]
+
+
 class InpaintOptions(ctypes.Structure):
     """xfr_inpaint_options: what the _ex forms of the xfr_inpaint_* calls take."""
     _fields_ = [('struct_size', ctypes.c_int32), ('levels_per_map', ctypes.c_int32), ('totals_host', ctypes.POINTER(ctypes.c_double)),
@@ -103,6 +117,16 @@ SYMBOLS = [
     ('xfr_strise_combine', _I, [_P, _P, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _P, _P]),
     ('xfr_strise_debug_masks', _I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _I, _P, _P]),
     ('xfr_strise_debug_masked_probes', _I, [_P, _P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _I, _P, _P]),
+    ('xfr_strise_score_ex', _I, [_P, _P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _P, _I, _P, _I, _I, _P, _P,
+                                 ctypes.POINTER(StriseOptions), _P]),
+    ('xfr_strise_combine_ex', _I, [_P, _P, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _P,
+                                   ctypes.POINTER(StriseOptions), _P]),
+    ('xfr_strise_debug_masks_ex', _I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _I, _I, _P,
+                                       ctypes.POINTER(StriseOptions), _P]),
+    ('xfr_strise_debug_masked_probes_ex', _I, [_P, _P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _I, _P,
+                                               ctypes.POINTER(StriseOptions), _P]),
+    ('xfr_strise_debug_quantized', _I, [_P, _P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(StriseGeometry), _I, _I, _P,
+                                        ctypes.POINTER(StriseOptions), _P]),
     ('xfr_inpaint_score', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     ('xfr_inpaint_iou', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _P]),
     ('xfr_inpaint_debug_masks', _I, [_P, _P, _I, _I, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _P]),

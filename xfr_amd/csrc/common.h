@@ -458,6 +458,26 @@ void launch_strise_score(const float* emb, int first, int count, const float* re
 void launch_strise_merge(const double* weights, const int* cells, const int* order, const int* group_off, double* A, double* wsum, double count, double sign,
                          double* sal, const StriseGeom& g, hipStream_t s);
 
+// The quantised chain of the generator's black box (whitebox.py:787-806 behind blackbox.py:343): masks by scipy's zoom to the bit, then
+// q = uint8((v / 255) * 255).  A row of the image list with a negative shift has no mask: q = probe.
+// out [n][3][H][W] = (float)((double)q - mean[c])
+void launch_strise_quant(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, float* out, const StriseGeom& g,
+                         const double* mean, hipStream_t s);
+// out [n][H][W][3] = q (parity hook)
+void launch_strise_quant_u8(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, uint8_t* out, const StriseGeom& g,
+                            hipStream_t s);
+// out [n][H][W]: the float64 masks under the exact law (parity hook)
+void launch_strise_masks_exact(const int* cells, const int* shifts, int n, double* out, const StriseGeom& g, hipStream_t s);
+// one output row or column of PIL's 8-bit bilinear resize: pixels [first, first + count) weighted by coef in 2^-22 (xfr_strise_tap)
+constexpr int STRISE_MAX_TAPS = 8;
+struct StriseTap { int first, count; int coef[STRISE_MAX_TAPS]; };
+constexpr int STRISE_LUM_BAND = 16;      // output rows per workgroup of the luminance kernel
+constexpr size_t strise_lum_lds_bytes(int rows_max, int W, int in_w) { return (size_t)rows_max * (size_t)(W + in_w) * 3; }
+// out [n][1][in_h][in_w] = rgb2gray of the resized and cropped q; row_tab [in_h], col_tab [in_w] on the device; rows_max: the most probe rows one
+// band of STRISE_LUM_BAND output rows reads
+void launch_strise_quant_lum(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, const StriseTap* row_tab,
+                             const StriseTap* col_tab, float* out, const StriseGeom& g, int in_h, int in_w, int rows_max, const double* weight, hipStream_t s);
+
 // ---- inpainting-game scoring (inpaint.hip; python/xfr/inpainting_game/inpainting_game.py:12-197) ----------------------------
 // Nested threshold masks are stored as one byte per pixel, first_on: the first level at which the pixel is on, n_levels where it never is; mask l
 // is first_on <= l.  A level table travels as a kernel argument: thr[l] is the threshold of level l (non-increasing in l).

@@ -243,7 +243,242 @@ __global__ __launch_bounds__(1024) void strise_normalize_kernel(double* __restri
     for (int i = threadIdx.x; i < n; i += 1024) sal[i] = (sal[i] - mn) / top;
 }
 
+// ---- the generator's black box (eval/generate_inpaintinggame_bb_saliency_maps_multigpu.py:73-101): every masked probe goes through
+// Whitebox.convert_from_numpy (whitebox.py:787-806), which TRUNCATES (v / 255) * 255 to uint8 -- a mask that is 1 - 2^-53 where the law above gives 1
+// costs a level.  So this path evaluates scipy's zoom to the bit: one rounded float64 operation per step, none contracted.
+
+// one rounded operation each (inpaint.hip states the same helpers: the __dmul_rn / __dadd_rn of the HIP headers are plain operators under the
+// translation unit's default contraction)
+__device__ inline double mul_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ inline double add_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ inline double sub_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a - b;
+}
+__device__ inline double div_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a / b;
+}
+
+// scipy.ndimage.zoom(order=1, mode='mirror', grid_mode=True) along one axis of g cells, output coordinate o (shift included): only a negative
+// coordinate is reflected, the second spline weight is one minus the first (not the fraction), the upper tap folds at g - 1
+__device__ inline void exact_taps(int o, int g, double ratio, int& i0, int& i1, double& w0, double& w1)
+{
+    const double cc = sub_rn(mul_rn((double)o + 0.5, ratio), 0.5);
+    const double c = cc < 0.0 ? -cc : cc;
+    const double st = floor(c);
+    w0 = sub_rn(1.0, sub_rn(c, st));
+    w1 = sub_rn(1.0, w0);
+    i0 = min((int)st, g - 1);
+    i1 = i0 + 1;
+    if (i1 > g - 1) i1 = 2 * (g - 1) - i1;
+    if (g == 1) { i0 = i1 = 0; w0 = 1.0; w1 = 0.0; }
+}
+
+// scipy's accumulation: from 0.0, rows outermost, each product as (G * wy) * wx
+__device__ inline double mask_exact(double g00, double g01, double g10, double g11, double wy0, double wy1, double wx0, double wx1)
+{
+    double t = add_rn(0.0, mul_rn(mul_rn(g00, wy0), wx0));
+    t = add_rn(t, mul_rn(mul_rn(g01, wy0), wx1));
+    t = add_rn(t, mul_rn(mul_rn(g10, wy1), wx0));
+    return add_rn(t, mul_rn(mul_rn(g11, wy1), wx1));
+}
+
+// blackbox.py:343 then whitebox.py:794-795,803: np.uint8((v / 255) * 255) of v = mask * probe + (1 - mask) * fill, an IEEE division and product,
+// truncated (v lies in [0, 255])
+__device__ inline int quantize_blend(double m, double p, double f)
+{
+    const double v = add_rn(mul_rn(m, p), mul_rn(sub_rn(1.0, m), f));
+    return (int)mul_rn(div_rn(v, 255.0), 255.0);
+}
+
+// K_strise_quant: strise_masked_kernel for the quantised chain.  A row of the image list whose shift is negative has no mask (image zero: the
+// unmasked probe, and the padding): q = probe, since uint8((k / 255) * 255) == k for every level and an all-ones mask under the exact law is not
+// the probe.  U8OUT: the parity hook, q itself as uint8 H x W x 3; else the network input (float)((double)q - mean[c]), NCHW, float4 stores.
+template <bool U8OUT>
+__global__ __launch_bounds__(NT, 8) void strise_quant_kernel(const uint8_t* __restrict__ probe, const double* __restrict__ fill, const int* __restrict__ cells,
+                                                          const int* __restrict__ shifts, void* __restrict__ out_any, StriseGeom g, double m0, double m1, double m2)
+{
+    __shared__ uint8_t grid[STRISE_MAX_CELLS];
+    const int k = blockIdx.y;
+    build_grid(grid, cells + (size_t)k * g.n_elem, g.n_elem, g.gh * g.gw);
+    const int W4 = (g.W + 3) >> 2;
+    const int q = blockIdx.x * NT + threadIdx.x;
+    if (q >= g.H * W4) return;
+    const int row = q / W4, x0 = (q - row * W4) * 4;
+    const int sx = shifts[2 * k], sy = shifts[2 * k + 1];
+    const bool masked = sx >= 0;
+    double m[4] = {1.0, 1.0, 1.0, 1.0};
+    if (masked) {
+        int r0, r1;
+        double wy0, wy1;
+        exact_taps(row + sx, g.gh, g.ry, r0, r1, wy0, wy1);
+        const uint8_t* g0 = grid + r0 * g.gw;
+        const uint8_t* g1 = grid + r1 * g.gw;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int c0, c1;
+            double wx0, wx1;
+            exact_taps(min(x0 + j, g.W - 1) + sy, g.gw, g.rx, c0, c1, wx0, wx1);
+            m[j] = mask_exact((double)g0[c0], (double)g0[c1], (double)g1[c0], (double)g1[c1], wy0, wy1, wx0, wx1);
+        }
+    }
+    const double mean[3] = {m0, m1, m2};
+    const size_t plane = (size_t)g.H * g.W;
+    const size_t px = ((size_t)row * g.W + x0) * 3;
+    const bool vec = (g.W & 3) == 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int lv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const size_t at = px + 3 * (vec ? j : min(j, g.W - 1 - x0)) + c;
+            lv[j] = masked ? quantize_blend(m[j], (double)probe[at], fill[at]) : (int)probe[at];
+        }
+        if (U8OUT) {
+            uint8_t* o = (uint8_t*)out_any + (size_t)k * 3 * plane + px + c;
+            for (int j = 0; j < 4 && x0 + j < g.W; ++j) o[3 * j] = (uint8_t)lv[j];
+        } else {
+            float* o = (float*)out_any + (size_t)k * 3 * plane + (size_t)row * g.W + x0 + c * plane;
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (float)sub_rn((double)lv[j], mean[c]);
+            if (vec) {
+                *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+            } else {
+                for (int j = 0; j < 4 && x0 + j < g.W; ++j) o[j] = v[j];
+            }
+        }
+    }
+}
+
+// parity hook: the float64 masks under the exact law, n x H x W
+__global__ __launch_bounds__(NT) void strise_masks_exact_kernel(const int* __restrict__ cells, const int* __restrict__ shifts, double* __restrict__ out, StriseGeom g)
+{
+    __shared__ uint8_t grid[STRISE_MAX_CELLS];
+    const int k = blockIdx.y;
+    build_grid(grid, cells + (size_t)k * g.n_elem, g.n_elem, g.gh * g.gw);
+    const int q = blockIdx.x * NT + threadIdx.x;
+    if (q >= g.H * g.W) return;
+    const int row = q / g.W, x = q - row * g.W;
+    int r0, r1, c0, c1;
+    double wy0, wy1, wx0, wx1;
+    exact_taps(row + shifts[2 * k], g.gh, g.ry, r0, r1, wy0, wy1);
+    exact_taps(x + shifts[2 * k + 1], g.gw, g.rx, c0, c1, wx0, wx1);
+    out[(size_t)k * g.H * g.W + q] = mask_exact((double)grid[r0 * g.gw + c0], (double)grid[r0 * g.gw + c1], (double)grid[r1 * g.gw + c0],
+                                                (double)grid[r1 * g.gw + c1], wy0, wy1, wx0, wx1);
+}
+
+// one pass of PIL's 8-bit resampling (Resample.c, ImagingResampleHorizontal_8bpc): clip8((2^21 + sum pixel * coef) >> 22), pixels `stride` apart
+__device__ inline int resample_u8(const uint8_t* __restrict__ px, int stride, const StriseTap& t)
+{
+    int acc = 1 << 21;
+    for (int i = 0; i < t.count; ++i) acc += (int)px[i * stride] * t.coef[i];
+    return min(max(acc >> 22, 0), 255);
+}
+
+// K_strise_quant_lum: the quantised chain for XFR_U8_LUMINANCE networks (Light-CNN, lightcnn.py:19-31): q at probe resolution, PIL's bilinear
+// Resize + CenterCrop as two integer passes from the caller's cropped tap tables (columns first, rounded to uint8, then rows), then rgb2gray as
+// u8hwc_to_cnhw_kernel states it, into the 1 x in_h x in_w input.  One workgroup per (image, band of STRISE_LUM_BAND output rows): q of the
+// probe rows the band reads as bytes in LDS, the horizontal pass into a second byte plane, the vertical pass and the luminance from there.
+// Dynamic LDS: rows_max x (W + in_w) x 3 bytes behind the grid.
+__global__ __launch_bounds__(NT) void strise_quant_lum_kernel(const uint8_t* __restrict__ probe, const double* __restrict__ fill, const int* __restrict__ cells,
+                                                              const int* __restrict__ shifts, const StriseTap* __restrict__ row_tab,
+                                                              const StriseTap* __restrict__ col_tab, float* __restrict__ out, StriseGeom g, int in_h, int in_w,
+                                                              int rows_max, double w0, double w1, double w2)
+{
+    __shared__ uint8_t grid[STRISE_MAX_CELLS];
+    extern __shared__ uint8_t planes[];
+    uint8_t* qs = planes;                                      // [rows][W][3]
+    uint8_t* hs = planes + (size_t)rows_max * g.W * 3;         // [rows][in_w][3]
+    const int k = blockIdx.y;
+    build_grid(grid, cells + (size_t)k * g.n_elem, g.n_elem, g.gh * g.gw);
+    const int oy0 = blockIdx.x * STRISE_LUM_BAND, oy1 = min(oy0 + STRISE_LUM_BAND, in_h);
+    int lo = g.H, hi = 0;
+    for (int oy = oy0; oy < oy1; ++oy) {
+        lo = min(lo, row_tab[oy].first);
+        hi = max(hi, row_tab[oy].first + row_tab[oy].count);
+    }
+    const int rows = min(hi - lo, rows_max);                   // the host sized rows_max by the same walk
+    const int sx = shifts[2 * k], sy = shifts[2 * k + 1];
+    const bool masked = sx >= 0;
+    for (int i = threadIdx.x; i < rows * g.W; i += NT) {
+        const int r = i / g.W, x = i - r * g.W;
+        const size_t at = ((size_t)(lo + r) * g.W + x) * 3;
+        uint8_t* o = qs + (size_t)i * 3;
+        if (masked) {
+            int r0, r1, c0, c1;
+            double wy0, wy1, wx0, wx1;
+            exact_taps(lo + r + sx, g.gh, g.ry, r0, r1, wy0, wy1);
+            exact_taps(x + sy, g.gw, g.rx, c0, c1, wx0, wx1);
+            const double m = mask_exact((double)grid[r0 * g.gw + c0], (double)grid[r0 * g.gw + c1], (double)grid[r1 * g.gw + c0],
+                                        (double)grid[r1 * g.gw + c1], wy0, wy1, wx0, wx1);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = (uint8_t)quantize_blend(m, (double)probe[at + c], fill[at + c]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = probe[at + c];
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < rows * in_w; i += NT) {
+        const int r = i / in_w, ox = i - r * in_w;
+        const StriseTap& t = col_tab[ox];
+        const uint8_t* px = qs + ((size_t)r * g.W + t.first) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) hs[(size_t)i * 3 + c] = (uint8_t)resample_u8(px + c, 3, t);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < (oy1 - oy0) * in_w; i += NT) {
+        const int oy = oy0 + i / in_w, ox = i % in_w;
+        const StriseTap& t = row_tab[oy];
+        const uint8_t* px = hs + ((size_t)(t.first - lo) * in_w + ox) * 3;
+        const int r = resample_u8(px, in_w * 3, t), gr = resample_u8(px + 1, in_w * 3, t), b = resample_u8(px + 2, in_w * 3, t);
+        // (rgb / 255) @ w, left to right (elementwise.hip, u8hwc_to_cnhw_kernel)
+        double v = mul_rn(div_rn((double)r, 255.0), w0);
+        v = add_rn(v, mul_rn(div_rn((double)gr, 255.0), w1));
+        v = add_rn(v, mul_rn(div_rn((double)b, 255.0), w2));
+        out[((size_t)k * in_h + oy) * in_w + ox] = (float)v;
+    }
+}
+
 }  // namespace
+
+void launch_strise_quant(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, float* out, const StriseGeom& g,
+                         const double* mean, hipStream_t s)
+{
+    const int quads = g.H * ((g.W + 3) / 4);
+    hipLaunchKernelGGL(strise_quant_kernel<false>, dim3((quads + NT - 1) / NT, n), dim3(NT), 0, s, probe, fill, cells, shifts, (void*)out, g, mean[0], mean[1], mean[2]);
+}
+
+void launch_strise_quant_u8(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, uint8_t* out, const StriseGeom& g, hipStream_t s)
+{
+    const int quads = g.H * ((g.W + 3) / 4);
+    hipLaunchKernelGGL(strise_quant_kernel<true>, dim3((quads + NT - 1) / NT, n), dim3(NT), 0, s, probe, fill, cells, shifts, (void*)out, g, 0.0, 0.0, 0.0);
+}
+
+void launch_strise_masks_exact(const int* cells, const int* shifts, int n, double* out, const StriseGeom& g, hipStream_t s)
+{
+    hipLaunchKernelGGL(strise_masks_exact_kernel, dim3((g.H * g.W + NT - 1) / NT, n), dim3(NT), 0, s, cells, shifts, out, g);
+}
+
+void launch_strise_quant_lum(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, const StriseTap* row_tab,
+                             const StriseTap* col_tab, float* out, const StriseGeom& g, int in_h, int in_w, int rows_max, const double* weight, hipStream_t s)
+{
+    const size_t lds = strise_lum_lds_bytes(rows_max, g.W, in_w);
+    hipLaunchKernelGGL(strise_quant_lum_kernel, dim3((in_h + STRISE_LUM_BAND - 1) / STRISE_LUM_BAND, n), dim3(NT), lds, s, probe, fill, cells, shifts, row_tab,
+                       col_tab, out, g, in_h, in_w, rows_max, weight[0], weight[1], weight[2]);
+}
 
 void launch_strise_masked(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, float* out, const StriseGeom& g,
                           const double* mean, hipStream_t s)

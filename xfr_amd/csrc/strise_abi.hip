@@ -34,17 +34,44 @@ StriseState* strise_state(xfr_engine* e)
     return e->strise;
 }
 
+// the options of the _ex calls as the entry points use them; opt == NULL: the engine's input size, no quantisation
+struct StriseOpt {
+    int H = 0, W = 0;
+    bool given = false, quant = false, lum = false;
+    const xfr_strise_tap* row_tab = nullptr;
+    const xfr_strise_tap* col_tab = nullptr;
+    int rows_max = 0;                                  // luminance: the most probe rows one band of STRISE_LUM_BAND output rows reads
+};
+
+static_assert(sizeof(xfr_strise_tap) == sizeof(StriseTap) && XFR_STRISE_MAX_TAPS == STRISE_MAX_TAPS, "xfr_strise_tap is StriseTap");
+
 // what every entry point checks before anything is launched
-xfr_status check_masks(xfr_engine* e, const int32_t* cells, const int32_t* shifts, int n_masks, const xfr_strise_geometry* geom, StriseGeom* g)
+xfr_status check_masks(xfr_engine* e, const int32_t* cells, const int32_t* shifts, int n_masks, const xfr_strise_geometry* geom, const xfr_strise_options* opt,
+                       StriseGeom* g, StriseOpt* o)
 {
     if (!e) return fail(XFR_INVALID_ARG, "null engine");
+    o->H = e->in_h;
+    o->W = e->in_w;
+    if (opt) {
+        if (opt->struct_size != (int32_t)sizeof(xfr_strise_options))
+            return fail(XFR_INVALID_ARG, "strise: options of struct_size %d, this library's xfr_strise_options has %d bytes", opt->struct_size,
+                        (int)sizeof(xfr_strise_options));
+        if (opt->probe_h < 1 || opt->probe_w < 1) return fail(XFR_INVALID_ARG, "strise: a probe of %d x %d", opt->probe_h, opt->probe_w);
+        if (opt->quantize != 0 && opt->quantize != 1) return fail(XFR_INVALID_ARG, "strise: quantize must be 0 or 1, got %d", opt->quantize);
+        o->given = true;
+        o->H = opt->probe_h;
+        o->W = opt->probe_w;
+        o->quant = opt->quantize == 1;
+        o->row_tab = opt->row_tab;
+        o->col_tab = opt->col_tab;
+    }
     if (!cells || !shifts || !geom) return fail(XFR_INVALID_ARG, "strise: null argument");
     if (n_masks < 1) return fail(XFR_INVALID_ARG, "strise: %d masks", n_masks);
     if (geom->grid_h < 1 || geom->grid_w < 1 || geom->mask_scale < 1 || geom->num_elements < 1)
         return fail(XFR_INVALID_ARG, "strise: grid %d x %d, mask_scale %d, %d elements per mask", geom->grid_h, geom->grid_w, geom->mask_scale, geom->num_elements);
     // a shift lies inside one cell of the image: a larger scale is no mask geometry, and scale^2 shift groups size the merge's workspace and grid
-    if (geom->mask_scale > e->in_h || geom->mask_scale > e->in_w)
-        return fail(XFR_INVALID_ARG, "strise: mask_scale %d exceeds the %d x %d input", geom->mask_scale, e->in_h, e->in_w);
+    if (geom->mask_scale > o->H || geom->mask_scale > o->W)
+        return fail(XFR_INVALID_ARG, "strise: mask_scale %d exceeds the %d x %d input", geom->mask_scale, o->H, o->W);
     const long nc = (long)geom->grid_h * geom->grid_w;
     if (nc > STRISE_MAX_CELLS) return fail(XFR_INVALID_ARG, "strise: a grid of %d x %d cells exceeds %d", geom->grid_h, geom->grid_w, STRISE_MAX_CELLS);
     if (geom->num_elements > nc) return fail(XFR_INVALID_ARG, "strise: %d elements per mask in a grid of %ld cells", geom->num_elements, nc);
@@ -54,17 +81,66 @@ xfr_status check_masks(xfr_engine* e, const int32_t* cells, const int32_t* shift
     for (long i = 0; i < 2L * n_masks; ++i)
         if (shifts[i] < 0 || shifts[i] >= geom->mask_scale)
             return fail(XFR_INVALID_ARG, "strise: shift %d of mask %ld outside [0, %d)", shifts[i], i / 2, geom->mask_scale);
-    *g = StriseGeom{e->in_h, e->in_w, geom->grid_h, geom->grid_w, geom->mask_scale, geom->num_elements,
-                    (double)geom->grid_h / (double)(e->in_h + geom->mask_scale), (double)geom->grid_w / (double)(e->in_w + geom->mask_scale)};
+    *g = StriseGeom{o->H, o->W, geom->grid_h, geom->grid_w, geom->mask_scale, geom->num_elements,
+                    (double)geom->grid_h / (double)(o->H + geom->mask_scale), (double)geom->grid_w / (double)(o->W + geom->mask_scale)};
     return XFR_OK;
 }
 
-// only the arithmetic of convert_resnet101v4_image is built into the masked-probe kernel
-xfr_status check_u8(xfr_engine* e)
+// one tap table of a luminance engine against the probe's axis of n pixels
+xfr_status check_taps(const xfr_strise_tap* tab, int entries, int n, const char* what)
 {
+    for (int i = 0; i < entries; ++i) {
+        const xfr_strise_tap& t = tab[i];
+        if (t.count < 1 || t.count > XFR_STRISE_MAX_TAPS)
+            return fail(XFR_INVALID_ARG, "strise: %s table entry %d has count %d, outside [1, %d]", what, i, t.count, XFR_STRISE_MAX_TAPS);
+        if (t.first < 0 || (long)t.first + t.count > n)
+            return fail(XFR_INVALID_ARG, "strise: %s table entry %d reads [%d, %d + %d), a window outside the probe's %d", what, i, t.first, t.first, t.count, n);
+        long sum = 0;
+        for (int j = 0; j < t.count; ++j) {
+            if (t.coef[j] < 0) return fail(XFR_INVALID_ARG, "strise: %s table entry %d has the negative coefficient %d", what, i, t.coef[j]);
+            sum += t.coef[j];
+        }
+        if (sum * 255 + (1L << 21) > 2147483647L)
+            return fail(XFR_INVALID_ARG, "strise: %s table entry %d: 255 x the coefficient sum %ld overflows int32", what, i, sum);
+    }
+    return XFR_OK;
+}
+
+// what the network input needs of the engine.  quantize 0: only the arithmetic of convert_resnet101v4_image is built into the masked-probe kernel;
+// quantize 1: the engine's own uint8 preprocessing, sub-mean at the probe's size or luminance behind the caller's resampling tables
+xfr_status check_u8(xfr_engine* e, StriseOpt* o)
+{
+    if (o->quant && !e->u8_set)
+        return fail(XFR_INVALID_ARG, "strise: quantize = 1 needs the engine's uint8 preprocessing (xfr_engine_set_u8_preprocess)");
+    if (o->quant && e->u8_pre.kind == XFR_U8_LUMINANCE) {
+        if (e->in_c != 1 || e->u8_pre.channels != 3)
+            return fail(XFR_INVALID_ARG, "strise: XFR_U8_LUMINANCE of %d-channel images into a %d-channel network; 3 and 1 are built", e->u8_pre.channels, e->in_c);
+        if (!o->row_tab || !o->col_tab)
+            return fail(XFR_INVALID_ARG, "strise: an XFR_U8_LUMINANCE engine needs the resampling tables row_tab and col_tab");
+        xfr_status rc = check_taps(o->row_tab, e->in_h, o->H, "row");
+        if (rc != XFR_OK) return rc;
+        rc = check_taps(o->col_tab, e->in_w, o->W, "column");
+        if (rc != XFR_OK) return rc;
+        for (int oy0 = 0; oy0 < e->in_h; oy0 += STRISE_LUM_BAND) {      // the kernel's own walk over a band
+            int lo = o->H, hi = 0;
+            for (int oy = oy0; oy < std::min(oy0 + STRISE_LUM_BAND, e->in_h); ++oy) {
+                lo = std::min(lo, o->row_tab[oy].first);
+                hi = std::max(hi, o->row_tab[oy].first + o->row_tab[oy].count);
+            }
+            o->rows_max = std::max(o->rows_max, hi - lo);
+        }
+        const size_t lds = strise_lum_lds_bytes(o->rows_max, o->W, e->in_w);
+        if (lds > 60 * 1024)
+            return fail(XFR_INVALID_ARG, "strise: a band of %d output rows reads %d probe rows of %d pixels: %zu bytes of LDS, more than %d", STRISE_LUM_BAND,
+                        o->rows_max, o->W, lds, 60 * 1024);
+        o->lum = true;
+        return XFR_OK;
+    }
     if (e->in_c != 3 || !e->u8_set || e->u8_pre.kind != XFR_U8_SUB_MEAN || e->u8_pre.channels != 3)
         return fail(XFR_INVALID_ARG, "strise: masked probes need a 3-channel network with XFR_U8_SUB_MEAN preprocessing of 3-channel images "
                                      "(xfr_engine_set_u8_preprocess); this engine takes %d channels", e->in_c);
+    if (o->H != e->in_h || o->W != e->in_w)
+        return fail(XFR_INVALID_ARG, "strise: a probe of %d x %d for an XFR_U8_SUB_MEAN engine whose input size is %d x %d", o->H, o->W, e->in_h, e->in_w);
     return XFR_OK;
 }
 
@@ -78,12 +154,16 @@ xfr_status upload_table(StriseState* st, const std::vector<int>& tab, hipStream_
     return XFR_OK;
 }
 
+constexpr int TAP_INTS = (int)(sizeof(StriseTap) / sizeof(int));
+
 // rows [first, first + count) of the sweep's image list -- image 0 is the unmasked probe, images 1 .. n_masks the masks, anything beyond is padding
-// (all-ones masks: cell -1, shift 0) -- as one table on the device: count x n_elem cells, then count x 2 shifts
-xfr_status upload_rows(StriseState* st, const int32_t* cells, const int32_t* shifts, int n_masks, int n_elem, long first, long count, bool with_probe,
-                       hipStream_t s)
+// -- as one table on the device: count x n_elem cells, then count x 2 shifts, then (luminance) the in_h + in_w resampling taps.  A row without a
+// mask has cell -1 and shift 0, the all-ones mask of the closed-form law; under quantize = 1 its shift is -1: q = probe
+xfr_status upload_rows(xfr_engine* e, StriseState* st, const int32_t* cells, const int32_t* shifts, int n_masks, int n_elem, long first, long count,
+                       bool with_probe, const StriseOpt& o, hipStream_t s)
 {
-    std::vector<int> tab((size_t)count * (n_elem + 2), -1);
+    const size_t taps = o.lum ? (size_t)(e->in_h + e->in_w) * TAP_INTS : 0;
+    std::vector<int> tab((size_t)count * (n_elem + 2) + taps, -1);
     int* sh = tab.data() + (size_t)count * n_elem;
     for (long r = 0; r < count; ++r) {
         const long k = first + r - (with_probe ? 1 : 0);
@@ -92,25 +172,47 @@ xfr_status upload_rows(StriseState* st, const int32_t* cells, const int32_t* shi
             sh[2 * r] = shifts[2 * k];
             sh[2 * r + 1] = shifts[2 * k + 1];
         } else {
-            sh[2 * r] = sh[2 * r + 1] = 0;
+            sh[2 * r] = sh[2 * r + 1] = o.quant ? -1 : 0;
         }
     }
+    if (o.lum) {
+        int* t = sh + 2 * count;
+        memcpy(t, o.row_tab, sizeof(StriseTap) * e->in_h);
+        memcpy(t + (size_t)e->in_h * TAP_INTS, o.col_tab, sizeof(StriseTap) * e->in_w);
+    }
     return upload_table(st, tab, s);
+}
+
+// the network input of `n` rows of an uploaded table (upload_rows) into x: the sweep's generate step and the parity hook
+void launch_generate(xfr_engine* e, const uint8_t* probe, const double* fill, const int* tab, long rows, long row0, int n, float* x, const StriseGeom& g,
+                     const StriseOpt& o, hipStream_t s)
+{
+    const int* cells = tab + (size_t)row0 * g.n_elem;
+    const int* shifts = tab + (size_t)rows * g.n_elem + (size_t)row0 * 2;
+    if (!o.quant) {
+        launch_strise_masked(probe, fill, cells, shifts, n, x, g, e->u8_pre.mean, s);
+    } else if (!o.lum) {
+        launch_strise_quant(probe, fill, cells, shifts, n, x, g, e->u8_pre.mean, s);
+    } else {
+        const StriseTap* row_tab = reinterpret_cast<const StriseTap*>(tab + (size_t)rows * (g.n_elem + 2));
+        launch_strise_quant_lum(probe, fill, cells, shifts, n, row_tab, row_tab + e->in_h, x, g, e->in_h, e->in_w, o.rows_max, e->u8_pre.weight, s);
+    }
 }
 
 }  // namespace
 
 extern "C" {
 
-xfr_status xfr_strise_score(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host, const int32_t* shifts_host,
-                            int32_t n_masks, const xfr_strise_geometry* geom, const float* refs_dev, int32_t n_refs, const float* gallery_dev,
-                            int32_t n_gal, int32_t encode_tensor, double* scores_dev, double* orig_dev, void* stream)
+xfr_status xfr_strise_score_ex(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host, const int32_t* shifts_host,
+                               int32_t n_masks, const xfr_strise_geometry* geom, const float* refs_dev, int32_t n_refs, const float* gallery_dev,
+                               int32_t n_gal, int32_t encode_tensor, double* scores_dev, double* orig_dev, const xfr_strise_options* opt, void* stream)
 {
     StriseGeom g;
-    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, &g);
+    StriseOpt o;
+    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, opt, &g, &o);
     if (rc != XFR_OK) return rc;
     if (!probe_u8_dev || !fill_dev || !refs_dev || !gallery_dev || !scores_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
-    rc = check_u8(e);
+    rc = check_u8(e, &o);
     if (rc != XFR_OK) return rc;
     if (n_refs < 1 || n_gal < 1 || (n_refs != n_gal && n_refs != 1 && n_gal != 1))
         return fail(XFR_INVALID_ARG, "strise: %d references against %d gallery images do not broadcast (equal counts, or one of them 1)", n_refs, n_gal);
@@ -132,16 +234,13 @@ xfr_status xfr_strise_score(xfr_engine* e, const uint8_t* probe_u8_dev, const do
     // the fill may still be in flight there.  This is the sweep's one host wait
     rc = sweep_side_follows(sw, s);
     if (rc != XFR_OK) return rc;
-    rc = upload_rows(st, cells_host, shifts_host, n_masks, g.n_elem, 0, rows, true, sw->s_gen);
+    rc = upload_rows(e, st, cells_host, shifts_host, n_masks, g.n_elem, 0, rows, true, o, sw->s_gen);
     if (rc != XFR_OK) return rc;
-    const int* cells_d = st->tab;
-    const int* shifts_d = st->tab + (size_t)rows * g.n_elem;
+    const int* tab_d = st->tab;
     double* orig = st->orig;
     double* ginv = st->orig + nrg;
     rc = run_sweep(e, sw, total, encode_tensor, s,
-        [&](long i, float* x, hipStream_t side) {
-            launch_strise_masked(probe_u8_dev, fill_dev, cells_d + (size_t)i * B * g.n_elem, shifts_d + (size_t)i * B * 2, B, x, g, e->u8_pre.mean, side);
-        },
+        [&](long i, float* x, hipStream_t side) { launch_generate(e, probe_u8_dev, fill_dev, tab_d, rows, i * B, B, x, g, o, side); },
         [&](long i, const float* emb, hipStream_t) {
             if (i == 0) launch_strise_orig(emb, refs_dev, n_refs, gallery_dev, n_gal, D, orig, ginv, s);      // image 0: the unmasked probe
             // images [i B, i B + B) of the list; image 0 is the probe, images beyond n_masks are padding
@@ -154,11 +253,20 @@ xfr_status xfr_strise_score(xfr_engine* e, const uint8_t* probe_u8_dev, const do
     return XFR_OK;
 }
 
-xfr_status xfr_strise_combine(xfr_engine* e, const double* weights_dev, int32_t n_selected, const int32_t* cells_host, const int32_t* shifts_host,
-                              int32_t n_masks, const xfr_strise_geometry* geom, int32_t sign, double* sal_dev, void* stream)
+xfr_status xfr_strise_score(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host, const int32_t* shifts_host,
+                            int32_t n_masks, const xfr_strise_geometry* geom, const float* refs_dev, int32_t n_refs, const float* gallery_dev,
+                            int32_t n_gal, int32_t encode_tensor, double* scores_dev, double* orig_dev, void* stream)
+{
+    return xfr_strise_score_ex(e, probe_u8_dev, fill_dev, cells_host, shifts_host, n_masks, geom, refs_dev, n_refs, gallery_dev, n_gal, encode_tensor,
+                               scores_dev, orig_dev, nullptr, stream);
+}
+
+xfr_status xfr_strise_combine_ex(xfr_engine* e, const double* weights_dev, int32_t n_selected, const int32_t* cells_host, const int32_t* shifts_host,
+                                 int32_t n_masks, const xfr_strise_geometry* geom, int32_t sign, double* sal_dev, const xfr_strise_options* opt, void* stream)
 {
     StriseGeom g;
-    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, &g);
+    StriseOpt o;
+    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, opt, &g, &o);
     if (rc != XFR_OK) return rc;
     if (!weights_dev || !sal_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
     if (n_selected < 1 || n_selected > n_masks) return fail(XFR_INVALID_ARG, "strise: %d selected masks of %d", n_selected, n_masks);
@@ -201,22 +309,75 @@ xfr_status xfr_strise_combine(xfr_engine* e, const double* weights_dev, int32_t 
     return XFR_OK;
 }
 
-xfr_status xfr_strise_debug_masks(xfr_engine* e, const int32_t* cells_host, const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom,
-                                  int32_t first, int32_t count, double* masks_dev, void* stream)
+xfr_status xfr_strise_combine(xfr_engine* e, const double* weights_dev, int32_t n_selected, const int32_t* cells_host, const int32_t* shifts_host,
+                              int32_t n_masks, const xfr_strise_geometry* geom, int32_t sign, double* sal_dev, void* stream)
+{
+    return xfr_strise_combine_ex(e, weights_dev, n_selected, cells_host, shifts_host, n_masks, geom, sign, sal_dev, nullptr, stream);
+}
+
+namespace {
+
+// masks [first, first + count) of the parity hooks; with options the range is one of the sweep's image list: first == -1 is image zero, the
+// unmasked probe, and up to `pad` rows behind the last mask are the padding of the last batch
+xfr_status check_range(const StriseOpt& o, int first, int count, int n_masks, int at_most, int pad)
+{
+    if (first < (o.given ? -1 : 0) || count < 1 || (long)first + count > (long)n_masks + (o.given ? pad : 0) || count > at_most)
+        return fail(XFR_INVALID_ARG, "strise: masks [%d, %d + %d) of %d, at most %d per call", first, first, count, n_masks, at_most);
+    return XFR_OK;
+}
+
+}  // namespace
+
+xfr_status xfr_strise_debug_masks_ex(xfr_engine* e, const int32_t* cells_host, const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom,
+                                     int32_t first, int32_t count, int32_t exact, double* masks_dev, const xfr_strise_options* opt, void* stream)
 {
     StriseGeom g;
-    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, &g);
+    StriseOpt o;
+    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, opt, &g, &o);
     if (rc != XFR_OK) return rc;
     if (!masks_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
+    if (exact != 0 && exact != 1) return fail(XFR_INVALID_ARG, "strise: exact must be 0 or 1, got %d", exact);
     if (first < 0 || count < 1 || (long)first + count > n_masks) return fail(XFR_INVALID_ARG, "strise: masks [%d, %d + %d) of %d", first, first, count, n_masks);
     hipStream_t s = (hipStream_t)stream;
     SweepCall call;
     rc = call.enter(e, s);
     if (rc != XFR_OK) return rc;
     StriseState* st = strise_state(e);
-    rc = upload_rows(st, cells_host, shifts_host, n_masks, g.n_elem, first, count, false, s);
+    rc = upload_rows(e, st, cells_host, shifts_host, n_masks, g.n_elem, first, count, false, StriseOpt(), s);
     if (rc != XFR_OK) return rc;
-    launch_strise_masks(st->tab, st->tab + (size_t)count * g.n_elem, count, masks_dev, g, s);
+    if (exact) launch_strise_masks_exact(st->tab, st->tab + (size_t)count * g.n_elem, count, masks_dev, g, s);
+    else launch_strise_masks(st->tab, st->tab + (size_t)count * g.n_elem, count, masks_dev, g, s);
+    HIP_TRY(hipGetLastError());
+    return XFR_OK;
+}
+
+xfr_status xfr_strise_debug_masks(xfr_engine* e, const int32_t* cells_host, const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom,
+                                  int32_t first, int32_t count, double* masks_dev, void* stream)
+{
+    return xfr_strise_debug_masks_ex(e, cells_host, shifts_host, n_masks, geom, first, count, 0, masks_dev, nullptr, stream);
+}
+
+xfr_status xfr_strise_debug_masked_probes_ex(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host,
+                                             const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom, int32_t first, int32_t count,
+                                             float* out_dev, const xfr_strise_options* opt, void* stream)
+{
+    StriseGeom g;
+    StriseOpt o;
+    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, opt, &g, &o);
+    if (rc != XFR_OK) return rc;
+    if (!probe_u8_dev || !fill_dev || !out_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
+    rc = check_u8(e, &o);
+    if (rc != XFR_OK) return rc;
+    rc = check_range(o, first, count, n_masks, e->max_batch, e->max_batch);
+    if (rc != XFR_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    SweepCall call;
+    rc = call.enter(e, s);
+    if (rc != XFR_OK) return rc;
+    StriseState* st = strise_state(e);
+    rc = upload_rows(e, st, cells_host, shifts_host, n_masks, g.n_elem, first, count, false, o, s);
+    if (rc != XFR_OK) return rc;
+    launch_generate(e, probe_u8_dev, fill_dev, st->tab, count, 0, count, out_dev, g, o, s);
     HIP_TRY(hipGetLastError());
     return XFR_OK;
 }
@@ -225,22 +386,31 @@ xfr_status xfr_strise_debug_masked_probes(xfr_engine* e, const uint8_t* probe_u8
                                           const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom, int32_t first, int32_t count,
                                           float* out_nchw_dev, void* stream)
 {
+    return xfr_strise_debug_masked_probes_ex(e, probe_u8_dev, fill_dev, cells_host, shifts_host, n_masks, geom, first, count, out_nchw_dev, nullptr, stream);
+}
+
+xfr_status xfr_strise_debug_quantized(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host,
+                                      const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom, int32_t first, int32_t count,
+                                      uint8_t* q_dev, const xfr_strise_options* opt, void* stream)
+{
     StriseGeom g;
-    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, &g);
+    StriseOpt o;
+    if (e && !opt) return fail(XFR_INVALID_ARG, "strise: xfr_strise_debug_quantized needs options (the probe's size)");
+    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, opt, &g, &o);
     if (rc != XFR_OK) return rc;
-    if (!probe_u8_dev || !fill_dev || !out_nchw_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
-    rc = check_u8(e);
+    if (!probe_u8_dev || !fill_dev || !q_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
+    rc = check_range(o, first, count, n_masks, n_masks + 1 + e->max_batch, e->max_batch);
     if (rc != XFR_OK) return rc;
-    if (first < 0 || count < 1 || (long)first + count > n_masks || count > e->max_batch)
-        return fail(XFR_INVALID_ARG, "strise: masks [%d, %d + %d) of %d, at most %d per call", first, first, count, n_masks, e->max_batch);
     hipStream_t s = (hipStream_t)stream;
     SweepCall call;
     rc = call.enter(e, s);
     if (rc != XFR_OK) return rc;
     StriseState* st = strise_state(e);
-    rc = upload_rows(st, cells_host, shifts_host, n_masks, g.n_elem, first, count, false, s);
+    StriseOpt q;
+    q.quant = true;      // rows without a mask: q = probe
+    rc = upload_rows(e, st, cells_host, shifts_host, n_masks, g.n_elem, first, count, false, q, s);
     if (rc != XFR_OK) return rc;
-    launch_strise_masked(probe_u8_dev, fill_dev, st->tab, st->tab + (size_t)count * g.n_elem, count, out_nchw_dev, g, e->u8_pre.mean, s);
+    launch_strise_quant_u8(probe_u8_dev, fill_dev, st->tab, st->tab + (size_t)count * g.n_elem, count, q_dev, g, s);
     HIP_TRY(hipGetLastError());
     return XFR_OK;
 }

@@ -142,10 +142,21 @@ def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, dev
     return out
 
 
+def run_blackbox_rise(wb, probe_im, mates, nonmates, rise_scale=12, num_mask_elements=2, mask_fill_type='blur', blur_sigma_percent=4, net=None, **kw):
+    """create_bbox of generate_blackbox_saliency.py:48-73 with the eval script's bb_fn around `wb` as the black box: STRise over the probe, its
+    mates as references and the non-mates as gallery -> the saliency map.  `net`: the ResNet-101 Whitebox of the mean-EBP prior (created on
+    demand, as in the reference); further keywords go to STRise (num_masks, prior_type, ...)."""
+    from .models.blackbox import STRise, WhiteboxBlackBox
+    strise = STRise(probe=probe_im, refs=mates, gallery=nonmates, mask_scale=rise_scale, black_box_fn=WhiteboxBlackBox(wb),
+                    num_mask_elements=num_mask_elements, mask_fill_type=mask_fill_type, blur_fill_sigma_percent=blur_sigma_percent, net=net, **kw)
+    strise.evaluate()
+    return strise.saliency_map
+
+
 def shorten_subtree_mode(ebp_subtree_mode):
     """:216-219"""
     return 'awp' if ebp_subtree_mode == 'affineonly_with_prior' else ebp_subtree_mode
 
 
-__all__ = ['mean_ebp', 'run_contrastive_triplet_ebp', 'run_weighted_subtree_triplet_ebp', 'run_jobs_batched', 'shorten_subtree_mode', 'mean_encoding',
+__all__ = ['run_blackbox_rise', 'mean_ebp', 'run_contrastive_triplet_ebp', 'run_weighted_subtree_triplet_ebp', 'run_jobs_batched', 'shorten_subtree_mode', 'mean_encoding',
            'SUBTREE_VERSIONS']

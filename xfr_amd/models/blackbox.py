@@ -24,6 +24,10 @@ saliency_map, prior, original_probe_ref_scores, original_probe_gallery_scores). 
 * Percentile.  np.percentile over the scores stays on the host, bit for bit the reference's; the weights go to xfr_strise_combine.
 * User callable.  A `black_box_fn` callable still works: masked probes are produced by the device kernel batch by batch, handed to the callable as
   float64 H x W x 3 arrays (the fp32 network input plus the mean: within 2**-16 of the reference's arrays), and the score rows are concatenated.
+* Generator's black box.  WhiteboxBlackBox(wb) as `black_box_fn` is the eval scripts' bb_fn (every masked probe through wb.convert_from_numpy,
+  i.e. a uint8 image, and the network's own preprocess) for ResNet-101, ResNet-50-128d and Light-CNN; score_masks runs it as one native sweep
+  (xfr_strise_score_ex, quantize = 1; masks by scipy's zoom to the bit, mask_law_scipy) and falls back to the callable itself where
+  WhiteboxBlackBox.device_route says so.  `score_route` tells which was taken.
 * Progress.  evaluate() runs the reference's five stages in its order and prints one line of its own before each.
 
 Out of scope, as in the issue this implements: potential_gallery / build_gallery (commented out in the reference), the plotting helpers."""
@@ -65,6 +69,97 @@ def mask_law(grid, out_shape, mask_scale, shift):
     return (1.0 - fy)[:, None] * top + fy[:, None] * bot
 
 
+def mask_law_scipy(grid, out_shape, mask_scale, shift):
+    """One mask on the host in scipy's own arithmetic: scipy.ndimage.zoom(grid, order=1, mode='mirror', grid_mode=True) to
+    (H + mask_scale, W + mask_scale), cropped at `shift`, BIT FOR BIT (scipy 1.15.3; csrc/strise.hip's exact_taps / mask_exact are the device
+    twin).  Per axis: the coordinate is (k + 0.5) * (g / (n + s)) - 0.5 with a negative coordinate reflected (not the tap indices), the last
+    spline weight is one minus the other (w1 = 1 - w0, not the fraction), the upper tap folds at g - 1; the four products are summed from 0.0
+    in tap order, rows outermost, each as (G * wy) * wx.  Where mask_law above is 1 this is often 1 - 2**-53, which the quantised black box
+    of WhiteboxBlackBox sees as a uint8 level."""
+    grid = np.asarray(grid, dtype=np.float64)
+
+    def taps(n, g, sh):
+        ratio = g / float(n + mask_scale)
+        cc = ((np.arange(n) + sh + 0.5) * ratio) - 0.5
+        c = np.where(cc < 0, -cc, cc)
+        st = np.floor(c)
+        w0 = 1.0 - (c - st)
+        w1 = 1.0 - w0
+        i0 = st.astype(np.int64)
+        i1 = i0 + 1
+        i1 = np.where(i1 > g - 1, 2 * (g - 1) - i1, i1)
+        if g == 1:
+            return np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.ones(n), np.zeros(n)
+        return i0, i1, w0, w1
+    r0, r1, wy0, wy1 = taps(out_shape[0], grid.shape[0], shift[0])
+    c0, c1, wx0, wx1 = taps(out_shape[1], grid.shape[1], shift[1])
+    t = 0.0 + (grid[np.ix_(r0, c0)] * wy0[:, None]) * wx0[None, :]
+    t = t + (grid[np.ix_(r0, c1)] * wy0[:, None]) * wx1[None, :]
+    t = t + (grid[np.ix_(r1, c0)] * wy1[:, None]) * wx0[None, :]
+    return t + (grid[np.ix_(r1, c1)] * wy1[:, None]) * wx1[None, :]
+
+
+PIL_PRECISION_BITS = 22      # Pillow's 8-bit resampling: coefficients in 2**-22, src/libImaging/Resample.c
+STRISE_MAX_TAPS = 8          # XFR_STRISE_MAX_TAPS
+
+
+def pil_bilinear_axis(n_in, n_out):
+    """PIL.Image.resize(..., BILINEAR) along one axis of a uint8 image, as integers: (first [n_out], count [n_out], coef [n_out][ksize] int32).
+    Output xx is clip8((2**21 + sum_t pixel[first + t] * coef[t]) >> 22)  (Pillow 12's precompute_coeffs / normalize_coeffs_8bpc)."""
+    scale = n_in / float(n_out)
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ksize = int(np.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    first = np.zeros(n_out, dtype=np.int32)
+    count = np.zeros(n_out, dtype=np.int32)
+    coef = np.zeros((n_out, ksize), dtype=np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), n_in) - xmin
+        w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) * ss)) for x in range(xmax)]
+        total = sum(w, 0.0)                                       # Pillow adds the weights one by one, left to right
+        first[xx], count[xx] = xmin, xmax
+        coef[xx, :xmax] = [int(0.5 + (v / total if total != 0.0 else v) * (1 << PIL_PRECISION_BITS)) for v in w]
+    return first, count, coef
+
+
+def pil_bilinear_tables(probe_hw, resize_short, crop_hw):
+    """The two tap tables (rows, columns) of torchvision's Resize(resize_short) + CenterCrop(crop_hw) on a uint8 probe of probe_hw, restated on
+    PIL's integer bilinear resize (lightcnn.py:27-31; xfr_amd.models.lightcnn.lightcnn_preprocess): only the outputs the crop keeps.  Each table
+    is a dict first [n] int32, count [n] int32, coef [n][ksize] int32; the resize runs its horizontal pass (columns) first, rounded to uint8, then
+    the vertical one (rows) -- apply_pil_tables below is the numpy statement.  A table with more than STRISE_MAX_TAPS taps does not fit the
+    device path (Engine.strise_* refuses it; STRise.score_masks falls back to the host)."""
+    h, w = int(probe_hw[0]), int(probe_hw[1])
+    if w <= h:
+        nw, nh = int(resize_short), int(resize_short * h / w)
+    else:
+        nw, nh = int(resize_short * w / h), int(resize_short)
+    tabs = []
+    for n_in, n_out, n_crop in ((h, nh, int(crop_hw[0])), (w, nw, int(crop_hw[1]))):
+        off = int(round((n_out - n_crop) / 2.0))
+        if off < 0:
+            raise ValueError('pil_bilinear_tables: a crop of %d from %d' % (n_crop, n_out))
+        first, count, coef = pil_bilinear_axis(n_in, n_out)
+        tabs.append(dict(first=first[off:off + n_crop].copy(), count=count[off:off + n_crop].copy(), coef=coef[off:off + n_crop].copy()))
+    return tabs[0], tabs[1]
+
+
+def apply_pil_tables(img_u8, row_tab, col_tab):
+    """uint8 H x W x C image -> the resized and cropped uint8 image of pil_bilinear_tables, in numpy: columns first, rounded, then rows."""
+    img = np.asarray(img_u8).astype(np.int64)
+
+    def one_pass(a, tab):      # along axis 0
+        out = np.empty((len(tab['first']),) + a.shape[1:], dtype=np.int64)
+        for i, (f, n) in enumerate(zip(tab['first'], tab['count'])):
+            acc = np.tensordot(tab['coef'][i, :n].astype(np.int64), a[f:f + n], axes=1) + (1 << (PIL_PRECISION_BITS - 1))
+            out[i] = np.clip(acc >> PIL_PRECISION_BITS, 0, 255)
+        return out
+    horiz = one_pass(img.transpose(1, 0, 2), col_tab).transpose(1, 0, 2)
+    return one_pass(horiz, row_tab).astype(np.uint8)
+
+
 BLACK_BOX_NAMES = ('resnetv4_pytorch', 'resnetv6_pytorch')
 _COLLECTION = 'a list of filepaths, NumPy arrays, or a Pandas dataframe'
 
@@ -91,6 +186,65 @@ def l2_similarity(probe_vecs, gallery_vecs):
     """1 - |p / |p| - g / |g|| / 2 for every (probe row, gallery row) pair (:385): len(probe_vecs) x len(gallery_vecs)."""
     gap = _unit_rows(probe_vecs)[:, None, :] - _unit_rows(gallery_vecs)[None, :, :]
     return 1.0 - 0.5 * np.linalg.norm(gap, axis=2)
+
+
+class WhiteboxBlackBox(object):
+    """The generator's black box (eval/generate_inpaintinggame_bb_saliency_maps_multigpu.py:73-101) around an xfr_amd Whitebox: called with
+    (probes, gallery) it is that bb_fn line for line -- H x W x 3 arrays through wb.convert_from_numpy, then wb.embeddings, then the L2
+    similarity -- and works wherever a user callable does.  STRise.score_masks recognises it and runs the whole sweep natively on wb's engine
+    (xfr_strise_score_ex, quantize = 1) where device_route allows."""
+
+    RESIZE_SHORT = 144      # lightcnn.py:28, Resize(144) in front of CenterCrop(in_h x in_w)
+
+    def __init__(self, wb):
+        if not isinstance(wb, Whitebox):
+            raise ValueError('wb must be an xfr_amd Whitebox')
+        self.wb = wb
+
+    def _vectors(self, images):
+        if isinstance(images[0], np.ndarray):
+            if images[0].shape[2] == 3:                    # "If third channel equals 3, assume images need preprocessing" (:81,88)
+                images = [self.wb.convert_from_numpy(im)[0] for im in images]
+        return self.wb.embeddings(images)
+
+    def __call__(self, probes, gallery):
+        gallery_vecs = self._vectors(gallery)
+        probe_vecs = self._vectors(probes)
+        return l2_similarity(probe_vecs, gallery_vecs)
+
+    def embed_raw(self, images):
+        """Un-normalised fp32 encodings n x D of references / gallery images, through the same conversion."""
+        if not _is_dataframe(images) and isinstance(images[0], np.ndarray) and images[0].shape[2] == 3:
+            images = [self.wb.convert_from_numpy(im)[0] for im in images]
+        v = np.asarray(self.wb.embeddings(images, norm=False))
+        return torch.from_numpy(v.reshape(v.shape[0], -1))
+
+    def resample_tables(self, probe_hw):
+        """The tap tables of a luminance network's Resize + CenterCrop (pil_bilinear_tables), None for a sub-mean network."""
+        spec = self.wb.net.u8_preprocess_spec()
+        if spec is None or spec[0] != 'luminance':
+            return None
+        return pil_bilinear_tables(probe_hw, self.RESIZE_SHORT, self.wb.net.net.in_shape[1:])
+
+    def device_route(self, probe, fill):
+        """-> (True, tables or None) where the native sweep computes what __call__ computes, else (False, the reason).  The host path is taken for
+        a probe that is not 224 x 224 (convert_from_numpy resizes it, whitebox.py:802); for np.minimum(probe, fill).max() < 2 (the / 255 of
+        whitebox.py:794-795 is conditional on the image's maximum exceeding 1, and only this bound guarantees it for every masked probe); for a
+        resampling table with more than STRISE_MAX_TAPS taps; for a network without u8_preprocess_spec; and for a sub-mean network whose input is
+        not the 224 x 224 that convert_from_numpy produces (xfr_strise_score_ex would refuse it)."""
+        if tuple(probe.shape[0:2]) != (224, 224):
+            return False, 'the probe is %d x %d, not 224 x 224' % tuple(probe.shape[0:2])
+        if np.minimum(probe, fill).max() < 2:
+            return False, 'min(probe, fill) stays below 2: the / 255 of convert_from_numpy is not certain'
+        spec = self.wb.net.u8_preprocess_spec()
+        if spec is None:
+            return False, 'the network states no uint8 preprocessing (u8_preprocess_spec)'
+        tables = self.resample_tables(probe.shape[0:2])
+        if tables is not None and max(int(t['count'].max()) for t in tables) > STRISE_MAX_TAPS:
+            return False, 'a resampling table has more than %d taps' % STRISE_MAX_TAPS
+        if tables is None and tuple(self.wb.net.net.in_shape[1:]) != (224, 224):
+            return False, 'the network input is not 224 x 224'
+        return True, tables
 
 
 class STRise:
@@ -164,6 +318,12 @@ class STRise:
     def _engine(self):
         wb = self._network()
         return wb._engine(wb.batch_size), wb.net._mark('encode')
+
+    def _merge_engine(self):
+        """The merge takes the probe's size, not the engine's: behind a WhiteboxBlackBox it runs on that network's engine, whatever its input."""
+        if isinstance(self.black_box_fn, WhiteboxBlackBox):
+            return self.black_box_fn.wb._engine(self.black_box_fn.wb.batch_size)
+        return self._engine()[0]
 
     def _grid(self, shape=None):
         """Cells of the coarse grid along each axis: ceil(size / mask_scale) (:302)."""
@@ -310,9 +470,27 @@ class STRise:
             self.masked_probe_ref_scores = self.masked_probe_gallery_scores = None
             self.mask_scores = scores.cpu().numpy()
             return
+        fn = self.black_box_fn
+        self.score_route = 'host'
+        if isinstance(fn, WhiteboxBlackBox):
+            # the generator's black box: one native sweep of the quantised chain on ITS network (the prior's network is `net`)
+            ok, tables = fn.device_route(self.probe, self._fill_image())
+            if ok:
+                self.score_route = 'device'
+                eng, enc = fn.wb._engine(fn.wb.batch_size), fn.wb.net._mark('encode')
+                cells, shifts, grid, scale = self._mask_args()
+                refs, gal = fn.embed_raw(self.refs), fn.embed_raw(self.gallery)
+                scores, orig = eng.strise_score(torch.from_numpy(self.probe), torch.from_numpy(self._fill_image()), cells, shifts, grid, scale, refs, gal,
+                                                enc, probe_shape=self.probe.shape[0:2], quantize=True, tables=tables)
+                orig = orig.cpu().numpy()
+                self.original_probe_ref_scores = orig[None, :refs.shape[0]]
+                self.original_probe_gallery_scores = orig[None, refs.shape[0]:]
+                self.masked_probe_ref_scores = self.masked_probe_gallery_scores = None
+                self.mask_scores = scores.cpu().numpy()
+                return
+            self.score_route = 'host: ' + tables
         # a user callable (:396-414): masked probes batch by batch from the device kernel; the probe's gallery scores survive from an earlier
         # call unless set_probe dropped them
-        fn = self.black_box_fn
         self.original_probe_ref_scores = fn([self.probe], self.refs)
         if getattr(self, 'original_probe_gallery_scores', None) is None:
             self.original_probe_gallery_scores = fn([self.probe], self.gallery)
@@ -343,10 +521,11 @@ class STRise:
     def compute_saliency_map(self, positive_scores=True, percentile=0):
         selected_indices, sign = self.select_masks(positive_scores, percentile)
         self.selected_indices = selected_indices
-        eng, _ = self._engine()
+        eng = self._merge_engine()
         cells, shifts, grid, scale = self._mask_args()
         weights = np.where(selected_indices, self.mask_scores, 0.0)
-        self.saliency_map = eng.strise_combine(weights, int(selected_indices.sum()), cells, shifts, grid, scale, sign).cpu().numpy()
+        self.saliency_map = eng.strise_combine(weights, int(selected_indices.sum()), cells, shifts, grid, scale, sign,
+                                               probe_shape=self.probe.shape[0:2]).cpu().numpy()
 
     def evaluate(self):
         """Prior, masks, fill, scores, map (:450-479), with a line of progress before each."""
@@ -357,4 +536,4 @@ class STRise:
             run()
 
 
-__all__ = ['STRise', 'mask_law', 'convert_resnet101v4_image', 'l2_similarity', 'BLACK_BOX_NAMES']
+__all__ = ['STRise', 'WhiteboxBlackBox', 'mask_law', 'mask_law_scipy', 'pil_bilinear_tables', 'apply_pil_tables', 'convert_resnet101v4_image', 'l2_similarity', 'BLACK_BOX_NAMES']
