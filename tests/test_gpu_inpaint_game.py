@@ -13,6 +13,7 @@ Bars (none of them taken from the code under test):
   drop-in         the device path against the same function on the host path (snet.embeddings): distances of unit vectors within 1e-4, the
                   forward's tolerance (tools/embeddings_sweep.py), masks and blends equal.
 With XFR_INPAINT_REPORT=<file> in the environment the measured figures are written there as JSON."""
+import functools
 import json
 import os
 
@@ -21,15 +22,16 @@ import pytest
 import torch
 
 import inpaint_game_inputs as I
-from parity_utils import make_backbone
+import probe_scoring_utils as U
+from probe_scoring_utils import lcnn, mini32, mini48      # noqa: F401 (fixtures)
 from xfr_amd import inpainting_score as S
-from xfr_amd.models import whitebox as WB
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = np.load(os.path.join(ROOT, 'tests', 'golden', 'golden_inpaint_game.npz'))
+GOLD = U.gold('inpaint_game')
 MINI_CASES = ('mini/zero_on', 'mini/zero_off', 'mini/thresholds', 'mini/two_maps')
 REPORT = {}
+_whitebox, _noise, _case = U.whitebox, U.noise, functools.partial(U.inpaint_case, GOLD)
+_check_scores = functools.partial(U.check_scores, GOLD, report=REPORT)
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -39,43 +41,6 @@ def _report():
     if REPORT and path:
         with open(path, 'w') as f:
             json.dump(dict(sorted(REPORT.items())), f, indent=1)
-
-
-def _whitebox(arch, batch, device):
-    bb, _ = make_backbone(arch, seed=0, num_classes=I.NUM_CLASSES[arch])
-    bb.to(device)
-    wbn = WB.WhiteboxSTResnet(bb) if arch != 'lightcnn29v2' else WB.WhiteboxLightCNN(bb)
-    wbn.default_max_batch = batch
-    wb = WB.Whitebox(wbn)
-    wb.batch_size = batch
-    return wb
-
-
-@pytest.fixture(scope='module')
-def mini48(gpu_device):
-    return _whitebox('stresnet_mini', 48, gpu_device)
-
-
-@pytest.fixture(scope='module')
-def mini32(gpu_device):
-    return _whitebox('stresnet_mini', 32, gpu_device)
-
-
-@pytest.fixture(scope='module')
-def lcnn(gpu_device):
-    return _whitebox('lightcnn29v2', 8, gpu_device)
-
-
-def _noise(seed, shape):
-    np.random.seed(seed)
-    return np.random.rand(*shape)
-
-
-def _case(name):
-    arch, method, levels, include_zero, _ = I.CASES[name]
-    seed = int(GOLD[name + '/seed'])
-    maps = I.maps_of(name, seed)
-    return dict(arch=arch, method=method, levels=levels, include_zero=include_zero, seed=seed, maps=maps, noise=_noise(seed, maps.shape[1:]))
 
 
 def _guarded(m, levels, seed, include_zero):
@@ -104,21 +69,6 @@ def _score(wb, name):
     cls, pg, pr = eng.inpaint_score(c['maps'], c['levels'], a, b, GOLD[key + '/gal_orig'], GOLD[key + '/gal_inp'], wb.net._mark('encode'),
                                     method=c['method'], noise=c['noise'], include_zero=c['include_zero'])
     return cls.cpu().numpy().astype(bool), pg.cpu().numpy(), pr.cpu().numpy()
-
-
-def _check_scores(name, tag, cls, pg, pr):
-    pg64, pr64, r = GOLD[name + '/pg64'], GOLD[name + '/pr64'], float(GOLD[name + '/r'])
-    top = max(np.abs(pg64).max(), np.abs(pr64).max())
-    err = max(np.abs(pg - pg64).max(), np.abs(pr - pr64).max()) / top
-    keep = ~GOLD[name + '/excluded']
-    flips = int((cls != GOLD[name + '/cls64'])[keep].sum())
-    REPORT['scores/%s%s' % (name, tag)] = {'rel_err_vs_ref64': float(err), 'r_ref32_vs_ref64': r, 'bar': 4 * r, 'class_flips': flips,
-                                           'levels_excluded': int((~keep).sum())}
-    print('%s%s distances: %.3e (r = %.3e, bar %.3e), %d classification flips' % (name, tag, err, r, 4 * r, flips))
-    assert pg.shape == pg64.shape and pg.dtype == np.float64 and np.isfinite(pg).all() and np.isfinite(pr).all()
-    assert err <= 4 * r
-    assert flips == 0
-    assert np.array_equal(cls, pg < pr) and not cls[:, 0].any()
 
 
 # ---- masks -----------------------------------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ Bars (none of them taken from the code under test):
                   numpy's own values; IoU counts exact;
   drop-in         the device path against the same function on the host path: masks and blends equal, distances within 1e-4."""
 import ctypes
-import os
+import functools
 
 import numpy as np
 import pytest
@@ -22,41 +22,16 @@ import torch
 
 import inpaint_game_inputs as I
 import inpaint_soft_inputs as J
-from parity_utils import make_backbone
+import probe_scoring_utils as U
+from probe_scoring_utils import lcnn, mini48      # noqa: F401 (fixtures)
 from xfr_amd import _lib
 from xfr_amd import inpainting_score as S
-from xfr_amd.models import whitebox as WB
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = np.load(os.path.join(ROOT, 'tests', 'golden', 'golden_inpaint_soft.npz'))
+GOLD = U.gold('inpaint_soft')
 MINI_CASES = tuple(n for n in J.CASES if n.startswith('mini/'))
 BLUR_CASES = tuple(n for n in J.CASES if J.CASES[n][5] is not None)
-
-
-def _whitebox(arch, batch, device):
-    bb, _ = make_backbone(arch, seed=0, num_classes=I.NUM_CLASSES[arch])
-    bb.to(device)
-    wbn = WB.WhiteboxSTResnet(bb) if arch != 'lightcnn29v2' else WB.WhiteboxLightCNN(bb)
-    wbn.default_max_batch = batch
-    wb = WB.Whitebox(wbn)
-    wb.batch_size = batch
-    return wb
-
-
-@pytest.fixture(scope='module')
-def mini48(gpu_device):
-    return _whitebox('stresnet_mini', 48, gpu_device)
-
-
-@pytest.fixture(scope='module')
-def lcnn(gpu_device):
-    return _whitebox('lightcnn29v2', 8, gpu_device)
-
-
-def _noise(seed, shape):
-    np.random.seed(seed)
-    return np.random.rand(*shape)
+_whitebox, _noise, _check_scores = U.whitebox, U.noise, functools.partial(U.check_scores, GOLD)
 
 
 def _request(name):
@@ -86,19 +61,6 @@ def _score(wb, name):
     key = name.split('/')[0]
     cls, pg, pr = wb._engine(wb.batch_size).inpaint_score(maps, lv, a, b, GOLD[key + '/gal_orig'], GOLD[key + '/gal_inp'], wb.net._mark('encode'), **kw)
     return cls.cpu().numpy().astype(bool), pg.cpu().numpy(), pr.cpu().numpy()
-
-
-def _check_scores(name, tag, cls, pg, pr):
-    pg64, pr64, r = GOLD[name + '/pg64'], GOLD[name + '/pr64'], float(GOLD[name + '/r'])
-    top = max(np.abs(pg64).max(), np.abs(pr64).max())
-    err = max(np.abs(pg - pg64).max(), np.abs(pr - pr64).max()) / top
-    keep = ~GOLD[name + '/excluded']
-    flips = int((cls != GOLD[name + '/cls64'])[keep].sum())
-    print('%s%s distances: %.3e (r = %.3e, bar %.3e), %d classification flips, %d levels excluded' % (name, tag, err, r, 4 * r, flips, int((~keep).sum())))
-    assert pg.shape == pg64.shape and pg.dtype == np.float64 and np.isfinite(pg).all() and np.isfinite(pr).all()
-    assert err <= 4 * r
-    assert flips == 0
-    assert np.array_equal(cls, pg < pr) and not cls[:, 0].any()
 
 
 # ---- soft masks ------------------------------------------------------------------------------------------------------------------------

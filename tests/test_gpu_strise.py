@@ -15,6 +15,7 @@ Bars (none of them taken from the code under test):
   map            <= 1e-6 against the fixture's float64-run map given the FIXTURE's scores (the merge kernel alone; float32-stored goldens of a
                  [0, 1] map), <= 4 x the fixture's ref32-to-ref64 map distance given the engine's own scores.
 With XFR_STRISE_REPORT=<file> in the environment the measured figures are written there as JSON (profiles/r8/strise_parity.json is such a file)."""
+import functools
 import json
 import os
 
@@ -23,18 +24,18 @@ import pytest
 import scipy.ndimage
 import torch
 
-from parity_utils import make_backbone
-from xfr_amd import synth
+import probe_scoring_utils as U
+from probe_scoring_utils import images, lcnn, mini32, mini48      # noqa: F401 (fixtures)
 from xfr_amd.models import blackbox as BB
-from xfr_amd.models import whitebox as WB
 from xfr_amd.models.resnet import MEAN_RGB
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = np.load(os.path.join(ROOT, 'tests', 'golden', 'golden_strise.npz'))
+GOLD = U.gold('strise')
 MINI_CASES = ('mini/e1', 'mini/e40', 'mini/bcast', 'mini/neg', 'mini/gray')
 SCALE = 12
 REPORT = {}
+_whitebox, _reference_selection = U.whitebox, U.reference_selection
+_strise, _score_error = functools.partial(U.strise, GOLD), functools.partial(U.score_error, GOLD)
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -44,50 +45,6 @@ def _report():
     if REPORT and path:
         with open(path, 'w') as f:
             json.dump(dict(sorted(REPORT.items())), f, indent=1)
-
-
-@pytest.fixture(scope='module')
-def images():
-    """Probe (seed 1), references (2-4), gallery (5-7): the fixture's images."""
-    return [synth.synth_smooth_images(1, (3, 224, 224), seed=s)[0].permute(1, 2, 0).numpy().astype(np.uint8) for s in range(1, 8)]
-
-
-def _whitebox(arch, batch, device, ncls):
-    bb, _ = make_backbone(arch, seed=0, num_classes=ncls)
-    bb.to(device)
-    wbn = WB.WhiteboxSTResnet(bb) if arch != 'lightcnn29v2' else WB.WhiteboxLightCNN(bb)
-    wbn.default_max_batch = batch
-    wb = WB.Whitebox(wbn)
-    wb.batch_size = batch
-    return wb
-
-
-@pytest.fixture(scope='module')
-def mini48(gpu_device):
-    return _whitebox('stresnet_mini', 48, gpu_device, 5)
-
-
-@pytest.fixture(scope='module')
-def mini32(gpu_device):
-    return _whitebox('stresnet_mini', 32, gpu_device, 5)
-
-
-@pytest.fixture(scope='module')
-def lcnn(gpu_device):
-    return _whitebox('lightcnn29v2', 8, gpu_device, 10)
-
-
-def _strise(case, images, wb, **kw):
-    n_refs, n_gal = int(GOLD[case + '/n_refs']), int(GOLD[case + '/n_gal'])
-    args = dict(probe=images[0], refs=list(images[1:1 + n_refs]), gallery=list(images[4:4 + n_gal]), black_box='resnetv4_pytorch',
-                num_masks=int(GOLD[case + '/num_masks']), num_mask_elements=int(GOLD[case + '/num_mask_elements']),
-                mask_fill_type=str(GOLD[case + '/fill']), net=wb)
-    args.update(kw)
-    st = BB.STRise(**args)
-    st.mask_cells = GOLD[case + '/mask_cells'].copy()
-    st.mask_shifts = GOLD[case + '/mask_shifts'].copy()
-    st.apply_masks()
-    return st
 
 
 def _zoom_masks(cells, shifts, g, size):
@@ -114,19 +71,6 @@ def _edge_cells(g, n_masks, n_elem, seed):
     shifts[1] = (SCALE - 1, SCALE - 1)
     shifts[2] = (0, SCALE - 1)
     return cells, shifts
-
-
-def _score_error(case, scores):
-    s32, s64 = GOLD[case + '/scores32'], GOLD[case + '/scores64']
-    top = np.abs(s64).max()
-    return np.abs(np.asarray(scores) - s64).max() / top, np.abs(s32 - s64).max() / top
-
-
-def _reference_selection(scores, positive, percentile=0):
-    """blackbox.py:424-437."""
-    if positive:
-        return scores >= np.percentile(scores[scores > 0], percentile)
-    return -scores >= np.percentile(-scores[scores < 0], percentile)
 
 
 def _reference_map(scores, sel, masks, sign):

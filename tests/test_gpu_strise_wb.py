@@ -13,7 +13,7 @@ Bars (none of them taken from the code under test):
                  is stored as float32, half an ulp of [0.5, 1) -- in the 40-element case the reference's own distance (4.9e-12) lies below it;
   sweep vs hook  the sweep's scores against numpy's float64 evaluation of blackbox.py:385-394 on the encodings of the parity hook's batches: 1e-12
                  (two float64 summation orders over D <= 512 terms of magnitude <= 2: 512 x 2 x 2**-53 = 1.1e-13, and a square root)."""
-import os
+import functools
 import zlib
 
 import numpy as np
@@ -21,53 +21,18 @@ import PIL.Image
 import pytest
 import torch
 
+import probe_scoring_utils as U
 from parity_utils import make_backbone
+from probe_scoring_utils import images, lcnn, mini32, mini48, r50      # noqa: F401 (fixtures)
 from xfr_amd import synth
 from xfr_amd.models import blackbox as BB
-from xfr_amd.models import whitebox as WB
 from xfr_amd.models.lightcnn import prepare_lightCNN_image
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = np.load(os.path.join(ROOT, 'tests', 'golden', 'golden_strise_wb.npz'))
+GOLD = U.gold('strise_wb')
 CASES = ('mini/blur', 'mini/gray', 'mini/e40', 'lcnn/blur', 'r50/blur', 'r101/blur')
 SCALE = 12
-
-
-@pytest.fixture(scope='module')
-def images():
-    """Probe (seed 1), references (2-4), gallery (5-7): the fixture's images."""
-    return [synth.synth_smooth_images(1, (3, 224, 224), seed=s)[0].permute(1, 2, 0).numpy().astype(np.uint8) for s in range(1, 8)]
-
-
-def _whitebox(arch, batch, device, ncls):
-    bb, _ = make_backbone(arch, seed=0, num_classes=ncls)
-    bb.to(device)
-    wbn = {'lightcnn29v2': WB.WhiteboxLightCNN, 'resnet50_128': WB.Whitebox_resnet50_128}.get(arch, WB.WhiteboxSTResnet)(bb)
-    wbn.default_max_batch = batch
-    wb = WB.Whitebox(wbn)
-    wb.batch_size = batch
-    return wb
-
-
-@pytest.fixture(scope='module')
-def mini48(gpu_device):
-    return _whitebox('stresnet_mini', 48, gpu_device, 5)
-
-
-@pytest.fixture(scope='module')
-def mini32(gpu_device):
-    return _whitebox('stresnet_mini', 32, gpu_device, 5)
-
-
-@pytest.fixture(scope='module')
-def lcnn(gpu_device):
-    return _whitebox('lightcnn29v2', 8, gpu_device, 10)
-
-
-@pytest.fixture(scope='module')
-def r50(gpu_device):
-    return _whitebox('resnet50_128', 4, gpu_device, None)
+_whitebox, _score_error = U.whitebox, functools.partial(U.score_error, GOLD)
 
 
 @pytest.fixture(scope='module')
@@ -109,12 +74,6 @@ def _gold_tensor(case, q_gold):
 
 def _box_for(case, mini48, lcnn, r50):
     return {'lightcnn29v2': lcnn, 'resnet50_128': r50}.get(str(GOLD[case + '/arch']), mini48)
-
-
-def _score_error(case, scores):
-    s32, s64 = GOLD[case + '/scores32'], GOLD[case + '/scores64']
-    top = np.abs(s64).max()
-    return np.abs(np.asarray(scores) - s64).max() / top, np.abs(s32 - s64).max() / top
 
 
 def _native_scores(case, wb, images, fills):

@@ -5,7 +5,8 @@
     python tools/isa_digest.py > after.txt        # on the new one; `diff before.txt after.txt` must be empty
 
 Every file is compiled with the Makefile's flags plus `--cuda-device-only -S`.  One line per kernel: the sha256 of its instruction stream (label to
-.Lfunc_end, comments and blank lines stripped, the function index taken out of local labels), its name and its resource figures; a total over all of
+.Lfunc_end, comments and blank lines stripped, the function index taken out of local labels and the kernel's own name out of its descriptor, so
+that a kernel that only changed its name, as a template instantiation does, keeps its hash), its name and its resource figures; a total over all of
 them follows.  --dump DIR also writes each kernel's normalised text, to see what moved.
 """
 import argparse
@@ -19,7 +20,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'xfr_amd', 'csrc')
-DEFAULT_FILES = ('conv_gemm.hip', 'conv_gemm_split.hip', 'elementwise.hip', 'strise.hip')
+DEFAULT_FILES = ('conv_gemm.hip', 'conv_gemm_split.hip', 'elementwise.hip', 'strise.hip', 'inpaint.hip', 'saliency.hip')
 FIGURES = (('vgpr', 'NumVgprs'), ('agpr', 'NumAgprs'), ('sgpr', '(?:Total)?NumSgprs'), ('scratch', 'ScratchSize'), ('lds', 'LDSByteSize'), ('occupancy', 'Occupancy'))
 
 
@@ -55,7 +56,7 @@ def kernels_of(asm):
         while i < len(lines) and not re.match(r'\.Lfunc_end\d+:', lines[i]):
             code = lines[i].split(';', 1)[0].strip()
             if code:
-                body.append(re.sub(r'\.LBB\d+_', '.LBB_', re.sub(r'\s+', ' ', code)))
+                body.append(re.sub(r'\.LBB\d+_', '.LBB_', re.sub(r'\s+', ' ', code)).replace(name, '<kernel>'))
             i += 1
         figures = {}
         while i < len(lines) and not re.match(r'\s*\.(text|section\s+\.text)', lines[i]) and len(figures) < len(FIGURES):

@@ -432,6 +432,33 @@ __device__ inline double wave_sum(double v)
     return v;
 }
 
+// wave_sum, handed to every lane
+__device__ inline double wave_sum_all(double v) { return __shfl(wave_sum(v), 0); }
+
+// One rounded float64 operation each, for the paths of strise.hip and inpaint.hip that are pinned to scipy bit for bit: with contraction switched
+// off where the operator stands, no inlining can fuse a product into a sum.  The __dmul_rn / __dadd_rn of the HIP headers are plain operators
+// compiled under the translation unit's default, which contracts; the call sites of the two families are not interchangeable.
+__device__ inline double mul_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ inline double add_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ inline double sub_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a - b;
+}
+__device__ inline double div_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a / b;
+}
+
 // the float64 form of the minimum / maximum reduction of saliency.hip's subtree_merge_kernel
 __device__ inline void wave_min_max(double& mn, double& mx)
 {
@@ -446,8 +473,8 @@ struct StriseGeom { int H, W, gh, gw, scale, n_elem; double ry, rx; };      // r
 // out [n][3][H][W] = (float)(mask * u8 + (1 - mask) * fill - mean[c]) in float64; probe uint8 H x W x 3, fill float64 H x W x 3
 void launch_strise_masked(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, float* out, const StriseGeom& g,
                           const double* mean, hipStream_t s);
-// out [n][H][W]: the float64 masks (parity hook)
-void launch_strise_masks(const int* cells, const int* shifts, int n, double* out, const StriseGeom& g, hipStream_t s);
+// out [n][H][W]: the float64 masks (parity hook), under the closed-form law or (exact) the exact law of the quantised chain below
+void launch_strise_masks(const int* cells, const int* shifts, int n, bool exact, double* out, const StriseGeom& g, hipStream_t s);
 // orig [n_refs + n_gal] = similarity of emb0 to every reference / gallery embedding, ginv = 1 / |g| of each
 void launch_strise_orig(const float* emb0, const float* refs, int n_refs, const float* gal, int n_gal, int D, double* orig, double* ginv, hipStream_t s);
 // scores[i] = contrastive triplet similarity of embedding first + i, i < count
@@ -466,8 +493,6 @@ void launch_strise_quant(const uint8_t* probe, const double* fill, const int* ce
 // out [n][H][W][3] = q (parity hook)
 void launch_strise_quant_u8(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, uint8_t* out, const StriseGeom& g,
                             hipStream_t s);
-// out [n][H][W]: the float64 masks under the exact law (parity hook)
-void launch_strise_masks_exact(const int* cells, const int* shifts, int n, double* out, const StriseGeom& g, hipStream_t s);
 // one output row or column of PIL's 8-bit bilinear resize: pixels [first, first + count) weighted by coef in 2^-22 (xfr_strise_tap)
 constexpr int STRISE_MAX_TAPS = 8;
 struct StriseTap { int first, count; int coef[STRISE_MAX_TAPS]; };

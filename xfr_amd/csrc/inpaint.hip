@@ -73,24 +73,6 @@ __device__ inline T block_excl_scan(T v, T* s_w)
     return base + inc - v;
 }
 
-// one rounded operation each: with contraction switched off where the operator stands, no inlining can fuse a product into a sum (the
-// __dmul_rn / __dadd_rn of the HIP headers are plain operators compiled under the translation unit's default, which contracts)
-__device__ inline double mul_rn(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ inline double add_rn(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ inline double sub_rn(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a - b;
-}
-
 __device__ inline double noisy(const double* __restrict__ sal, const double* __restrict__ noise, double max_noise, int include_zero, long i)
 {
     const double a = sal[i];
@@ -348,8 +330,6 @@ __global__ __launch_bounds__(NT) void inpaint_soft_masks_kernel(const uint8_t* _
     for (int j = 0; j < 4 && x + j < W; ++j) masks[(size_t)blockIdx.y * HW + (long)y * W + x + j] = s_m[row * TW + (x - x0) + j];
 }
 
-__device__ inline double wave_sum_all(double v) { return __shfl(wave_sum(v), 0); }
-
 // K_inpaint_dist (:134-140), one wavefront per hybrid, float64 from the fp32 embeddings
 __global__ __launch_bounds__(NT) void inpaint_dist_kernel(const float* __restrict__ emb, int count, const float* __restrict__ g_orig,
                                                          const float* __restrict__ g_inp, int D, double* __restrict__ pg, double* __restrict__ pr,
@@ -404,17 +384,18 @@ void launch_inpaint_masks(const double* sal, const double* noise, double max_noi
                        total);
 }
 
+// the soft kernels' grid: (tiles of the image, entries of the list)
+static dim3 soft_grid(int H, int W, int rows) { return dim3((unsigned)(((H + TH - 1) / TH) * ((W + TW - 1) / TW)), rows); }
+
 void launch_inpaint_soft_blend(const uint8_t* first_on, const float* orig, const float* inpaint, float* out, int C, int H, int W, long first, int rows, long total,
                                int n_levels, const InpaintBlur& blur, hipStream_t s)
 {
-    const unsigned tiles = (unsigned)(((H + TH - 1) / TH) * ((W + TW - 1) / TW));
-    hipLaunchKernelGGL(inpaint_soft_blend_kernel, dim3(tiles, rows), dim3(NT), 0, s, first_on, orig, inpaint, out, C, H, W, first, total, n_levels, blur);
+    hipLaunchKernelGGL(inpaint_soft_blend_kernel, soft_grid(H, W, rows), dim3(NT), 0, s, first_on, orig, inpaint, out, C, H, W, first, total, n_levels, blur);
 }
 
 void launch_inpaint_soft_masks(const uint8_t* first_on, double* masks, int H, int W, long first, int rows, int n_levels, const InpaintBlur& blur, hipStream_t s)
 {
-    const unsigned tiles = (unsigned)(((H + TH - 1) / TH) * ((W + TW - 1) / TW));
-    hipLaunchKernelGGL(inpaint_soft_masks_kernel, dim3(tiles, rows), dim3(NT), 0, s, first_on, masks, H, W, first, n_levels, blur);
+    hipLaunchKernelGGL(inpaint_soft_masks_kernel, soft_grid(H, W, rows), dim3(NT), 0, s, first_on, masks, H, W, first, n_levels, blur);
 }
 
 void launch_inpaint_blend(const uint8_t* first_on, const float* orig, const float* inpaint, float* out, int C, long HW, long first, int rows, long total,

@@ -125,33 +125,6 @@ xfr_status check_call(xfr_engine* e, const MaskArgs& a, long h, long w, const xf
     return XFR_OK;
 }
 
-// the masks of all maps into the state's first_on (or the caller's), on `s`
-xfr_status run_masks(xfr_engine* e, const MaskArgs& a, const Options& o, long n, uint8_t* first_on, double* cdf, hipStream_t s)
-{
-    if (!e->inpaint) e->inpaint = new InpaintState();
-    InpaintState* st = e->inpaint;
-    xfr_status rc = grow(&st->scratch, &st->scratch_cap, a.method == XFR_INPAINT_PERCENT_DENSITY ? (size_t)a.n_maps * inpaint_scratch_bytes(n) : (size_t)256);
-    if (rc != XFR_OK) return rc;
-    if (!first_on) {
-        rc = grow(&st->first_on, &st->first_on_cap, (size_t)a.n_maps * n);
-        if (rc != XFR_OK) return rc;
-        first_on = st->first_on;
-    }
-    const int density = a.method == XFR_INPAINT_PERCENT_DENSITY ? 1 : 0;
-    if (!o.per_map) {
-        launch_inpaint_masks(a.sal, a.noise, a.max_noise, a.include_zero, density, o.lv[0], a.n_maps, n, st->scratch, first_on, cdf, s);
-        HIP_TRY(hipGetLastError());
-        return XFR_OK;
-    }
-    for (int m = 0; m < a.n_maps; ++m) {                   // the map's table and total are arguments of its own launch
-        launch_inpaint_masks(a.sal + (size_t)m * n, a.noise, a.max_noise, a.include_zero, density, o.lv[o.lv.size() > 1 ? m : 0], 1, n,
-                             st->scratch + (density ? (size_t)m * inpaint_scratch_bytes(n) : (size_t)0), first_on + (size_t)m * n,
-                             cdf ? cdf + (size_t)m * n : nullptr, s, o.totals ? o.totals[m] : 0.0);
-        HIP_TRY(hipGetLastError());
-    }
-    return XFR_OK;
-}
-
 // the hybrids [first, first + rows) of the list into `out`
 void blend(const Options& o, const uint8_t* first_on, const float* orig, const float* inpaint, float* out, xfr_engine* e, long first, int rows, long total,
            int n_levels, hipStream_t s)
@@ -159,6 +132,69 @@ void blend(const Options& o, const uint8_t* first_on, const float* orig, const f
     if (o.blur.r > 0) launch_inpaint_soft_blend(first_on, orig, inpaint, out, e->in_c, e->in_h, e->in_w, first, rows, total, n_levels, o.blur, s);
     else launch_inpaint_blend(first_on, orig, inpaint, out, e->in_c, (long)e->in_h * e->in_w, first, rows, total, n_levels, s);
 }
+
+// what a call that launched closes with
+xfr_status finish() { HIP_TRY(hipGetLastError()); return XFR_OK; }
+
+// What every entry point opens with.  check(): the refusals in their order -- the engine, the masks and the options, then the entry point's own
+// pointers (args_ok); without h and w the maps have the engine's input size.  The entry point's further checks follow it, then masks(): the sweep's
+// guard on the caller's stream and the masks of all maps there, into the state's first_on (or the caller's).
+struct Call : SweepCall {
+    MaskArgs a;
+    Options o;
+    long HW = 0;
+
+    xfr_status check(xfr_engine* e, const MaskArgs& args, long h, long w, const xfr_inpaint_options* opt, bool blur_allowed, bool args_ok)
+    {
+        if (!e) return fail(XFR_INVALID_ARG, "null engine");
+        a = args;
+        HW = h * w;
+        const xfr_status rc = check_call(e, a, h, w, opt, blur_allowed, &o);
+        if (rc != XFR_OK) return rc;
+        return args_ok ? XFR_OK : fail(XFR_INVALID_ARG, "inpaint: null argument");
+    }
+    xfr_status check(xfr_engine* e, const MaskArgs& args, const xfr_inpaint_options* opt, bool blur_allowed, bool args_ok)
+    {
+        return check(e, args, e ? e->in_h : 0, e ? e->in_w : 0, opt, blur_allowed, args_ok);
+    }
+
+    // [first, first + count) of the list of n_maps x n_levels entries, for the hooks that write one row per entry
+    xfr_status check_range(int first, int count, const char* what) const
+    {
+        const long total = (long)a.n_maps * a.n_levels;
+        if (first < 0 || count < 1 || (long)first + count > total || count > 65535)
+            return fail(XFR_INVALID_ARG, "inpaint: %s [%d, %d + %d) of %ld, at most 65535 per call", what, first, first, count, total);
+        return XFR_OK;
+    }
+
+    xfr_status masks(xfr_engine* e, void* stream, uint8_t* first_on = nullptr, double* cdf = nullptr)
+    {
+        xfr_status rc = enter(e, (hipStream_t)stream);
+        if (rc != XFR_OK) return rc;
+        const long n = HW;
+        if (!e->inpaint) e->inpaint = new InpaintState();
+        InpaintState* st = e->inpaint;
+        rc = grow(&st->scratch, &st->scratch_cap, a.method == XFR_INPAINT_PERCENT_DENSITY ? (size_t)a.n_maps * inpaint_scratch_bytes(n) : (size_t)256);
+        if (rc != XFR_OK) return rc;
+        if (!first_on) {
+            rc = grow(&st->first_on, &st->first_on_cap, (size_t)a.n_maps * n);
+            if (rc != XFR_OK) return rc;
+            first_on = st->first_on;
+        }
+        const int density = a.method == XFR_INPAINT_PERCENT_DENSITY ? 1 : 0;
+        if (!o.per_map) {
+            launch_inpaint_masks(a.sal, a.noise, a.max_noise, a.include_zero, density, o.lv[0], a.n_maps, n, st->scratch, first_on, cdf, s);
+            return finish();
+        }
+        for (int m = 0; m < a.n_maps; ++m) {               // the map's table and total are arguments of its own launch
+            launch_inpaint_masks(a.sal + (size_t)m * n, a.noise, a.max_noise, a.include_zero, density, o.lv[o.lv.size() > 1 ? m : 0], 1, n,
+                                 st->scratch + (density ? (size_t)m * inpaint_scratch_bytes(n) : (size_t)0), first_on + (size_t)m * n,
+                                 cdf ? cdf + (size_t)m * n : nullptr, s, o.totals ? o.totals[m] : 0.0);
+            HIP_TRY(hipGetLastError());
+        }
+        return XFR_OK;
+    }
+};
 
 }  // namespace
 
@@ -169,28 +205,22 @@ xfr_status xfr_inpaint_score_ex(xfr_engine* e, const double* sal_dev, int32_t n_
                                 const float* gal_orig_dev, const float* gal_inp_dev, int32_t encode_tensor, double* pg_dev, double* pr_dev,
                                 uint8_t* cls_dev, const xfr_inpaint_options* opt, void* stream)
 {
-    if (!e) return fail(XFR_INVALID_ARG, "null engine");
-    const MaskArgs a{sal_dev, n_maps, noise_dev, max_noise, include_zero, method, levels_host, n_levels};
-    Options o;
-    xfr_status rc = check_call(e, a, e->in_h, e->in_w, opt, true, &o);
+    Call c;
+    xfr_status rc = c.check(e, {sal_dev, n_maps, noise_dev, max_noise, include_zero, method, levels_host, n_levels}, opt, true,
+                            orig_dev && inpaint_dev && gal_orig_dev && gal_inp_dev && pg_dev && pr_dev && cls_dev);
     if (rc != XFR_OK) return rc;
-    if (!orig_dev || !inpaint_dev || !gal_orig_dev || !gal_inp_dev || !pg_dev || !pr_dev || !cls_dev) return fail(XFR_INVALID_ARG, "inpaint: null argument");
     if (encode_tensor < 1 || encode_tensor >= (int)e->tens.size()) return fail(XFR_INVALID_ARG, "inpaint: bad tensor id %d", encode_tensor);
     if (!e->weights_loaded) return fail(XFR_STATE_ERROR, "weights not loaded");
-    hipStream_t s = (hipStream_t)stream;
-    SweepCall call;
-    rc = call.enter(e, s);
+    rc = c.masks(e, stream);
     if (rc != XFR_OK) return rc;
+    hipStream_t s = c.s;
     const int B = e->max_batch, D = (int)e->tens[encode_tensor].per_n();
-    const long HW = (long)e->in_h * e->in_w;
-    rc = run_masks(e, a, o, HW, nullptr, nullptr, s);
-    if (rc != XFR_OK) return rc;
-    rc = sweep_side_follows(call.sw, s);                   // the masks, and the two images, which may still be in flight on the caller's stream
+    rc = sweep_side_follows(c.sw, s);                      // the masks, and the two images, which may still be in flight on the caller's stream
     if (rc != XFR_OK) return rc;
     const uint8_t* first_on = e->inpaint->first_on;
     const long total = (long)n_maps * n_levels;
-    return run_sweep(e, call.sw, total, encode_tensor, s,
-        [&](long i, float* x, hipStream_t side) { blend(o, first_on, orig_dev, inpaint_dev, x, e, i * B, B, total, n_levels, side); },
+    return run_sweep(e, c.sw, total, encode_tensor, s,
+        [&](long i, float* x, hipStream_t side) { blend(c.o, first_on, orig_dev, inpaint_dev, x, e, i * B, B, total, n_levels, side); },
         [&](long i, const float* emb, hipStream_t) {
             const long lo = i * B, hi = std::min(total, (i + 1) * B);       // hybrids [lo, hi); anything beyond is padding
             launch_inpaint_dist(emb, (int)(hi - lo), gal_orig_dev, gal_inp_dev, D, pg_dev + lo, pr_dev + lo, cls_dev + lo, s);
@@ -201,38 +231,21 @@ xfr_status xfr_inpaint_iou_ex(xfr_engine* e, const double* sal_dev, int32_t n_ma
                               int32_t method, const double* levels_host, int32_t n_levels, const uint8_t* gt_dev, int64_t* counts_dev,
                               const xfr_inpaint_options* opt, void* stream)
 {
-    if (!e) return fail(XFR_INVALID_ARG, "null engine");
-    const MaskArgs a{sal_dev, n_maps, noise_dev, max_noise, include_zero, method, levels_host, n_levels};
-    Options o;
-    xfr_status rc = check_call(e, a, e->in_h, e->in_w, opt, false, &o);
+    Call c;
+    xfr_status rc = c.check(e, {sal_dev, n_maps, noise_dev, max_noise, include_zero, method, levels_host, n_levels}, opt, false, gt_dev && counts_dev);
+    if (rc == XFR_OK) rc = c.masks(e, stream);
     if (rc != XFR_OK) return rc;
-    if (!gt_dev || !counts_dev) return fail(XFR_INVALID_ARG, "inpaint: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    SweepCall call;
-    rc = call.enter(e, s);
-    if (rc != XFR_OK) return rc;
-    const long HW = (long)e->in_h * e->in_w;
-    rc = run_masks(e, a, o, HW, nullptr, nullptr, s);
-    if (rc != XFR_OK) return rc;
-    launch_inpaint_iou(e->inpaint->first_on, gt_dev, HW, n_maps, n_levels, reinterpret_cast<long long*>(counts_dev), s);
-    HIP_TRY(hipGetLastError());
-    return XFR_OK;
+    launch_inpaint_iou(e->inpaint->first_on, gt_dev, c.HW, n_maps, n_levels, reinterpret_cast<long long*>(counts_dev), c.s);
+    return finish();
 }
 
 xfr_status xfr_inpaint_debug_masks_ex(xfr_engine* e, const double* sal_dev, int32_t n_maps, int32_t h, int32_t w, const double* noise_dev,
                                       double max_noise, int32_t include_zero, int32_t method, const double* levels_host, int32_t n_levels,
                                       uint8_t* first_on_dev, double* cdf_dev, const xfr_inpaint_options* opt, void* stream)
 {
-    if (!e) return fail(XFR_INVALID_ARG, "null engine");
-    const MaskArgs a{sal_dev, n_maps, noise_dev, max_noise, include_zero, method, levels_host, n_levels};
-    Options o;
-    xfr_status rc = check_call(e, a, h, w, opt, false, &o);
-    if (rc != XFR_OK) return rc;
-    if (!first_on_dev) return fail(XFR_INVALID_ARG, "inpaint: null argument");
-    SweepCall call;
-    rc = call.enter(e, (hipStream_t)stream);
-    if (rc != XFR_OK) return rc;
-    return run_masks(e, a, o, (long)h * w, first_on_dev, cdf_dev, (hipStream_t)stream);
+    Call c;
+    const xfr_status rc = c.check(e, {sal_dev, n_maps, noise_dev, max_noise, include_zero, method, levels_host, n_levels}, h, w, opt, false, first_on_dev);
+    return rc != XFR_OK ? rc : c.masks(e, stream, first_on_dev, cdf_dev);
 }
 
 xfr_status xfr_inpaint_debug_blends_ex(xfr_engine* e, const double* sal_dev, int32_t n_maps, const double* noise_dev, double max_noise,
@@ -240,54 +253,31 @@ xfr_status xfr_inpaint_debug_blends_ex(xfr_engine* e, const double* sal_dev, int
                                        const float* inpaint_dev, int32_t first, int32_t count, float* out_dev, const xfr_inpaint_options* opt,
                                        void* stream)
 {
-    if (!e) return fail(XFR_INVALID_ARG, "null engine");
-    const MaskArgs a{sal_dev, n_maps, noise_dev, max_noise, include_zero, method, levels_host, n_levels};
-    Options o;
-    xfr_status rc = check_call(e, a, e->in_h, e->in_w, opt, true, &o);
+    Call c;
+    xfr_status rc = c.check(e, {sal_dev, n_maps, noise_dev, max_noise, include_zero, method, levels_host, n_levels}, opt, true,
+                            orig_dev && inpaint_dev && out_dev);
+    if (rc == XFR_OK) rc = c.check_range(first, count, "hybrids");
+    if (rc == XFR_OK) rc = c.masks(e, stream);
     if (rc != XFR_OK) return rc;
-    if (!orig_dev || !inpaint_dev || !out_dev) return fail(XFR_INVALID_ARG, "inpaint: null argument");
-    const long total = (long)n_maps * n_levels;
-    if (first < 0 || count < 1 || (long)first + count > total || count > 65535)
-        return fail(XFR_INVALID_ARG, "inpaint: hybrids [%d, %d + %d) of %ld, at most 65535 per call", first, first, count, total);
-    hipStream_t s = (hipStream_t)stream;
-    SweepCall call;
-    rc = call.enter(e, s);
-    if (rc != XFR_OK) return rc;
-    const long HW = (long)e->in_h * e->in_w;
-    rc = run_masks(e, a, o, HW, nullptr, nullptr, s);
-    if (rc != XFR_OK) return rc;
-    blend(o, e->inpaint->first_on, orig_dev, inpaint_dev, out_dev, e, first, count, total, n_levels, s);
-    HIP_TRY(hipGetLastError());
-    return XFR_OK;
+    blend(c.o, e->inpaint->first_on, orig_dev, inpaint_dev, out_dev, e, first, count, (long)n_maps * n_levels, n_levels, c.s);
+    return finish();
 }
 
 xfr_status xfr_inpaint_debug_soft_masks(xfr_engine* e, const double* sal_dev, int32_t n_maps, const double* noise_dev, double max_noise,
                                         int32_t include_zero, int32_t method, const double* levels_host, int32_t n_levels, int32_t h, int32_t w,
                                         const xfr_inpaint_options* opt, int32_t first, int32_t count, double* masks_dev, void* stream)
 {
-    if (!e) return fail(XFR_INVALID_ARG, "null engine");
-    const MaskArgs a{sal_dev, n_maps, noise_dev, max_noise, include_zero, method, levels_host, n_levels};
-    Options o;
-    xfr_status rc = check_call(e, a, h, w, opt, true, &o);
+    Call c;
+    xfr_status rc = c.check(e, {sal_dev, n_maps, noise_dev, max_noise, include_zero, method, levels_host, n_levels}, h, w, opt, true, masks_dev);
+    if (rc == XFR_OK) rc = c.check_range(first, count, "masks");
+    if (rc == XFR_OK) rc = c.masks(e, stream);
     if (rc != XFR_OK) return rc;
-    if (!masks_dev) return fail(XFR_INVALID_ARG, "inpaint: null argument");
-    const long total = (long)n_maps * n_levels;
-    if (first < 0 || count < 1 || (long)first + count > total || count > 65535)
-        return fail(XFR_INVALID_ARG, "inpaint: masks [%d, %d + %d) of %ld, at most 65535 per call", first, first, count, total);
-    hipStream_t s = (hipStream_t)stream;
-    SweepCall call;
-    rc = call.enter(e, s);
-    if (rc != XFR_OK) return rc;
-    const long HW = (long)h * w;
-    rc = run_masks(e, a, o, HW, nullptr, nullptr, s);
-    if (rc != XFR_OK) return rc;
-    if (o.blur.r == 0) {                                   // no options, or a radius of 0: every level hard, through the same kernel
-        o.blur.half[0] = 1.0;
-        for (int l = 0; l < n_levels; ++l) o.blur.soft[l] = 0;
+    if (c.o.blur.r == 0) {                                 // no options, or a radius of 0: every level hard, through the same kernel
+        c.o.blur.half[0] = 1.0;
+        for (int l = 0; l < n_levels; ++l) c.o.blur.soft[l] = 0;
     }
-    launch_inpaint_soft_masks(e->inpaint->first_on, masks_dev, h, w, first, count, n_levels, o.blur, s);
-    HIP_TRY(hipGetLastError());
-    return XFR_OK;
+    launch_inpaint_soft_masks(e->inpaint->first_on, masks_dev, h, w, first, count, n_levels, c.o.blur, c.s);
+    return finish();
 }
 
 xfr_status xfr_inpaint_score(xfr_engine* e, const double* sal_dev, int32_t n_maps, const double* noise_dev, double max_noise, int32_t include_zero,

@@ -21,23 +21,75 @@ __device__ inline int mirror_index(int i, int g)
     return i > g - 1 ? p - i : i;
 }
 
-// the two taps and the weight of the second one for output coordinate o (shift included) of an axis with g cells; ratio = g / (size + scale), divided
-// once on the host -- the order in which scipy's zoom evaluates the coordinate
-__device__ inline void axis_taps(int o, int g, double ratio, int& i0, int& i1, double& f)
-{
-    const double c = __dsub_rn(__dmul_rn((double)o + 0.5, ratio), 0.5);
-    const double fl = floor(c);
-    f = c - fl;
-    i0 = mirror_index((int)fl, g);
-    i1 = mirror_index((int)fl + 1, g);
-}
+// A mask law is stated once, as a type with  taps(o, g, ratio) -> the two taps i0, i1 and their weights w0, w1  for output coordinate o (shift
+// included) of an axis with g cells,  value(the four grid values, the row's weights, the column's weights)  and what a probe pixel becomes under
+// it: pixel(mask, probe, fill) and input(pixel, mean), the network's fp32 input.  ratio = g / (size + scale), divided once on the host -- the order
+// in which scipy's zoom evaluates the coordinate.
 
-__device__ inline double blend(double v00, double v01, double v10, double v11, double fy, double fx)
-{
-    const double top = __dadd_rn(__dmul_rn(1.0 - fx, v00), __dmul_rn(fx, v01));
-    const double bot = __dadd_rn(__dmul_rn(1.0 - fx, v10), __dmul_rn(fx, v11));
-    return __dadd_rn(__dmul_rn(1.0 - fy, top), __dmul_rn(fy, bot));
-}
+// The law above in closed form, as the float64 sweep and the merge evaluate it: w1 is the coordinate's fraction, and value() takes one minus it
+// where it multiplies instead of reading w0 (the __d*_rn of the HIP headers contract with their surroundings: these expressions stay as they are)
+struct ClosedLaw {
+    static __device__ inline void taps(int o, int g, double ratio, int& i0, int& i1, double& w0, double& w1)
+    {
+        const double c = __dsub_rn(__dmul_rn((double)o + 0.5, ratio), 0.5);
+        const double fl = floor(c);
+        w1 = c - fl;
+        w0 = 1.0 - w1;
+        i0 = mirror_index((int)fl, g);
+        i1 = mirror_index((int)fl + 1, g);
+    }
+
+    static __device__ inline double value(double v00, double v01, double v10, double v11, double, double fy, double, double fx)
+    {
+        const double top = __dadd_rn(__dmul_rn(1.0 - fx, v00), __dmul_rn(fx, v01));
+        const double bot = __dadd_rn(__dmul_rn(1.0 - fx, v10), __dmul_rn(fx, v11));
+        return __dadd_rn(__dmul_rn(1.0 - fy, top), __dmul_rn(fy, bot));
+    }
+
+    // blackbox.py:343 and resnet.py:32,37: mask * u8 + (1 - mask) * fill, then (float)(v - mean[c]), in float64
+    static __device__ inline double pixel(double m, double p, double f) { return __dadd_rn(__dmul_rn(m, p), __dmul_rn(__dsub_rn(1.0, m), f)); }
+    static __device__ inline float input(double v, double mean) { return (float)__dsub_rn(v, mean); }
+};
+
+// The mask law of the generator's black box (eval/generate_inpaintinggame_bb_saliency_maps_multigpu.py:73-101): every masked probe goes through
+// Whitebox.convert_from_numpy (whitebox.py:787-806), which TRUNCATES (v / 255) * 255 to uint8 -- a mask that is 1 - 2^-53 where the closed form gives
+// 1 costs a level.  So this law evaluates scipy's zoom to the bit: one rounded float64 operation per step (common.h), none contracted.  A row of
+// the image list whose shift is negative has no mask (image zero: the unmasked probe, and the padding): q = probe, since
+// uint8((k / 255) * 255) == k for every level and an all-ones mask under this law is not the probe.
+struct ExactLaw {
+    // scipy.ndimage.zoom(order=1, mode='mirror', grid_mode=True) along one axis of g cells, output coordinate o (shift included): only a negative
+    // coordinate is reflected, the second spline weight is one minus the first (not the fraction), the upper tap folds at g - 1
+    static __device__ inline void taps(int o, int g, double ratio, int& i0, int& i1, double& w0, double& w1)
+    {
+        const double cc = sub_rn(mul_rn((double)o + 0.5, ratio), 0.5);
+        const double c = cc < 0.0 ? -cc : cc;
+        const double st = floor(c);
+        w0 = sub_rn(1.0, sub_rn(c, st));
+        w1 = sub_rn(1.0, w0);
+        i0 = min((int)st, g - 1);
+        i1 = i0 + 1;
+        if (i1 > g - 1) i1 = 2 * (g - 1) - i1;
+        if (g == 1) { i0 = i1 = 0; w0 = 1.0; w1 = 0.0; }
+    }
+
+    // scipy's accumulation: from 0.0, rows outermost, each product as (G * wy) * wx
+    static __device__ inline double value(double g00, double g01, double g10, double g11, double wy0, double wy1, double wx0, double wx1)
+    {
+        double t = add_rn(0.0, mul_rn(mul_rn(g00, wy0), wx0));
+        t = add_rn(t, mul_rn(mul_rn(g01, wy0), wx1));
+        t = add_rn(t, mul_rn(mul_rn(g10, wy1), wx0));
+        return add_rn(t, mul_rn(mul_rn(g11, wy1), wx1));
+    }
+
+    // blackbox.py:343 then whitebox.py:794-795,803: np.uint8((v / 255) * 255) of v = mask * probe + (1 - mask) * fill, an IEEE division and
+    // product, truncated (v lies in [0, 255]); then (float)((double)q - mean[c])
+    static __device__ inline int pixel(double m, double p, double f)
+    {
+        const double v = add_rn(mul_rn(m, p), mul_rn(sub_rn(1.0, m), f));
+        return (int)mul_rn(div_rn(v, 255.0), 255.0);
+    }
+    static __device__ inline float input(int q, double mean) { return (float)sub_rn((double)q, mean); }
+};
 
 // the grid of one mask in LDS: 1 everywhere, 0 at its cells (cell < 0: no cell -- the all-ones mask of the unmasked probe and of the padding)
 __device__ inline void build_grid(uint8_t* grid, const int* __restrict__ cells, int n_elem, int cells_total)
@@ -51,9 +103,9 @@ __device__ inline void build_grid(uint8_t* grid, const int* __restrict__ cells, 
     __syncthreads();
 }
 
-// K_strise_masked: the fp32 network input of a batch of masked probes, NCHW, (float)(mask * u8 + (1 - mask) * fill - mean[c]) in float64
-// (blackbox.py:343 and resnet.py:32,37).  One thread: four pixels of a row, the mask once per pixel, three channels; float4 stores along W.  Eight waves per SIMD (64 VGPRs): the kernel runs
-// beside the forward of the batch before and must not take its occupancy.
+// K_strise_masked: the fp32 network input of a batch of masked probes under the closed law, NCHW.  One thread: four pixels of a row, the mask once
+// per pixel, three channels; float4 stores along W.  Eight waves per SIMD (64 VGPRs, 63 used): the kernel runs beside the forward of the batch
+// before and must not take its occupancy.
 __global__ __launch_bounds__(NT, 8) void strise_masked_kernel(const uint8_t* __restrict__ probe, const double* __restrict__ fill, const int* __restrict__ cells,
                                                            const int* __restrict__ shifts, float* __restrict__ out, StriseGeom g, double m0, double m1, double m2)
 {
@@ -65,18 +117,18 @@ __global__ __launch_bounds__(NT, 8) void strise_masked_kernel(const uint8_t* __r
     if (q >= g.H * W4) return;
     const int row = q / W4, x0 = (q - row * W4) * 4;
     const int sx = shifts[2 * k], sy = shifts[2 * k + 1];
+    double m[4];
     int r0, r1;
-    double fy;
-    axis_taps(row + sx, g.gh, g.ry, r0, r1, fy);
+    double wy0, wy1;
+    ClosedLaw::taps(row + sx, g.gh, g.ry, r0, r1, wy0, wy1);
     const uint8_t* g0 = grid + r0 * g.gw;
     const uint8_t* g1 = grid + r1 * g.gw;
-    double m[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         int c0, c1;
-        double fx;
-        axis_taps(min(x0 + j, g.W - 1) + sy, g.gw, g.rx, c0, c1, fx);
-        m[j] = blend((double)g0[c0], (double)g0[c1], (double)g1[c0], (double)g1[c1], fy, fx);
+        double wx0, wx1;
+        ClosedLaw::taps(min(x0 + j, g.W - 1) + sy, g.gw, g.rx, c0, c1, wx0, wx1);
+        m[j] = ClosedLaw::value((double)g0[c0], (double)g0[c1], (double)g1[c0], (double)g1[c1], wy0, wy1, wx0, wx1);
     }
     const double mean[3] = {m0, m1, m2};
     const size_t plane = (size_t)g.H * g.W;
@@ -89,8 +141,7 @@ __global__ __launch_bounds__(NT, 8) void strise_masked_kernel(const uint8_t* __r
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const size_t at = px + 3 * (vec ? j : min(j, g.W - 1 - x0)) + c;
-            const double blended = __dadd_rn(__dmul_rn(m[j], (double)probe[at]), __dmul_rn(__dsub_rn(1.0, m[j]), fill[at]));
-            v[j] = (float)__dsub_rn(blended, mean[c]);
+            v[j] = ClosedLaw::input(ClosedLaw::pixel(m[j], (double)probe[at], fill[at]), mean[c]);
         }
         if (vec) {
             *reinterpret_cast<float4*>(o + c * plane) = make_float4(v[0], v[1], v[2], v[3]);
@@ -100,7 +151,68 @@ __global__ __launch_bounds__(NT, 8) void strise_masked_kernel(const uint8_t* __r
     }
 }
 
-// parity hook: the float64 masks themselves, n x H x W
+// K_strise_quant: strise_masked_kernel for the quantised chain, under the exact law.  U8OUT: the parity hook, q itself as uint8 H x W x 3; else
+// the network input, NCHW, float4 stores.  The two stay two kernels: as one template over (law, output) the closed-law instantiation came out in
+// another register assignment, and strise_masked_kernel sits one register under its limit.
+template <bool U8OUT>
+__global__ __launch_bounds__(NT, 8) void strise_quant_kernel(const uint8_t* __restrict__ probe, const double* __restrict__ fill, const int* __restrict__ cells,
+                                                          const int* __restrict__ shifts, void* __restrict__ out_any, StriseGeom g, double m0, double m1, double m2)
+{
+    __shared__ uint8_t grid[STRISE_MAX_CELLS];
+    const int k = blockIdx.y;
+    build_grid(grid, cells + (size_t)k * g.n_elem, g.n_elem, g.gh * g.gw);
+    const int W4 = (g.W + 3) >> 2;
+    const int q = blockIdx.x * NT + threadIdx.x;
+    if (q >= g.H * W4) return;
+    const int row = q / W4, x0 = (q - row * W4) * 4;
+    const int sx = shifts[2 * k], sy = shifts[2 * k + 1];
+    const bool masked = sx >= 0;
+    double m[4] = {1.0, 1.0, 1.0, 1.0};
+    if (masked) {
+        int r0, r1;
+        double wy0, wy1;
+        ExactLaw::taps(row + sx, g.gh, g.ry, r0, r1, wy0, wy1);
+        const uint8_t* g0 = grid + r0 * g.gw;
+        const uint8_t* g1 = grid + r1 * g.gw;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int c0, c1;
+            double wx0, wx1;
+            ExactLaw::taps(min(x0 + j, g.W - 1) + sy, g.gw, g.rx, c0, c1, wx0, wx1);
+            m[j] = ExactLaw::value((double)g0[c0], (double)g0[c1], (double)g1[c0], (double)g1[c1], wy0, wy1, wx0, wx1);
+        }
+    }
+    const double mean[3] = {m0, m1, m2};
+    const size_t plane = (size_t)g.H * g.W;
+    const size_t px = ((size_t)row * g.W + x0) * 3;
+    const bool vec = (g.W & 3) == 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int lv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const size_t at = px + 3 * (vec ? j : min(j, g.W - 1 - x0)) + c;
+            lv[j] = masked ? ExactLaw::pixel(m[j], (double)probe[at], fill[at]) : (int)probe[at];
+        }
+        if (U8OUT) {
+            uint8_t* o = (uint8_t*)out_any + (size_t)k * 3 * plane + px + c;
+            for (int j = 0; j < 4 && x0 + j < g.W; ++j) o[3 * j] = (uint8_t)lv[j];
+        } else {
+            float* o = (float*)out_any + (size_t)k * 3 * plane + (size_t)row * g.W + x0 + c * plane;
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = ExactLaw::input(lv[j], mean[c]);
+            if (vec) {
+                *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+            } else {
+                for (int j = 0; j < 4 && x0 + j < g.W; ++j) o[j] = v[j];
+            }
+        }
+    }
+}
+
+// parity hook: the float64 masks of a law themselves, n x H x W
+template <class Law>
 __global__ __launch_bounds__(NT) void strise_masks_kernel(const int* __restrict__ cells, const int* __restrict__ shifts, double* __restrict__ out, StriseGeom g)
 {
     __shared__ uint8_t grid[STRISE_MAX_CELLS];
@@ -110,15 +222,12 @@ __global__ __launch_bounds__(NT) void strise_masks_kernel(const int* __restrict_
     if (q >= g.H * g.W) return;
     const int row = q / g.W, x = q - row * g.W;
     int r0, r1, c0, c1;
-    double fy, fx;
-    axis_taps(row + shifts[2 * k], g.gh, g.ry, r0, r1, fy);
-    axis_taps(x + shifts[2 * k + 1], g.gw, g.rx, c0, c1, fx);
-    out[(size_t)k * g.H * g.W + q] = blend((double)grid[r0 * g.gw + c0], (double)grid[r0 * g.gw + c1], (double)grid[r1 * g.gw + c0],
-                                           (double)grid[r1 * g.gw + c1], fy, fx);
+    double wy0, wy1, wx0, wx1;
+    Law::taps(row + shifts[2 * k], g.gh, g.ry, r0, r1, wy0, wy1);
+    Law::taps(x + shifts[2 * k + 1], g.gw, g.rx, c0, c1, wx0, wx1);
+    out[(size_t)k * g.H * g.W + q] = Law::value((double)grid[r0 * g.gw + c0], (double)grid[r0 * g.gw + c1], (double)grid[r1 * g.gw + c0],
+                                                (double)grid[r1 * g.gw + c1], wy0, wy1, wx0, wx1);
 }
-
-// common.h's wavefront sum, handed to every lane
-__device__ inline double wave_sum_all(double v) { return __shfl(wave_sum(v), 0); }
 
 // 1 / |v| of a D-vector, by one wavefront (every lane returns it)
 __device__ inline double wave_inv_norm(const float* __restrict__ v, int D, int lane)
@@ -212,17 +321,17 @@ __global__ __launch_bounds__(NT) void strise_merge_pixels_kernel(const double* _
     double acc = 0.0;
     for (int sx = 0; sx < g.scale; ++sx) {
         int r0, r1;
-        double fy;
-        axis_taps(row + sx, g.gh, g.ry, r0, r1, fy);
+        double wy0, wy1;
+        ClosedLaw::taps(row + sx, g.gh, g.ry, r0, r1, wy0, wy1);
         for (int sy = 0; sy < g.scale; ++sy) {
             const int grp = sx * g.scale + sy;
             const double ws = wsum[grp];
             if (ws == 0.0) continue;
             int c0, c1;
-            double fx;
-            axis_taps(x + sy, g.gw, g.rx, c0, c1, fx);
+            double wx0, wx1;
+            ClosedLaw::taps(x + sy, g.gw, g.rx, c0, c1, wx0, wx1);
             const double* a = A + (size_t)grp * nc;
-            acc += ws - blend(a[r0 * g.gw + c0], a[r0 * g.gw + c1], a[r1 * g.gw + c0], a[r1 * g.gw + c1], fy, fx);
+            acc += ws - ClosedLaw::value(a[r0 * g.gw + c0], a[r0 * g.gw + c1], a[r1 * g.gw + c0], a[r1 * g.gw + c1], wy0, wy1, wx0, wx1);
         }
     }
     sal[q] = sign * (1.0 - acc / count);
@@ -241,142 +350,6 @@ __global__ __launch_bounds__(1024) void strise_normalize_kernel(double* __restri
     for (int i = 1; i < 16; ++i) { mn = fmin(mn, s_mn[i]); mx = fmax(mx, s_mx[i]); }
     const double top = mx - mn;
     for (int i = threadIdx.x; i < n; i += 1024) sal[i] = (sal[i] - mn) / top;
-}
-
-// ---- the generator's black box (eval/generate_inpaintinggame_bb_saliency_maps_multigpu.py:73-101): every masked probe goes through
-// Whitebox.convert_from_numpy (whitebox.py:787-806), which TRUNCATES (v / 255) * 255 to uint8 -- a mask that is 1 - 2^-53 where the law above gives 1
-// costs a level.  So this path evaluates scipy's zoom to the bit: one rounded float64 operation per step, none contracted.
-
-// one rounded operation each (inpaint.hip states the same helpers: the __dmul_rn / __dadd_rn of the HIP headers are plain operators under the
-// translation unit's default contraction)
-__device__ inline double mul_rn(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ inline double add_rn(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ inline double sub_rn(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a - b;
-}
-__device__ inline double div_rn(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a / b;
-}
-
-// scipy.ndimage.zoom(order=1, mode='mirror', grid_mode=True) along one axis of g cells, output coordinate o (shift included): only a negative
-// coordinate is reflected, the second spline weight is one minus the first (not the fraction), the upper tap folds at g - 1
-__device__ inline void exact_taps(int o, int g, double ratio, int& i0, int& i1, double& w0, double& w1)
-{
-    const double cc = sub_rn(mul_rn((double)o + 0.5, ratio), 0.5);
-    const double c = cc < 0.0 ? -cc : cc;
-    const double st = floor(c);
-    w0 = sub_rn(1.0, sub_rn(c, st));
-    w1 = sub_rn(1.0, w0);
-    i0 = min((int)st, g - 1);
-    i1 = i0 + 1;
-    if (i1 > g - 1) i1 = 2 * (g - 1) - i1;
-    if (g == 1) { i0 = i1 = 0; w0 = 1.0; w1 = 0.0; }
-}
-
-// scipy's accumulation: from 0.0, rows outermost, each product as (G * wy) * wx
-__device__ inline double mask_exact(double g00, double g01, double g10, double g11, double wy0, double wy1, double wx0, double wx1)
-{
-    double t = add_rn(0.0, mul_rn(mul_rn(g00, wy0), wx0));
-    t = add_rn(t, mul_rn(mul_rn(g01, wy0), wx1));
-    t = add_rn(t, mul_rn(mul_rn(g10, wy1), wx0));
-    return add_rn(t, mul_rn(mul_rn(g11, wy1), wx1));
-}
-
-// blackbox.py:343 then whitebox.py:794-795,803: np.uint8((v / 255) * 255) of v = mask * probe + (1 - mask) * fill, an IEEE division and product,
-// truncated (v lies in [0, 255])
-__device__ inline int quantize_blend(double m, double p, double f)
-{
-    const double v = add_rn(mul_rn(m, p), mul_rn(sub_rn(1.0, m), f));
-    return (int)mul_rn(div_rn(v, 255.0), 255.0);
-}
-
-// K_strise_quant: strise_masked_kernel for the quantised chain.  A row of the image list whose shift is negative has no mask (image zero: the
-// unmasked probe, and the padding): q = probe, since uint8((k / 255) * 255) == k for every level and an all-ones mask under the exact law is not
-// the probe.  U8OUT: the parity hook, q itself as uint8 H x W x 3; else the network input (float)((double)q - mean[c]), NCHW, float4 stores.
-template <bool U8OUT>
-__global__ __launch_bounds__(NT, 8) void strise_quant_kernel(const uint8_t* __restrict__ probe, const double* __restrict__ fill, const int* __restrict__ cells,
-                                                          const int* __restrict__ shifts, void* __restrict__ out_any, StriseGeom g, double m0, double m1, double m2)
-{
-    __shared__ uint8_t grid[STRISE_MAX_CELLS];
-    const int k = blockIdx.y;
-    build_grid(grid, cells + (size_t)k * g.n_elem, g.n_elem, g.gh * g.gw);
-    const int W4 = (g.W + 3) >> 2;
-    const int q = blockIdx.x * NT + threadIdx.x;
-    if (q >= g.H * W4) return;
-    const int row = q / W4, x0 = (q - row * W4) * 4;
-    const int sx = shifts[2 * k], sy = shifts[2 * k + 1];
-    const bool masked = sx >= 0;
-    double m[4] = {1.0, 1.0, 1.0, 1.0};
-    if (masked) {
-        int r0, r1;
-        double wy0, wy1;
-        exact_taps(row + sx, g.gh, g.ry, r0, r1, wy0, wy1);
-        const uint8_t* g0 = grid + r0 * g.gw;
-        const uint8_t* g1 = grid + r1 * g.gw;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            int c0, c1;
-            double wx0, wx1;
-            exact_taps(min(x0 + j, g.W - 1) + sy, g.gw, g.rx, c0, c1, wx0, wx1);
-            m[j] = mask_exact((double)g0[c0], (double)g0[c1], (double)g1[c0], (double)g1[c1], wy0, wy1, wx0, wx1);
-        }
-    }
-    const double mean[3] = {m0, m1, m2};
-    const size_t plane = (size_t)g.H * g.W;
-    const size_t px = ((size_t)row * g.W + x0) * 3;
-    const bool vec = (g.W & 3) == 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        int lv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const size_t at = px + 3 * (vec ? j : min(j, g.W - 1 - x0)) + c;
-            lv[j] = masked ? quantize_blend(m[j], (double)probe[at], fill[at]) : (int)probe[at];
-        }
-        if (U8OUT) {
-            uint8_t* o = (uint8_t*)out_any + (size_t)k * 3 * plane + px + c;
-            for (int j = 0; j < 4 && x0 + j < g.W; ++j) o[3 * j] = (uint8_t)lv[j];
-        } else {
-            float* o = (float*)out_any + (size_t)k * 3 * plane + (size_t)row * g.W + x0 + c * plane;
-            float v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = (float)sub_rn((double)lv[j], mean[c]);
-            if (vec) {
-                *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-            } else {
-                for (int j = 0; j < 4 && x0 + j < g.W; ++j) o[j] = v[j];
-            }
-        }
-    }
-}
-
-// parity hook: the float64 masks under the exact law, n x H x W
-__global__ __launch_bounds__(NT) void strise_masks_exact_kernel(const int* __restrict__ cells, const int* __restrict__ shifts, double* __restrict__ out, StriseGeom g)
-{
-    __shared__ uint8_t grid[STRISE_MAX_CELLS];
-    const int k = blockIdx.y;
-    build_grid(grid, cells + (size_t)k * g.n_elem, g.n_elem, g.gh * g.gw);
-    const int q = blockIdx.x * NT + threadIdx.x;
-    if (q >= g.H * g.W) return;
-    const int row = q / g.W, x = q - row * g.W;
-    int r0, r1, c0, c1;
-    double wy0, wy1, wx0, wx1;
-    exact_taps(row + shifts[2 * k], g.gh, g.ry, r0, r1, wy0, wy1);
-    exact_taps(x + shifts[2 * k + 1], g.gw, g.rx, c0, c1, wx0, wx1);
-    out[(size_t)k * g.H * g.W + q] = mask_exact((double)grid[r0 * g.gw + c0], (double)grid[r0 * g.gw + c1], (double)grid[r1 * g.gw + c0],
-                                                (double)grid[r1 * g.gw + c1], wy0, wy1, wx0, wx1);
 }
 
 // one pass of PIL's 8-bit resampling (Resample.c, ImagingResampleHorizontal_8bpc): clip8((2^21 + sum pixel * coef) >> 22), pixels `stride` apart
@@ -419,12 +392,12 @@ __global__ __launch_bounds__(NT) void strise_quant_lum_kernel(const uint8_t* __r
         if (masked) {
             int r0, r1, c0, c1;
             double wy0, wy1, wx0, wx1;
-            exact_taps(lo + r + sx, g.gh, g.ry, r0, r1, wy0, wy1);
-            exact_taps(x + sy, g.gw, g.rx, c0, c1, wx0, wx1);
-            const double m = mask_exact((double)grid[r0 * g.gw + c0], (double)grid[r0 * g.gw + c1], (double)grid[r1 * g.gw + c0],
-                                        (double)grid[r1 * g.gw + c1], wy0, wy1, wx0, wx1);
+            ExactLaw::taps(lo + r + sx, g.gh, g.ry, r0, r1, wy0, wy1);
+            ExactLaw::taps(x + sy, g.gw, g.rx, c0, c1, wx0, wx1);
+            const double m = ExactLaw::value((double)grid[r0 * g.gw + c0], (double)grid[r0 * g.gw + c1], (double)grid[r1 * g.gw + c0],
+                                             (double)grid[r1 * g.gw + c1], wy0, wy1, wx0, wx1);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) o[c] = (uint8_t)quantize_blend(m, (double)probe[at + c], fill[at + c]);
+            for (int c = 0; c < 3; ++c) o[c] = (uint8_t)ExactLaw::pixel(m, (double)probe[at + c], fill[at + c]);
         } else {
 #pragma unroll
             for (int c = 0; c < 3; ++c) o[c] = probe[at + c];
@@ -454,22 +427,31 @@ __global__ __launch_bounds__(NT) void strise_quant_lum_kernel(const uint8_t* __r
 
 }  // namespace
 
+// the grid of the kernels that take four pixels of a row per thread and one image per blockIdx.y
+static dim3 quad_grid(const StriseGeom& g, int n) { return dim3((g.H * ((g.W + 3) / 4) + NT - 1) / NT, n); }
+
+void launch_strise_masked(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, float* out, const StriseGeom& g,
+                          const double* mean, hipStream_t s)
+{
+    hipLaunchKernelGGL(strise_masked_kernel, quad_grid(g, n), dim3(NT), 0, s, probe, fill, cells, shifts, out, g, mean[0], mean[1], mean[2]);
+}
+
 void launch_strise_quant(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, float* out, const StriseGeom& g,
                          const double* mean, hipStream_t s)
 {
-    const int quads = g.H * ((g.W + 3) / 4);
-    hipLaunchKernelGGL(strise_quant_kernel<false>, dim3((quads + NT - 1) / NT, n), dim3(NT), 0, s, probe, fill, cells, shifts, (void*)out, g, mean[0], mean[1], mean[2]);
+    hipLaunchKernelGGL(strise_quant_kernel<false>, quad_grid(g, n), dim3(NT), 0, s, probe, fill, cells, shifts, (void*)out, g, mean[0], mean[1], mean[2]);
 }
 
 void launch_strise_quant_u8(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, uint8_t* out, const StriseGeom& g, hipStream_t s)
 {
-    const int quads = g.H * ((g.W + 3) / 4);
-    hipLaunchKernelGGL(strise_quant_kernel<true>, dim3((quads + NT - 1) / NT, n), dim3(NT), 0, s, probe, fill, cells, shifts, (void*)out, g, 0.0, 0.0, 0.0);
+    hipLaunchKernelGGL(strise_quant_kernel<true>, quad_grid(g, n), dim3(NT), 0, s, probe, fill, cells, shifts, (void*)out, g, 0.0, 0.0, 0.0);
 }
 
-void launch_strise_masks_exact(const int* cells, const int* shifts, int n, double* out, const StriseGeom& g, hipStream_t s)
+void launch_strise_masks(const int* cells, const int* shifts, int n, bool exact, double* out, const StriseGeom& g, hipStream_t s)
 {
-    hipLaunchKernelGGL(strise_masks_exact_kernel, dim3((g.H * g.W + NT - 1) / NT, n), dim3(NT), 0, s, cells, shifts, out, g);
+    const dim3 grid((g.H * g.W + NT - 1) / NT, n);
+    if (exact) hipLaunchKernelGGL(strise_masks_kernel<ExactLaw>, grid, dim3(NT), 0, s, cells, shifts, out, g);
+    else hipLaunchKernelGGL(strise_masks_kernel<ClosedLaw>, grid, dim3(NT), 0, s, cells, shifts, out, g);
 }
 
 void launch_strise_quant_lum(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, const StriseTap* row_tab,
@@ -478,18 +460,6 @@ void launch_strise_quant_lum(const uint8_t* probe, const double* fill, const int
     const size_t lds = strise_lum_lds_bytes(rows_max, g.W, in_w);
     hipLaunchKernelGGL(strise_quant_lum_kernel, dim3((in_h + STRISE_LUM_BAND - 1) / STRISE_LUM_BAND, n), dim3(NT), lds, s, probe, fill, cells, shifts, row_tab,
                        col_tab, out, g, in_h, in_w, rows_max, weight[0], weight[1], weight[2]);
-}
-
-void launch_strise_masked(const uint8_t* probe, const double* fill, const int* cells, const int* shifts, int n, float* out, const StriseGeom& g,
-                          const double* mean, hipStream_t s)
-{
-    const int quads = g.H * ((g.W + 3) / 4);
-    hipLaunchKernelGGL(strise_masked_kernel, dim3((quads + NT - 1) / NT, n), dim3(NT), 0, s, probe, fill, cells, shifts, out, g, mean[0], mean[1], mean[2]);
-}
-
-void launch_strise_masks(const int* cells, const int* shifts, int n, double* out, const StriseGeom& g, hipStream_t s)
-{
-    hipLaunchKernelGGL(strise_masks_kernel, dim3((g.H * g.W + NT - 1) / NT, n), dim3(NT), 0, s, cells, shifts, out, g);
 }
 
 void launch_strise_orig(const float* emb0, const float* refs, int n_refs, const float* gal, int n_gal, int D, double* orig, double* ginv, hipStream_t s)

@@ -199,6 +199,48 @@ void launch_generate(xfr_engine* e, const uint8_t* probe, const double* fill, co
     }
 }
 
+// masks [first, first + count) of the parity hooks; with options the range is one of the sweep's image list: first == -1 is image zero, the
+// unmasked probe, and up to `pad` rows behind the last mask are the padding of the last batch
+xfr_status check_range(const StriseOpt& o, int first, int count, int n_masks, int at_most, int pad)
+{
+    if (first < (o.given ? -1 : 0) || count < 1 || (long)first + count > (long)n_masks + (o.given ? pad : 0) || count > at_most)
+        return fail(XFR_INVALID_ARG, "strise: masks [%d, %d + %d) of %d, at most %d per call", first, first, count, n_masks, at_most);
+    return XFR_OK;
+}
+
+// What every entry point opens and closes with.  check(): the refusals in their order -- the masks and the options, the entry point's own pointers
+// (args_ok), then (u8) what the network input needs of the engine.  The entry point's further checks follow it, then begin(): the sweep's guard on
+// the caller's stream and the state; with a range, rows [first, first + count) of the image list as a table on the device (upload_rows).
+struct Call : SweepCall {
+    StriseGeom g;
+    StriseOpt o;
+    StriseState* st = nullptr;
+
+    xfr_status check(xfr_engine* e, const int32_t* cells, const int32_t* shifts, int n_masks, const xfr_strise_geometry* geom,
+                     const xfr_strise_options* opt, bool args_ok, bool u8)
+    {
+        const xfr_status rc = check_masks(e, cells, shifts, n_masks, geom, opt, &g, &o);
+        if (rc != XFR_OK) return rc;
+        if (!args_ok) return fail(XFR_INVALID_ARG, "strise: null argument");
+        return u8 ? check_u8(e, &o) : XFR_OK;
+    }
+
+    xfr_status begin(xfr_engine* e, void* stream)
+    {
+        const xfr_status rc = enter(e, (hipStream_t)stream);
+        if (rc == XFR_OK) st = strise_state(e);
+        return rc;
+    }
+
+    xfr_status begin(xfr_engine* e, void* stream, const int32_t* cells, const int32_t* shifts, int n_masks, long first, long count, const StriseOpt& rows)
+    {
+        const xfr_status rc = begin(e, stream);
+        return rc != XFR_OK ? rc : upload_rows(e, st, cells, shifts, n_masks, g.n_elem, first, count, false, rows, s);
+    }
+
+    static xfr_status finish() { HIP_TRY(hipGetLastError()); return XFR_OK; }
+};
+
 }  // namespace
 
 extern "C" {
@@ -207,23 +249,20 @@ xfr_status xfr_strise_score_ex(xfr_engine* e, const uint8_t* probe_u8_dev, const
                                int32_t n_masks, const xfr_strise_geometry* geom, const float* refs_dev, int32_t n_refs, const float* gallery_dev,
                                int32_t n_gal, int32_t encode_tensor, double* scores_dev, double* orig_dev, const xfr_strise_options* opt, void* stream)
 {
-    StriseGeom g;
-    StriseOpt o;
-    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, opt, &g, &o);
-    if (rc != XFR_OK) return rc;
-    if (!probe_u8_dev || !fill_dev || !refs_dev || !gallery_dev || !scores_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
-    rc = check_u8(e, &o);
+    Call c;
+    xfr_status rc = c.check(e, cells_host, shifts_host, n_masks, geom, opt, probe_u8_dev && fill_dev && refs_dev && gallery_dev && scores_dev, true);
     if (rc != XFR_OK) return rc;
     if (n_refs < 1 || n_gal < 1 || (n_refs != n_gal && n_refs != 1 && n_gal != 1))
         return fail(XFR_INVALID_ARG, "strise: %d references against %d gallery images do not broadcast (equal counts, or one of them 1)", n_refs, n_gal);
     if (encode_tensor < 1 || encode_tensor >= (int)e->tens.size()) return fail(XFR_INVALID_ARG, "bad tensor id");
     if (!e->weights_loaded) return fail(XFR_STATE_ERROR, "weights not loaded");
-    hipStream_t s = (hipStream_t)stream;
-    SweepCall call;
-    rc = call.enter(e, s);
+    rc = c.begin(e, stream);
     if (rc != XFR_OK) return rc;
-    ProbeSweep* sw = call.sw;
-    StriseState* st = strise_state(e);
+    hipStream_t s = c.s;
+    ProbeSweep* sw = c.sw;
+    StriseState* st = c.st;
+    const StriseGeom& g = c.g;
+    const StriseOpt& o = c.o;
     const int B = e->max_batch, D = (int)e->tens[encode_tensor].per_n();
     const int nrg = n_refs + n_gal;
     rc = grow(&st->orig, &st->orig_cap, (size_t)2 * nrg);
@@ -249,8 +288,7 @@ xfr_status xfr_strise_score_ex(xfr_engine* e, const uint8_t* probe_u8_dev, const
         });
     if (rc != XFR_OK) return rc;
     if (orig_dev) HIP_TRY(hipMemcpyAsync(orig_dev, orig, nrg * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipGetLastError());
-    return XFR_OK;
+    return c.finish();
 }
 
 xfr_status xfr_strise_score(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host, const int32_t* shifts_host,
@@ -264,11 +302,10 @@ xfr_status xfr_strise_score(xfr_engine* e, const uint8_t* probe_u8_dev, const do
 xfr_status xfr_strise_combine_ex(xfr_engine* e, const double* weights_dev, int32_t n_selected, const int32_t* cells_host, const int32_t* shifts_host,
                                  int32_t n_masks, const xfr_strise_geometry* geom, int32_t sign, double* sal_dev, const xfr_strise_options* opt, void* stream)
 {
-    StriseGeom g;
-    StriseOpt o;
-    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, opt, &g, &o);
+    Call c;
+    xfr_status rc = c.check(e, cells_host, shifts_host, n_masks, geom, opt, weights_dev && sal_dev, false);
     if (rc != XFR_OK) return rc;
-    if (!weights_dev || !sal_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
+    const StriseGeom& g = c.g;
     if (n_selected < 1 || n_selected > n_masks) return fail(XFR_INVALID_ARG, "strise: %d selected masks of %d", n_selected, n_masks);
     if (sign != 1 && sign != -1) return fail(XFR_INVALID_ARG, "strise: sign must be +1 or -1, got %d", sign);
     const int nc = g.gh * g.gw, ng = g.scale * g.scale;
@@ -293,20 +330,16 @@ xfr_status xfr_strise_combine_ex(xfr_engine* e, const double* weights_dev, int32
         std::vector<int> at(off, off + ng);
         for (int k = 0; k < n_masks; ++k) order[at[shifts_host[2 * k] * g.scale + shifts_host[2 * k + 1]]++] = k;      // index order inside a group
     }
-    hipStream_t s = (hipStream_t)stream;
-    SweepCall call;      // the table may still be read by the side stream of an earlier xfr_strise_score: this call starts behind it
-    rc = call.enter(e, s);
+    rc = c.begin(e, stream);      // the table may still be read by the side stream of an earlier xfr_strise_score: this call starts behind it
     if (rc != XFR_OK) return rc;
-    StriseState* st = strise_state(e);
+    StriseState* st = c.st;
     rc = grow(&st->merge_ws, &st->merge_cap, (size_t)ng * nc + ng);
-    if (rc != XFR_OK) return rc;
-    rc = upload_table(st, tab, s);
+    if (rc == XFR_OK) rc = upload_table(st, tab, c.s);
     if (rc != XFR_OK) return rc;
     const int* order_d = st->tab + (size_t)n_masks * g.n_elem;
     launch_strise_merge(weights_dev, st->tab, order_d, order_d + n_masks, st->merge_ws, st->merge_ws + (size_t)ng * nc, (double)n_selected, (double)sign,
-                        sal_dev, g, s);
-    HIP_TRY(hipGetLastError());
-    return XFR_OK;
+                        sal_dev, g, c.s);
+    return c.finish();
 }
 
 xfr_status xfr_strise_combine(xfr_engine* e, const double* weights_dev, int32_t n_selected, const int32_t* cells_host, const int32_t* shifts_host,
@@ -315,40 +348,18 @@ xfr_status xfr_strise_combine(xfr_engine* e, const double* weights_dev, int32_t 
     return xfr_strise_combine_ex(e, weights_dev, n_selected, cells_host, shifts_host, n_masks, geom, sign, sal_dev, nullptr, stream);
 }
 
-namespace {
-
-// masks [first, first + count) of the parity hooks; with options the range is one of the sweep's image list: first == -1 is image zero, the
-// unmasked probe, and up to `pad` rows behind the last mask are the padding of the last batch
-xfr_status check_range(const StriseOpt& o, int first, int count, int n_masks, int at_most, int pad)
-{
-    if (first < (o.given ? -1 : 0) || count < 1 || (long)first + count > (long)n_masks + (o.given ? pad : 0) || count > at_most)
-        return fail(XFR_INVALID_ARG, "strise: masks [%d, %d + %d) of %d, at most %d per call", first, first, count, n_masks, at_most);
-    return XFR_OK;
-}
-
-}  // namespace
-
 xfr_status xfr_strise_debug_masks_ex(xfr_engine* e, const int32_t* cells_host, const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom,
                                      int32_t first, int32_t count, int32_t exact, double* masks_dev, const xfr_strise_options* opt, void* stream)
 {
-    StriseGeom g;
-    StriseOpt o;
-    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, opt, &g, &o);
+    Call c;
+    xfr_status rc = c.check(e, cells_host, shifts_host, n_masks, geom, opt, masks_dev, false);
     if (rc != XFR_OK) return rc;
-    if (!masks_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
     if (exact != 0 && exact != 1) return fail(XFR_INVALID_ARG, "strise: exact must be 0 or 1, got %d", exact);
     if (first < 0 || count < 1 || (long)first + count > n_masks) return fail(XFR_INVALID_ARG, "strise: masks [%d, %d + %d) of %d", first, first, count, n_masks);
-    hipStream_t s = (hipStream_t)stream;
-    SweepCall call;
-    rc = call.enter(e, s);
+    rc = c.begin(e, stream, cells_host, shifts_host, n_masks, first, count, StriseOpt());
     if (rc != XFR_OK) return rc;
-    StriseState* st = strise_state(e);
-    rc = upload_rows(e, st, cells_host, shifts_host, n_masks, g.n_elem, first, count, false, StriseOpt(), s);
-    if (rc != XFR_OK) return rc;
-    if (exact) launch_strise_masks_exact(st->tab, st->tab + (size_t)count * g.n_elem, count, masks_dev, g, s);
-    else launch_strise_masks(st->tab, st->tab + (size_t)count * g.n_elem, count, masks_dev, g, s);
-    HIP_TRY(hipGetLastError());
-    return XFR_OK;
+    launch_strise_masks(c.st->tab, c.st->tab + (size_t)count * c.g.n_elem, count, exact == 1, masks_dev, c.g, c.s);
+    return c.finish();
 }
 
 xfr_status xfr_strise_debug_masks(xfr_engine* e, const int32_t* cells_host, const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom,
@@ -361,25 +372,13 @@ xfr_status xfr_strise_debug_masked_probes_ex(xfr_engine* e, const uint8_t* probe
                                              const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom, int32_t first, int32_t count,
                                              float* out_dev, const xfr_strise_options* opt, void* stream)
 {
-    StriseGeom g;
-    StriseOpt o;
-    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, opt, &g, &o);
+    Call c;
+    xfr_status rc = c.check(e, cells_host, shifts_host, n_masks, geom, opt, probe_u8_dev && fill_dev && out_dev, true);
+    if (rc == XFR_OK) rc = check_range(c.o, first, count, n_masks, e->max_batch, e->max_batch);
+    if (rc == XFR_OK) rc = c.begin(e, stream, cells_host, shifts_host, n_masks, first, count, c.o);
     if (rc != XFR_OK) return rc;
-    if (!probe_u8_dev || !fill_dev || !out_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
-    rc = check_u8(e, &o);
-    if (rc != XFR_OK) return rc;
-    rc = check_range(o, first, count, n_masks, e->max_batch, e->max_batch);
-    if (rc != XFR_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    SweepCall call;
-    rc = call.enter(e, s);
-    if (rc != XFR_OK) return rc;
-    StriseState* st = strise_state(e);
-    rc = upload_rows(e, st, cells_host, shifts_host, n_masks, g.n_elem, first, count, false, o, s);
-    if (rc != XFR_OK) return rc;
-    launch_generate(e, probe_u8_dev, fill_dev, st->tab, count, 0, count, out_dev, g, o, s);
-    HIP_TRY(hipGetLastError());
-    return XFR_OK;
+    launch_generate(e, probe_u8_dev, fill_dev, c.st->tab, count, 0, count, out_dev, c.g, c.o, c.s);
+    return c.finish();
 }
 
 xfr_status xfr_strise_debug_masked_probes(xfr_engine* e, const uint8_t* probe_u8_dev, const double* fill_dev, const int32_t* cells_host,
@@ -393,26 +392,16 @@ xfr_status xfr_strise_debug_quantized(xfr_engine* e, const uint8_t* probe_u8_dev
                                       const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom, int32_t first, int32_t count,
                                       uint8_t* q_dev, const xfr_strise_options* opt, void* stream)
 {
-    StriseGeom g;
-    StriseOpt o;
     if (e && !opt) return fail(XFR_INVALID_ARG, "strise: xfr_strise_debug_quantized needs options (the probe's size)");
-    xfr_status rc = check_masks(e, cells_host, shifts_host, n_masks, geom, opt, &g, &o);
-    if (rc != XFR_OK) return rc;
-    if (!probe_u8_dev || !fill_dev || !q_dev) return fail(XFR_INVALID_ARG, "strise: null argument");
-    rc = check_range(o, first, count, n_masks, n_masks + 1 + e->max_batch, e->max_batch);
-    if (rc != XFR_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    SweepCall call;
-    rc = call.enter(e, s);
-    if (rc != XFR_OK) return rc;
-    StriseState* st = strise_state(e);
+    Call c;
+    xfr_status rc = c.check(e, cells_host, shifts_host, n_masks, geom, opt, probe_u8_dev && fill_dev && q_dev, false);
+    if (rc == XFR_OK) rc = check_range(c.o, first, count, n_masks, n_masks + 1 + e->max_batch, e->max_batch);
     StriseOpt q;
     q.quant = true;      // rows without a mask: q = probe
-    rc = upload_rows(e, st, cells_host, shifts_host, n_masks, g.n_elem, first, count, false, q, s);
+    if (rc == XFR_OK) rc = c.begin(e, stream, cells_host, shifts_host, n_masks, first, count, q);
     if (rc != XFR_OK) return rc;
-    launch_strise_quant_u8(probe_u8_dev, fill_dev, st->tab, st->tab + (size_t)count * g.n_elem, count, q_dev, g, s);
-    HIP_TRY(hipGetLastError());
-    return XFR_OK;
+    launch_strise_quant_u8(probe_u8_dev, fill_dev, c.st->tab, c.st->tab + (size_t)count * c.g.n_elem, count, q_dev, c.g, c.s);
+    return c.finish();
 }
 
 }  // extern "C"

@@ -540,75 +540,70 @@ class Engine(object):
                                                                                                       tuple(fill.shape)))
         return probe_u8.to(device).contiguous(), fill.to(device, torch.float64).contiguous()
 
+    def _strise_open(self, cells, shifts, grid, mask_scale, probe_shape=None, quantize=False, tables=None, first=0, count=None):
+        """What the STRise methods open with.  -> (n_masks, the four table arguments of the C calls, the options pointer or None, (H, W) of the probe,
+        count with its default: the masks from `first` on, what the pointers refer to)."""
+        cells, shifts, geom, cp, sp = self._strise_tables(cells, shifts, grid, mask_scale)
+        opt, hw, keep = self._strise_options(probe_shape, quantize, tables)
+        n = cells.shape[0]
+        return n, (cp, sp, n, ctypes.byref(geom)), opt, hw, n - first if count is None else int(count), (cells, shifts, geom, keep)
+
+    def _call(self, fn, *args):
+        """One C call on this engine's device and the current stream."""
+        with torch.cuda.device(self.device):
+            _lib.check(fn(self._h, *(args + (_stream_ptr(self.device),))))
+
     def strise_score(self, probe_u8, fill, cells, shifts, grid, mask_scale, refs, gallery, encode_tensor, probe_shape=None, quantize=False, tables=None):
         """The whole STRise sweep of one probe (xfr_strise_score_ex): probe uint8 H x W x 3, fill float64 H x W x 3, refs / gallery fp32 embeddings
         (n x D).  -> (scores float64 [n_masks], orig float64 [n_refs + n_gal]: the unmasked probe's similarities), device tensors.
         quantize: the generator's chain, every masked probe through the uint8 of Whitebox.convert_from_numpy and the engine's own preprocessing."""
-        cells, shifts, geom, cp, sp = self._strise_tables(cells, shifts, grid, mask_scale)
-        opt, hw, keep = self._strise_options(probe_shape, quantize, tables)
+        n, tab, opt, hw, _, keep = self._strise_open(cells, shifts, grid, mask_scale, probe_shape, quantize, tables)
         probe_u8, fill = self._strise_images(probe_u8, fill, hw, self.device)
         d = int(np.prod(self.tensor_shape(encode_tensor)))
         refs = refs.detach().to(self.device, torch.float32).reshape(-1, d).contiguous()
         gallery = gallery.detach().to(self.device, torch.float32).reshape(-1, d).contiguous()
-        scores = torch.empty(cells.shape[0], device=self.device, dtype=torch.float64)
+        scores = torch.empty(n, device=self.device, dtype=torch.float64)
         orig = torch.empty(refs.shape[0] + gallery.shape[0], device=self.device, dtype=torch.float64)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.xfr_strise_score_ex(self._h, probe_u8.data_ptr(), fill.data_ptr(), cp, sp, cells.shape[0], ctypes.byref(geom),
-                                                    refs.data_ptr(), refs.shape[0], gallery.data_ptr(), gallery.shape[0], int(encode_tensor),
-                                                    scores.data_ptr(), orig.data_ptr(), opt, _stream_ptr(self.device)))
+        self._call(self.lib.xfr_strise_score_ex, probe_u8.data_ptr(), fill.data_ptr(), *(tab + (refs.data_ptr(), refs.shape[0], gallery.data_ptr(),
+                   gallery.shape[0], int(encode_tensor), scores.data_ptr(), orig.data_ptr(), opt)))
         return scores, orig
 
     def strise_combine(self, weights, n_selected, cells, shifts, grid, mask_scale, sign=1, probe_shape=None):
         """xfr_strise_combine_ex: weights float64 [n_masks] (0 for unselected masks) -> the normalised H x W float64 map (device tensor)."""
-        cells, shifts, geom, cp, sp = self._strise_tables(cells, shifts, grid, mask_scale)
-        opt, (h, w), keep = self._strise_options(probe_shape, False, None)
+        n, tab, opt, hw, _, keep = self._strise_open(cells, shifts, grid, mask_scale, probe_shape)
         weights = torch.as_tensor(weights).detach().to(self.device, torch.float64).contiguous()
-        if tuple(weights.shape) != (cells.shape[0],):
-            raise ValueError('weights must hold %d values, got %s' % (cells.shape[0], tuple(weights.shape)))
-        sal = torch.empty((h, w), device=self.device, dtype=torch.float64)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.xfr_strise_combine_ex(self._h, weights.data_ptr(), int(n_selected), cp, sp, cells.shape[0], ctypes.byref(geom), int(sign),
-                                                      sal.data_ptr(), opt, _stream_ptr(self.device)))
+        if tuple(weights.shape) != (n,):
+            raise ValueError('weights must hold %d values, got %s' % (n, tuple(weights.shape)))
+        sal = torch.empty(hw, device=self.device, dtype=torch.float64)
+        self._call(self.lib.xfr_strise_combine_ex, weights.data_ptr(), int(n_selected), *(tab + (int(sign), sal.data_ptr(), opt)))
         return sal
 
     def strise_masks(self, cells, shifts, grid, mask_scale, first=0, count=None, probe_shape=None, exact=False):
         """Parity hook: masks [first, first + count) as float64 count x H x W (device tensor); exact: scipy's zoom to the bit
         (xfr_amd.models.blackbox.mask_law_scipy) instead of the closed form (mask_law)."""
-        cells, shifts, geom, cp, sp = self._strise_tables(cells, shifts, grid, mask_scale)
-        opt, (h, w), keep = self._strise_options(probe_shape, False, None)
-        count = cells.shape[0] - first if count is None else int(count)
-        out = torch.empty((max(count, 0), h, w), device=self.device, dtype=torch.float64)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.xfr_strise_debug_masks_ex(self._h, cp, sp, cells.shape[0], ctypes.byref(geom), int(first), count, int(bool(exact)),
-                                                          out.data_ptr(), opt, _stream_ptr(self.device)))
+        n, tab, opt, hw, count, keep = self._strise_open(cells, shifts, grid, mask_scale, probe_shape, first=first, count=count)
+        out = torch.empty((max(count, 0),) + hw, device=self.device, dtype=torch.float64)
+        self._call(self.lib.xfr_strise_debug_masks_ex, *(tab + (int(first), count, int(bool(exact)), out.data_ptr(), opt)))
         return out
 
     def strise_masked_probes(self, probe_u8, fill, cells, shifts, grid, mask_scale, first=0, count=None, probe_shape=None, quantize=False, tables=None):
         """Parity hook: the fp32 network input (count x in_c x in_h x in_w) of masks [first, first + count), count <= max_batch.  With options,
         first = -1 starts at image zero of the sweep, the unmasked probe."""
-        cells, shifts, geom, cp, sp = self._strise_tables(cells, shifts, grid, mask_scale)
-        opt, hw, keep = self._strise_options(probe_shape, quantize, tables)
+        n, tab, opt, hw, count, keep = self._strise_open(cells, shifts, grid, mask_scale, probe_shape, quantize, tables, first, count)
         probe_u8, fill = self._strise_images(probe_u8, fill, hw, self.device)
-        count = cells.shape[0] - first if count is None else int(count)
         c, h, w = self.program.in_shape
         out = torch.empty((max(count, 0), c if opt is not None else 3, h, w), device=self.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.xfr_strise_debug_masked_probes_ex(self._h, probe_u8.data_ptr(), fill.data_ptr(), cp, sp, cells.shape[0], ctypes.byref(geom),
-                                                                  int(first), count, out.data_ptr(), opt, _stream_ptr(self.device)))
+        self._call(self.lib.xfr_strise_debug_masked_probes_ex, probe_u8.data_ptr(), fill.data_ptr(), *(tab + (int(first), count, out.data_ptr(), opt)))
         return out
 
     def strise_quantized(self, probe_u8, fill, cells, shifts, grid, mask_scale, first=0, count=None, probe_shape=None):
         """Parity hook (xfr_strise_debug_quantized): q = uint8((v / 255) * 255) of masks [first, first + count), count x H x W x 3 uint8; first = -1
         starts at image zero of the sweep (q = probe)."""
-        cells, shifts, geom, cp, sp = self._strise_tables(cells, shifts, grid, mask_scale)
-        c, h, w = self.program.in_shape
-        opt, hw, keep = self._strise_options((h, w) if probe_shape is None else probe_shape, True, None)
+        probe_shape = self.program.in_shape[1:] if probe_shape is None else probe_shape
+        n, tab, opt, hw, count, keep = self._strise_open(cells, shifts, grid, mask_scale, probe_shape, True, None, first, count)
         probe_u8, fill = self._strise_images(probe_u8, fill, hw, self.device)
-        count = cells.shape[0] - first if count is None else int(count)
         out = torch.empty((max(count, 0), hw[0], hw[1], 3), device=self.device, dtype=torch.uint8)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.xfr_strise_debug_quantized(self._h, probe_u8.data_ptr(), fill.data_ptr(), cp, sp, cells.shape[0], ctypes.byref(geom),
-                                                           int(first), count, out.data_ptr(), opt, _stream_ptr(self.device)))
+        self._call(self.lib.xfr_strise_debug_quantized, probe_u8.data_ptr(), fill.data_ptr(), *(tab + (int(first), count, out.data_ptr(), opt)))
         return out
 
     # -- inpainting-game scoring (include/xfr_amd.h: xfr_inpaint_*) -----------------------------------------
@@ -674,6 +669,18 @@ class Engine(object):
             raise ValueError('expected the original and its inpainted twin in network format %s, got %s and %s' % (shape, tuple(orig.shape), tuple(inpaint.shape)))
         return orig.detach().to(self.device, torch.float32).contiguous(), inpaint.detach().to(self.device, torch.float32).contiguous()
 
+    def _inpaint_call(self, name, mask_args, tail, opt):
+        """xfr_inpaint_<name> when opt is None, else xfr_inpaint_<name>_ex with opt behind the tail.  mask_args: (sal, noise, max_noise, include_zero,
+        method id, levels pointer, n_levels) -- the leading arguments of every entry point, and (h, w) of the maps behind them where the entry point
+        takes them behind n_maps; tail: its own arguments."""
+        sal, noise, max_noise, include_zero, method, lp, n_levels = mask_args[:7]
+        args = (sal.data_ptr(), sal.shape[0]) + tuple(mask_args[7:]) + (noise.data_ptr() if noise is not None else None, float(max_noise),
+                                                                        1 if include_zero else 0, method, lp, n_levels) + tuple(tail)
+        if opt is None:
+            self._call(getattr(self.lib, 'xfr_inpaint_' + name), *args)
+        else:
+            self._call(getattr(self.lib, 'xfr_inpaint_%s_ex' % name), *(args + (opt,)))
+
     def inpaint_score(self, sal, levels, orig, inpaint, gal_orig, gal_inp, encode_tensor, method='percent-density', noise=None, max_noise=1e-9,
                       include_zero=True, totals=None, levels_per_map=False, blur_kernel=None, blur_levels=None):
         """xfr_inpaint_score: the inpainting game of n_maps maps of one probe.  sal n_maps x H x W float64, levels percentiles (or thresholds), orig /
@@ -693,14 +700,9 @@ class Engine(object):
         pg = torch.empty(shape, device=self.device, dtype=torch.float64)
         pr = torch.empty(shape, device=self.device, dtype=torch.float64)
         cls = torch.empty(shape, device=self.device, dtype=torch.uint8)
-        args = (self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None, float(max_noise), 1 if include_zero else 0, method, lp,
-                n_levels, orig.data_ptr(), inpaint.data_ptr(), gals[0].data_ptr(), gals[1].data_ptr(), int(encode_tensor), pg.data_ptr(), pr.data_ptr(),
-                cls.data_ptr())
-        with torch.cuda.device(self.device):
-            if opt is None:
-                _lib.check(self.lib.xfr_inpaint_score(*(args + (_stream_ptr(self.device),))))
-            else:
-                _lib.check(self.lib.xfr_inpaint_score_ex(*(args + (opt, _stream_ptr(self.device)))))
+        self._inpaint_call('score', (sal, noise, max_noise, include_zero, method, lp, n_levels),
+                           (orig.data_ptr(), inpaint.data_ptr(), gals[0].data_ptr(), gals[1].data_ptr(), int(encode_tensor), pg.data_ptr(), pr.data_ptr(),
+                            cls.data_ptr()), opt)
         return cls, pg, pr
 
     def inpaint_iou(self, sal, levels, ground_truth, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, totals=None,
@@ -714,13 +716,7 @@ class Engine(object):
             raise ValueError('expected a ground truth of %s, got %s' % (tuple(sal.shape[1:]), tuple(gt.shape)))
         gt = (gt != 0).to(self.device, torch.uint8).contiguous()
         counts = torch.empty((sal.shape[0], max(n_levels, 1), 3), device=self.device, dtype=torch.int64)
-        args = (self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None, float(max_noise), 1 if include_zero else 0, method, lp,
-                n_levels, gt.data_ptr(), counts.data_ptr())
-        with torch.cuda.device(self.device):
-            if opt is None:
-                _lib.check(self.lib.xfr_inpaint_iou(*(args + (_stream_ptr(self.device),))))
-            else:
-                _lib.check(self.lib.xfr_inpaint_iou_ex(*(args + (opt, _stream_ptr(self.device)))))
+        self._inpaint_call('iou', (sal, noise, max_noise, include_zero, method, lp, n_levels), (gt.data_ptr(), counts.data_ptr()), opt)
         return counts
 
     def inpaint_masks(self, sal, levels, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, want_cdf=False, totals=None,
@@ -731,13 +727,8 @@ class Engine(object):
         opt, n_levels, keep = self._inpaint_options(sal.shape[0], levels, totals, levels_per_map, **blur)
         first_on = torch.empty(tuple(sal.shape), device=self.device, dtype=torch.uint8)
         cdf = torch.empty(tuple(sal.shape), device=self.device, dtype=torch.float64) if want_cdf else None
-        args = (self._h, sal.data_ptr(), sal.shape[0], sal.shape[1], sal.shape[2], noise.data_ptr() if noise is not None else None, float(max_noise),
-                1 if include_zero else 0, method, lp, n_levels, first_on.data_ptr(), cdf.data_ptr() if want_cdf else None)
-        with torch.cuda.device(self.device):
-            if opt is None:
-                _lib.check(self.lib.xfr_inpaint_debug_masks(*(args + (_stream_ptr(self.device),))))
-            else:
-                _lib.check(self.lib.xfr_inpaint_debug_masks_ex(*(args + (opt, _stream_ptr(self.device)))))
+        self._inpaint_call('debug_masks', (sal, noise, max_noise, include_zero, method, lp, n_levels, sal.shape[1], sal.shape[2]),
+                           (first_on.data_ptr(), cdf.data_ptr() if want_cdf else None), opt)
         return (first_on, cdf) if want_cdf else first_on
 
     def inpaint_soft_masks(self, sal, levels, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, totals=None, levels_per_map=False,
@@ -748,10 +739,9 @@ class Engine(object):
         opt, n_levels, keep = self._inpaint_options(sal.shape[0], levels, totals, levels_per_map, blur_kernel, blur_levels)
         count = sal.shape[0] * n_levels - first if count is None else int(count)
         out = torch.empty((max(count, 0),) + tuple(sal.shape[1:]), device=self.device, dtype=torch.float64)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.xfr_inpaint_debug_soft_masks(self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None,
-                                                             float(max_noise), 1 if include_zero else 0, method, lp, n_levels, sal.shape[1], sal.shape[2],
-                                                             opt, int(first), count, out.data_ptr(), _stream_ptr(self.device)))
+        # one entry point, with the options in the middle of its own arguments
+        self._inpaint_call('debug_soft_masks', (sal, noise, max_noise, include_zero, method, lp, n_levels),
+                           (sal.shape[1], sal.shape[2], opt, int(first), count, out.data_ptr()), None)
         return out
 
     def inpaint_blends(self, sal, levels, orig, inpaint, method='percent-density', noise=None, max_noise=1e-9, include_zero=True, first=0, count=None,
@@ -763,13 +753,8 @@ class Engine(object):
         orig, inpaint = self._inpaint_images(orig, inpaint)
         count = sal.shape[0] * n_levels - first if count is None else int(count)
         out = torch.empty((max(count, 0),) + tuple(self.program.in_shape), device=self.device, dtype=torch.float32)
-        args = (self._h, sal.data_ptr(), sal.shape[0], noise.data_ptr() if noise is not None else None, float(max_noise), 1 if include_zero else 0, method, lp,
-                n_levels, orig.data_ptr(), inpaint.data_ptr(), int(first), count, out.data_ptr())
-        with torch.cuda.device(self.device):
-            if opt is None:
-                _lib.check(self.lib.xfr_inpaint_debug_blends(*(args + (_stream_ptr(self.device),))))
-            else:
-                _lib.check(self.lib.xfr_inpaint_debug_blends_ex(*(args + (opt, _stream_ptr(self.device)))))
+        self._inpaint_call('debug_blends', (sal, noise, max_noise, include_zero, method, lp, n_levels),
+                           (orig.data_ptr(), inpaint.data_ptr(), int(first), count, out.data_ptr()), opt)
         return out
 
     # ------------------------------------------------------------------------------------------------
