@@ -651,6 +651,34 @@ xfr_status XFR_EX xfr_strise_debug_quantized(xfr_engine* e, const uint8_t* probe
                                       const int32_t* shifts_host, int32_t n_masks, const xfr_strise_geometry* geom, int32_t first, int32_t count,
                                       uint8_t* q_dev, const xfr_strise_options* opt, void* stream);
 
+/* ---- Match calibration on embeddings (python/xfr/inpainting_game/net_mate_nonmate_dists.py:118-128, eval/filter_inpaintinggame_for_net.py:105-165,
+ * eval/eccv20.py:53-59).  Additive entry points, ABI version 7. ------------------------------------------------------------------------------
+ * Matrices are row-major float32 on the engine's device; index tables are HOST memory, read before the call returns; the work is enqueued on
+ * `stream`.  The engine lends its device and its error text: no weights are needed.  One distance arithmetic throughout,
+ *     |a - b| = (float) sqrt( sum_d (double)(a[d] - b[d])^2 ),    a[d] - b[d] one float32 subtraction
+ * the single rounding np.linalg.norm(a - b) makes on float32 input, with the sum of squares in float64: identical rows give exactly 0, and nothing
+ * is formed from |a|^2 + |b|^2 - 2 a.b.
+ * XFR_INVALID_ARG before anything is launched, with a text naming the value: a null pointer, a count below 1, 1 <= d <= XFR_MATCH_MAX_D violated, a
+ * row index outside its matrix, an empty group, k outside [1, XFR_MATCH_MAX_K] or above ng - (exclude_same_index != 0), an output that overlaps an
+ * input (by the sizes the counts imply) or the other output. */
+#define XFR_MATCH_MAX_K 64
+#define XFR_MATCH_MAX_D 4096
+/* Templates: group g is rows rows_host[offsets_host[g] .. offsets_host[g + 1]) of emb (n x d; repeats allowed, offsets_host[0] == 0, n_groups + 1
+ * offsets).  normalize_rows != 0: every gathered row is divided by its L2 norm (whitebox.py:778-783), the rows are averaged and the mean is divided
+ * by its norm (filter_inpaintinggame_for_net.py:107-109,143-146; plot_inpainting_game.py:934-943).  normalize_rows == 0: the rows are summed and the
+ * sum is divided by its norm (eccv20.py:53-54).  Norms and sums in float64, every stored value rounded once.  out_dev: n_groups x d. */
+xfr_status XFR_EX xfr_embed_templates(xfr_engine* e, const float* emb_dev, int32_t n, int32_t d, const int32_t* rows_host, const int32_t* offsets_host,
+                                      int32_t n_groups, int32_t normalize_rows, float* out_dev, void* stream);
+/* out_dev[p] = |A[i_p] - B[j_p]| for the n_pairs pairs (i_p, j_p) = (pairs_host[2 p], pairs_host[2 p + 1]); A is na x d, B is nb x d and may be A
+ * (net_mate_nonmate_dists.py:127-128, filter_inpaintinggame_for_net.py:114,149,164-165). */
+xfr_status XFR_EX xfr_pair_dists(xfr_engine* e, const float* a_dev, int32_t na, const float* b_dev, int32_t nb, int32_t d, const int32_t* pairs_host,
+                                 int32_t n_pairs, float* out_dev, void* stream);
+/* The k nearest rows of the gallery (ng x d) to every query (nq x d; may be the gallery itself): idx_dev int32 nq x k and dist_dev float32 nq x k in
+ * increasing distance, equal float32 distances by lower gallery index -- squareform(pdist(X)) and argsort of every row (eccv20.py:57-59) without the
+ * nq x ng matrix.  exclude_same_index != 0: query i ignores gallery row i, the reference's dropped self distance (:58). */
+xfr_status XFR_EX xfr_nearest_rows(xfr_engine* e, const float* q_dev, int32_t nq, const float* g_dev, int32_t ng, int32_t d, int32_t k,
+                                   int32_t exclude_same_index, int32_t* idx_dev, float* dist_dev, void* stream);
+
 /* Debug / parity: after an xfr_ebp call made while tracing is enabled, the per-firing trace
  * sum(P[i]) (what the golden fixtures store for every entry of Whitebox.P, whitebox.py:394).
  * xfr_engine_set_trace(e, 1) makes xfr_ebp record it (slower).  `sums` receives n_firings x S x N doubles

@@ -57,6 +57,7 @@ class InpaintOptions(ctypes.Structure):
 
 
 INPAINT_MAX_BLUR_RADIUS = 64      # XFR_INPAINT_MAX_BLUR_RADIUS
+MATCH_MAX_K, MATCH_MAX_D = 64, 4096      # XFR_MATCH_MAX_K, XFR_MATCH_MAX_D
 
 
 class XfrError(RuntimeError):
@@ -136,6 +137,9 @@ SYMBOLS = [
     ('xfr_inpaint_debug_masks_ex', _I, [_P, _P, _I, _I, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, ctypes.POINTER(InpaintOptions), _P]),
     ('xfr_inpaint_debug_blends_ex', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _P, _P, _I, _I, _P, ctypes.POINTER(InpaintOptions), _P]),
     ('xfr_inpaint_debug_soft_masks', _I, [_P, _P, _I, _P, _D, _I, _I, ctypes.POINTER(_D), _I, _I, _I, ctypes.POINTER(InpaintOptions), _I, _I, _P, _P]),
+    ('xfr_embed_templates', _I, [_P, _P, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _I, _P, _P]),
+    ('xfr_pair_dists', _I, [_P, _P, _I, _P, _I, _I, ctypes.POINTER(_I), _I, _P, _P]),
+    ('xfr_nearest_rows', _I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     ('xfr_ebp_store_firing', _I, [_P, _P, _I, _I, _P, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _P]),
     ('xfr_engine_set_trace', _I, [_P, _I]),
     ('xfr_engine_trace_size', _I, [_P, ctypes.POINTER(_I)]),

@@ -4,6 +4,8 @@ Same names, default subtree modes, match thresholds and Platt scalings as the re
 The reference resolves fixed checkpoint paths under its repository (all of them git-LFS pointers in the public tree);
 here the checkpoint is an explicit argument, and when it is None the backbone keeps its seeded random initialisation
 (a warning is emitted) so that the factory is usable for benchmarks and tests without the weights.
+The thresholds and scalings belong to the reference's own checkpoints: for any other weights compute them with
+xfr_amd.calibration (calc_mate_nonmate_dists, then calibrate(wb, mate_dists, nonmate_dists)).
 """
 import warnings
 

@@ -531,3 +531,15 @@ void launch_inpaint_soft_masks(const uint8_t* first_on, double* masks, int H, in
 void launch_inpaint_dist(const float* emb, int count, const float* g_orig, const float* g_inp, int D, double* pg, double* pr, uint8_t* cls, hipStream_t s);
 // counts [n_maps][n_levels][3] = |gt & mask|, |gt | mask|, |~gt & mask|
 void launch_inpaint_iou(const uint8_t* first_on, const uint8_t* gt, long n, int n_maps, int n_levels, long long* counts, hipStream_t s);
+
+// ---- match calibration (match.hip; net_mate_nonmate_dists.py:118-128, filter_inpaintinggame_for_net.py:105-165, eccv20.py:53-59) ----
+constexpr int MATCH_MAX_K = 64;
+constexpr int MATCH_MAX_D = 4096;
+// out [n_groups][D]: the rows tab[n_groups + 1 + p], p in [tab[g], tab[g + 1]), of emb [.][D], each divided by its norm first when normalize_rows,
+// averaged (summed without normalize_rows) and divided by the norm of the result; float64 throughout, one rounding per stored value
+void launch_embed_templates(const float* emb, int D, const int* tab, int n_groups, int normalize_rows, float* out, hipStream_t s);
+// out [p] = |A[pairs[2 p]] - B[pairs[2 p + 1]]|: float32 differences, their squares summed in float64, one rounding of the root
+void launch_pair_dists(const float* A, const float* B, int D, const int* pairs, int n_pairs, float* out, hipStream_t s);
+// idx, dist [nq][k]: the k nearest rows of G [ng][D] to every row of Q [nq][D] by that distance, ascending, equal distances by lower index;
+// exclude_same_index: query i skips gallery row i.  1 <= k <= MATCH_MAX_K, 1 <= D <= MATCH_MAX_D
+void launch_nearest_rows(const float* Q, long nq, const float* G, long ng, int D, int k, int exclude_same_index, int* idx, float* dist, hipStream_t s);

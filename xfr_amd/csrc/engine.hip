@@ -234,6 +234,7 @@ xfr_status xfr_engine_destroy(xfr_engine* e)
     if (e->wst_store) (void)hipFree(e->wst_store);
     strise_release(e);
     inpaint_release(e);
+    match_release(e);
     sweep_release(e);
     for (int i = 0; i < 3; ++i) { if (e->seedbuf[i]) (void)hipFree(e->seedbuf[i]); if (e->ev_slot_done[i]) (void)hipEventDestroy(e->ev_slot_done[i]); }
     for (int i = 0; i < 3; ++i) {

@@ -9,6 +9,7 @@
 //   probe_sweep.hip    the batched sweep with its side stream that the next two share (ProbeSweep)
 //   strise_abi.hip     the C ABI: STRise blackbox saliency
 //   inpaint_abi.hip    the C ABI: inpainting-game scoring
+//   match_abi.hip      the C ABI: match calibration (templates, pair distances, nearest rows)
 //   comm.hip           the C ABI: the RCCL binding
 //   plan_describe.hip  the C ABI: xfr_plan_describe
 #pragma once
@@ -266,6 +267,7 @@ struct xfr_engine {
     ProbeSweep* sweep = nullptr;            // xfr_strise_* and xfr_inpaint_*: side stream, events, input and embedding buffers, built on first use
     struct StriseState* strise = nullptr;   // xfr_strise_*: the family's own buffers, built on first use (strise_abi.hip)
     struct InpaintState* inpaint = nullptr; // xfr_inpaint_*: the same for inpainting-game scoring (inpaint_abi.hip)
+    struct MatchState* match = nullptr;     // xfr_embed_templates / xfr_pair_dists: the device copy of the caller's index table (match_abi.hip)
 
     float* t_bank = nullptr;       // when set, true activations live in this bank (gallery forward of a triplet step)
     float* ws_enc = nullptr;       // second bank of true activations (T region only), allocated on first use
@@ -377,5 +379,8 @@ void strise_release(xfr_engine* e);
 
 // inpaint_abi.hip
 void inpaint_release(xfr_engine* e);
+
+// match_abi.hip
+void match_release(xfr_engine* e);
 
 }  // namespace xfr

@@ -757,6 +757,60 @@ class Engine(object):
                            (orig.data_ptr(), inpaint.data_ptr(), int(first), count, out.data_ptr()), opt)
         return out
 
+    # -- match calibration (include/xfr_amd.h: xfr_embed_templates, xfr_pair_dists, xfr_nearest_rows) ------------------
+    def _matrix(self, x, what):
+        x = torch.as_tensor(x)
+        if x.dim() != 2:
+            raise ValueError('expected %s as a matrix of rows, got %s' % (what, tuple(x.shape)))
+        return x.detach().to(self.device, torch.float32).contiguous()
+
+    @staticmethod
+    def _int_table(values, shape=None):
+        t = np.ascontiguousarray(np.asarray(values, dtype=np.int64))
+        if shape is not None:
+            t = t.reshape(shape)
+        if t.size and (t.min() < -2 ** 31 or t.max() >= 2 ** 31):
+            raise ValueError('an index table holds int32 values')
+        t = np.ascontiguousarray(t.astype(np.int32))
+        return t, t.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+    def embed_templates(self, emb, rows, offsets, normalize_rows=True):
+        """xfr_embed_templates: emb n x D fp32, rows a list of row indices (repeats allowed), offsets G + 1 places in it.
+        -> G x D fp32 templates (device tensor): the group's rows, each divided by its norm first with normalize_rows, averaged (summed without) and
+        divided by the norm of the result."""
+        emb = self._matrix(emb, 'the embeddings')
+        rows, rp = self._int_table(rows, (-1,))
+        offsets, op = self._int_table(offsets, (-1,))
+        if offsets.size < 2 or offsets[-1] != rows.size:
+            raise ValueError('expected offsets from 0 to the %d rows of the list, got %s' % (rows.size, offsets.tolist()[:8]))
+        out = torch.empty((offsets.size - 1, emb.shape[1]), device=self.device, dtype=torch.float32)
+        self._call(self.lib.xfr_embed_templates, emb.data_ptr(), emb.shape[0], emb.shape[1], rp, op, offsets.size - 1, 1 if normalize_rows else 0,
+                   out.data_ptr())
+        return out
+
+    def pair_dists(self, a, b, pairs):
+        """xfr_pair_dists: a na x D, b nb x D fp32, pairs np x 2 row indices (i into a, j into b) -> |a[i] - b[j]| fp32 [np] (device tensor)."""
+        a, b = self._matrix(a, 'A'), self._matrix(b, 'B')
+        if a.shape[1] != b.shape[1]:
+            raise ValueError('rows of %d and of %d values' % (a.shape[1], b.shape[1]))
+        pairs, pp = self._int_table(pairs, (-1, 2))
+        out = torch.empty(pairs.shape[0], device=self.device, dtype=torch.float32)
+        self._call(self.lib.xfr_pair_dists, a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], a.shape[1], pp, pairs.shape[0], out.data_ptr())
+        return out
+
+    def nearest_rows(self, queries, gallery, k, exclude_same_index=False):
+        """xfr_nearest_rows: the k nearest gallery rows of every query -> (idx int32, dist fp32), nq x k device tensors, in increasing distance,
+        equal distances by lower index; exclude_same_index: query i ignores gallery row i."""
+        q, g = self._matrix(queries, 'the queries'), self._matrix(gallery, 'the gallery')
+        if q.shape[1] != g.shape[1]:
+            raise ValueError('rows of %d and of %d values' % (q.shape[1], g.shape[1]))
+        k = int(k)
+        idx = torch.empty((q.shape[0], max(k, 0)), device=self.device, dtype=torch.int32)
+        dist = torch.empty((q.shape[0], max(k, 0)), device=self.device, dtype=torch.float32)
+        self._call(self.lib.xfr_nearest_rows, q.data_ptr(), q.shape[0], g.data_ptr(), g.shape[0], q.shape[1], k, 1 if exclude_same_index else 0,
+                   idx.data_ptr(), dist.data_ptr())
+        return idx, dist
+
     # ------------------------------------------------------------------------------------------------
     def set_trace(self, on):
         _lib.check(self.lib.xfr_engine_set_trace(self._h, 1 if on else 0))
