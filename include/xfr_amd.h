@@ -687,6 +687,22 @@ xfr_status xfr_engine_set_trace(xfr_engine* e, int32_t enable);
 xfr_status xfr_engine_trace_size(xfr_engine* e, int32_t* n_firings);
 xfr_status xfr_engine_get_trace(xfr_engine* e, double* sums, int32_t* kinds, int32_t capacity);
 
+/* Test hook: the tail of xfr_contrastive_raw -- the per-sample sums, the truncation threshold, the contrast; no blur -- on a tensor the caller
+ * supplies, by exactly the launches the engine makes on its own P[-2].  Additive entry point, ABI version 7.
+ *   p_dev         [c][2 n][hw] float32, the engine's internal channel-major layout: rows 0 .. n-1 the mate sweep, n .. 2n-1 the non-mate sweep
+ *   percentile    0 .. 100: keep m = P / S where m >= the threshold (whitebox.py:550-556); below 0: the plain contrastive form (:524-526) -- no
+ *                 threshold launches, thr_dev is not written
+ *   sums_dev      NULL, or 2 n doubles: the sums S of the 2 n rows over c and hw
+ *   thr_dev       NULL, or n floats: the threshold of every sample, the smallest kept value of m
+ *   contrast_dev  n x hw float32
+ * The engine lends its device and its error text: no weights are needed and n is not bound by max_batch.  The call allocates its own scratch,
+ * enqueues on `stream`, WAITS for the stream and frees the scratch: it is a hook for tests, not for a hot path.
+ * XFR_INVALID_ARG before anything is launched, with a text naming the value: a null e, p_dev or contrast_dev; c, n or hw below 1 (2 n above 65535);
+ * a percentile above 100 or NaN; an output that overlaps p_dev (by the sizes the counts imply); a p_dev that is not 16-byte aligned (the sums read
+ * float4 whenever hw % 4 == 0, as they may on the engine's own aligned workspace). */
+xfr_status XFR_EX xfr_debug_contrast_tail(xfr_engine* e, const float* p_dev, int32_t c, int32_t n, int32_t hw, float percentile, double* sums_dev,
+                                          float* thr_dev, float* contrast_dev, void* stream);
+
 /* Test / tuning hook: one forward convolution through the engine's implicit-GEMM kernel, outside any engine.
  * in_dev/out_dev are CNHW device tensors ([C][NB][H][W]); w_host/bias_host are PyTorch-layout host arrays.
  * cfg % 100: 0 lets the launcher pick the tile configuration, 4 / 5 force the 16- / 32-deep 64x64 configuration;

@@ -60,6 +60,30 @@ def test_error_strings_and_arg_checks():
     assert lib.xfr_engine_set_mode(None, 1, 1e-16, 0) == _lib.XFR_INVALID_ARG
 
 
+def test_debug_contrast_tail_refuses_before_any_device_call():
+    """xfr_debug_contrast_tail checks its arguments before it touches the engine or the device, so the refusals show without either: the pointers
+    here are numbers that are never followed.  (tests/test_gpu_contrast_tail.py repeats them on real buffers and proves nothing was written.)"""
+    lib = _lib.load()
+    e, p, s, t, o = 1 << 20, 1 << 24, 1 << 28, 1 << 29, 1 << 30
+
+    def refused(text, e=e, p=p, c=3, n=2, hw=8, pct=20.0, s=s, t=t, o=o):
+        assert lib.xfr_debug_contrast_tail(e, p, c, n, hw, pct, s, t, o, None) == _lib.XFR_INVALID_ARG
+        assert text in lib.xfr_last_error(), lib.xfr_last_error()
+
+    refused(b'null argument', e=None)
+    refused(b'null argument', p=None)
+    refused(b'null argument', o=None)
+    refused(b'c 0, n 2, hw 8', c=0)
+    refused(b'c 3, n -2, hw 8', n=-2)
+    refused(b'c 3, n 2, hw 0', hw=0)
+    refused(b'percentile 100.5', pct=100.5)
+    refused(b'nan', pct=float('nan'))
+    refused(b'p_dev 0x1000004 is not 16-byte aligned', p=p + 4)
+    refused(b'sums_dev 0x1000010 (32 bytes) overlaps p_dev 0x1000000', s=p + 16)
+    refused(b'thr_dev 0x100017c (8 bytes) overlaps p_dev', t=p + 4 * 3 * 4 * 8 - 4)
+    refused(b'contrast_dev 0xffffc4 (64 bytes) overlaps p_dev', o=p - 60)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason='checks the no-GPU failure mode')
 def test_no_gpu_means_loud_failure_not_fallback():
     from parity_utils import make_backbone, make_images

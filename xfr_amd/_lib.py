@@ -96,6 +96,7 @@ SYMBOLS = [
     ('xfr_triplet_contrastive_u8_host', _I, [_P, _P, _P, _I, _I, _F, _F, _P, _P]),
     ('xfr_engine_wait_inputs_copied', _I, [_P]),
     ('xfr_debug_u8_preprocess', _I, [_P, _P, _I, _P, _P]),
+    ('xfr_debug_contrast_tail', _I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
     ('xfr_engine_set_pipeline', _I, [_P, _I]),
     ('xfr_engine_set_inputs_ready', _I, [_P, _I]),
     ('xfr_engine_set_tail_balance', _I, [_P, _I]),

@@ -736,6 +736,45 @@ xfr_status xfr_debug_u8_preprocess(xfr_engine* e, const uint8_t* x_u8_dev, int32
     return fence_slot0(e, s);
 }
 
+// contrastive_tail's launches (without the blur) on the caller's tensor, with the sums and thresholds readable
+xfr_status xfr_debug_contrast_tail(xfr_engine* e, const float* p_dev, int32_t c, int32_t n, int32_t hw, float percentile, double* sums_dev,
+                                   float* thr_dev, float* contrast_dev, void* stream)
+{
+    if (!e || !p_dev || !contrast_dev)
+        return fail(XFR_INVALID_ARG, "debug_contrast_tail: null argument (e %p, p_dev %p, contrast_dev %p)", (void*)e, (const void*)p_dev, (void*)contrast_dev);
+    if (c < 1 || n < 1 || hw < 1 || n > 32767)
+        return fail(XFR_INVALID_ARG, "debug_contrast_tail: c %d, n %d, hw %d: each at least 1, 2 n at most 65535", c, n, hw);
+    if (!(percentile <= 100.f))
+        return fail(XFR_INVALID_ARG, "debug_contrast_tail: percentile %g: at most 100, or below 0 for the plain contrastive form", (double)percentile);
+    if (((uintptr_t)p_dev & 15) != 0)
+        return fail(XFR_INVALID_ARG, "debug_contrast_tail: p_dev %p is not 16-byte aligned", (const void*)p_dev);
+    {
+        const uintptr_t p0 = (uintptr_t)p_dev, p1 = p0 + (size_t)c * 2 * n * hw * sizeof(float);
+        const struct { const char* name; const void* ptr; size_t bytes; } outs[3] = {{"sums_dev", sums_dev, sizeof(double) * 2 * n},
+                                                                                     {"thr_dev", thr_dev, sizeof(float) * n},
+                                                                                     {"contrast_dev", contrast_dev, sizeof(float) * n * hw}};
+        for (const auto& o : outs)
+            if (o.ptr && (uintptr_t)o.ptr < p1 && p0 < (uintptr_t)o.ptr + o.bytes)
+                return fail(XFR_INVALID_ARG, "debug_contrast_tail: %s %p (%zu bytes) overlaps p_dev %p", o.name, o.ptr, o.bytes, (const void*)p_dev);
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const bool truncated = percentile >= 0.f;
+    const size_t ws_bytes = truncation_scratch_bytes(n), sums_bytes = sizeof(double) * 2 * n;      // both multiples of 8
+    char* scratch = nullptr;
+    HIP_TRY(hipMalloc(&scratch, ws_bytes + sums_bytes + sizeof(float) * n));
+    double* sums = sums_dev ? sums_dev : reinterpret_cast<double*>(scratch + ws_bytes);
+    float* thr = !truncated ? nullptr : thr_dev ? thr_dev : reinterpret_cast<float*>(scratch + ws_bytes + sums_bytes);
+    launch_sample_sums(p_dev, sums, c, 2 * n, hw, s);
+    if (truncated) launch_truncation_threshold(p_dev, sums, percentile, thr, scratch, c, n, hw, s);
+    launch_contrast(p_dev, sums, thr, contrast_dev, c, n, hw, s);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(s);      // the scratch goes away with the call
+    (void)hipFree(scratch);
+    if (err != hipSuccess) return fail(XFR_HIP_ERROR, "debug_contrast_tail: %s", hipGetErrorString(err));
+    return XFR_OK;
+}
+
 xfr_status xfr_engine_set_epilogue_fusion(xfr_engine* e, int32_t enable)
 {
     if (!e) return fail(XFR_INVALID_ARG, "null engine");

@@ -350,6 +350,23 @@ class Engine(object):
                                                     _stream_ptr(self.device)))
         return out
 
+    def contrast_tail(self, P, percentile=None):
+        """Parity hook (xfr_debug_contrast_tail): the tail of contrastive(raw=True) on the caller's P, C x 2N x HW float32 in the engine's internal
+        layout (rows 0 .. N-1 the mate sweep, N .. 2N-1 the non-mate sweep) -> (sums 2N float64, thr N float32 or None for the plain contrastive
+        form, contrast N x HW)."""
+        P = P.detach().to(self.device, torch.float32).contiguous()
+        if P.dim() != 3 or P.shape[1] % 2:
+            raise ValueError('expected P as C x 2N x HW, got %s' % (tuple(P.shape),))
+        c, n, hw = P.shape[0], P.shape[1] // 2, P.shape[2]
+        sums = torch.empty((2 * n,), device=self.device, dtype=torch.float64)
+        thr = None if percentile is None else torch.empty((n,), device=self.device, dtype=torch.float32)
+        out = torch.empty((n, hw), device=self.device, dtype=torch.float32)
+        pct = -1.0 if percentile is None else float(percentile)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.xfr_debug_contrast_tail(self._h, P.data_ptr(), c, n, hw, pct, sums.data_ptr(), None if thr is None else thr.data_ptr(),
+                                                        out.data_ptr(), _stream_ptr(self.device)))
+        return sums, thr, out
+
     # -- "next" row: layerwise / weighted-subtree EBP ---------------------------------------------------
     def firing_count(self, seed_tensor):
         n = ctypes.c_int32()
