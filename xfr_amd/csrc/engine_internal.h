@@ -329,8 +329,9 @@ xfr_status run_conv(xfr_engine* e, const ConvParams& p_in, hipStream_t s);
 void conv_geometry(xfr_engine* e, int k, int NB, ConvParams& p);
 void fuse_forward_only(xfr_engine* e, int k, int B, ConvParams& p, hipStream_t s);
 void fuse_probe_forward(xfr_engine* e, int k, int B, ConvParams& p, hipStream_t s, bool dual = false, bool lean_try = true);
-bool fuse_mfm_forward(xfr_engine* e, int k, int B, bool keep_raw, ConvParams& p);
-xfr_status forward_all(xfr_engine* e, const float* x_dev, int B, int last_tensor, bool with_pos, hipStream_t s);
+bool fuse_mfm_forward(xfr_engine* e, int k, int B, bool keep_raw, ConvParams& p, bool want_pos = true);
+// keep_raw: no positive pass, but a plain-weight backward pass follows (xfr_subtree_weights): the MaxFeatureMap forwards still store the raw halves its VJP reads
+xfr_status forward_all(xfr_engine* e, const float* x_dev, int B, int last_tensor, bool with_pos, hipStream_t s, bool keep_raw = false);
 void lean_prepare(xfr_engine* e, BwdPlan& plan, int B);
 bool lean_applies(xfr_engine* e, BwdPlan& plan, int B);
 

@@ -28,7 +28,7 @@ EwStep& push(EwChain& ch, int type)
 
 }  // namespace
 
-static xfr_status fwd_op(xfr_engine* e, int k, int B, bool want_pos, hipStream_t s);
+static xfr_status fwd_op(xfr_engine* e, int k, int B, bool want_pos, hipStream_t s, bool keep_raw = false);
 static xfr_status pos_op(xfr_engine* e, int k, int B, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -314,7 +314,7 @@ void fuse_probe_forward(xfr_engine* e, int k, int B, ConvParams& p, hipStream_t 
 // the two halves interleaved, so a channel and its partner are neighbouring rows of one accumulator tile: the epilogue stores the raw
 // rows where the Split hook and the VJP expect them (keep_raw; a forward-only run needs neither) and the even rows store the maximum.
 // Returns false -- nothing fused, the three ops run as before -- where the float4 epilogue does not apply.
-bool fuse_mfm_forward(xfr_engine* e, int k, int B, bool keep_raw, ConvParams& p)
+bool fuse_mfm_forward(xfr_engine* e, int k, int B, bool keep_raw, ConvParams& p, bool want_pos)
 {
     const OpRec& o = e->ops[k];
     if (!o.pair || o.pair_max > e->fwd_last_op || e->interpret_chains) return false;      // the interpreter has no EW_MAXPAIR
@@ -337,7 +337,7 @@ bool fuse_mfm_forward(xfr_engine* e, int k, int B, bool keep_raw, ConvParams& p)
             const int other = ad.d.in0 == tmax ? ad.d.in1 : ad.d.in0;
             if (kc <= e->fwd_last_op && ad.d.kind == XFR_OP_ADD && !ad.fuse_relu && other != tmax && e->tens[other].producer < k &&
                 e->tens[other].alias < 0) {
-                if (keep_raw && e->tens[ad.d.out].need_pv) {
+                if (keep_raw && want_pos && e->tens[ad.d.out].need_pv) {      // (raw rows without a positive pass: the weights pass, no positive Add output)
                     EwStep& q = push(ch, EW_FORK_POSADD);
                     q.p0 = e->T(other);
                     q.pstore = e->Pv(ad.d.out);
@@ -411,7 +411,7 @@ static bool fuse_pool2_forward(xfr_engine* e, int k, int B, bool want_pos, hipSt
 }
 
 // forward of op k on true values (and, for "dual" convolutions, the positive output in the same launch)
-static xfr_status fwd_op(xfr_engine* e, int k, int B, bool want_pos, hipStream_t s)
+static xfr_status fwd_op(xfr_engine* e, int k, int B, bool want_pos, hipStream_t s, bool keep_raw)
 {
     OpRec& o = e->ops[k];
     const xfr_op_desc& d = o.d;
@@ -441,12 +441,12 @@ static xfr_status fwd_op(xfr_engine* e, int k, int B, bool want_pos, hipStream_t
             // Light-CNN's first layer (one input channel, 5x5, MaxFeatureMap): a direct convolution instead of a 25-deep GEMM
             if (o.pair && e->fuse_fwd_only && e->direct_stem && !dual && !p.relu_in && a.C == 1 && d.kh == 5 && d.kw == 5 && d.stride == 1 && d.pad == 2 &&
                 !o.tap_fwd && !o.tap4_fwd && o.pair_max <= e->fwd_last_op && !e->interpret_chains && stem5_mfm_ok(e->T(d.in0), B, a.H, a.W)) {
-                if (!e->dry_run) launch_stem5_mfm(e->T(d.in0), p.w, o.ldw, p.bias, want_pos ? e->T(d.out) : nullptr, e->T(e->ops[o.pair_max].d.out), o.pair, B, a.H, a.W, s);
+                if (!e->dry_run) launch_stem5_mfm(e->T(d.in0), p.w, o.ldw, p.bias, (want_pos || keep_raw) ? e->T(d.out) : nullptr, e->T(e->ops[o.pair_max].d.out), o.pair, B, a.H, a.W, s);
                 e->fwd_done[o.pair_split] = 1;
                 e->fwd_done[o.pair_max] = 1;
                 return XFR_OK;
             }
-            if (o.pair && e->fuse_fwd_only && !dual && !p.relu_in && fuse_mfm_forward(e, k, B, want_pos, p)) { }
+            if (o.pair && e->fuse_fwd_only && !dual && !p.relu_in && fuse_mfm_forward(e, k, B, want_pos || keep_raw, p, want_pos)) { }
             else if (!want_pos && e->fuse_fwd_only && !p.relu_in) fuse_forward_only(e, k, B, p, s);
             else if (want_pos && e->fuse_probe_fwd && !p.relu_in) fuse_probe_forward(e, k, B, p, s, dual);
             if (p.chain.n > 0 && p.chain.s[0].type == EW_LEAN_Q) {
@@ -560,7 +560,7 @@ static xfr_status pos_op(xfr_engine* e, int k, int B, hipStream_t s)
     return fail(XFR_UNSUPPORTED_LAYER, "positive pass: kind %d cannot have a computed positive value", d.kind);
 }
 
-xfr_status forward_all(xfr_engine* e, const float* x_dev, int B, int last_tensor, bool with_pos, hipStream_t s)
+xfr_status forward_all(xfr_engine* e, const float* x_dev, int B, int last_tensor, bool with_pos, hipStream_t s, bool keep_raw)
 {
     // xfr_engine_hold_forward: consecutive calls on the same input share one forward (slot 0, main bank only)
     const bool holdable = e->hold_forward && e->cur_slot == 0 && !e->t_bank;
@@ -579,7 +579,7 @@ xfr_status forward_all(xfr_engine* e, const float* x_dev, int B, int last_tensor
     e->fwd_last_op = last_op;
     for (int k = 0; k <= last_op; ++k) {
         xfr_status st = XFR_OK;
-        if (!e->fwd_done[k]) st = fwd_op(e, k, B, with_pos, s);
+        if (!e->fwd_done[k]) st = fwd_op(e, k, B, with_pos, s, keep_raw);
         if (st != XFR_OK) return st;
         if (with_pos) {
             const Tensor& t = e->tens[e->ops[k].d.out];

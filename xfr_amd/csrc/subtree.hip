@@ -38,7 +38,7 @@ xfr_status xfr_subtree_weights(xfr_engine* e, const float* x_dev, int32_t n, int
     if (st != XFR_OK) return st;
     const int nf = plan->n_firings;
     if (capacity < nf * n) return fail(XFR_INVALID_ARG, "need room for %d x %d values", nf, n);
-    st = forward_all(e, x_dev, n, seed_tensor, false, s);
+    st = forward_all(e, x_dev, n, seed_tensor, false, s, true);       // no positive pass, but the MaxFeatureMap VJPs below read the raw halves
     if (st != XFR_OK) return st;
     const Tensor& sd = e->tens[seed_tensor];
     launch_seed_to_cnhw(seed_dev, e->G(seed_tensor), 2 * n, sd.C, sd.HW(), s);
@@ -177,6 +177,10 @@ static xfr_status layerwise_run(xfr_engine* e, const float* x_dev, int32_t n, in
     bool ascending = n_sweeps > 1;
     for (int j = 1; j < n_sweeps; ++j) ascending = ascending && first[j] >= first[j - 1];
     if (ascending && !e->trace_on) e->rc_active = first;
+    // A sweep that is idle for every image (first[j] == nf) never joins the prefix launches, so nothing would write its rows of P[-2]: they are zeroed
+    // below, before the sweep (the launches that honour the prefix leave them alone, those that walk every row write the zeros the on-demand zeroing feeds them)
+    int live_sweeps = n_sweeps;
+    while (live_sweeps > 0 && first[live_sweeps - 1] >= nf) --live_sweeps;
     // one forward for all sweeps (whitebox.py:581 runs ebp(img, 0*P0) again for every layer); zero seeds: all the
     // gradient enters through the priors
     e->rc_priors = true;
@@ -192,6 +196,12 @@ static xfr_status layerwise_run(xfr_engine* e, const float* x_dev, int32_t n, in
         if (!e->rc_active.empty() && (eager || poison))
             HIP_TRY(hipMemsetAsync(e->ws + e->g_begin, eager ? 0 : 0xFF, (e->g_end - e->g_begin) * sizeof(float), s));
         launch_fill(e->G(seed_tensor), (long)sd.per_n() * rows, 0.f, s);
+        if (!e->rc_active.empty() && live_sweeps < n_sweeps) {
+            const Tensor& tp = e->tens[1];
+            const size_t hw = (size_t)tp.HW();
+            (void)hipMemset2DAsync(e->ws + e->tap_off + (size_t)live_sweeps * n * hw, (size_t)rows * hw * sizeof(float), 0,
+                                   (size_t)(n_sweeps - live_sweeps) * n * hw * sizeof(float), (size_t)tp.C, s);
+        }
         st = run_backward(e, *plan, n, n_sweeps, s);
     }
     e->rc_active.clear();
