@@ -679,6 +679,32 @@ xfr_status XFR_EX xfr_pair_dists(xfr_engine* e, const float* a_dev, int32_t na, 
 xfr_status XFR_EX xfr_nearest_rows(xfr_engine* e, const float* q_dev, int32_t nq, const float* g_dev, int32_t ng, int32_t d, int32_t k,
                                    int32_t exclude_same_index, int32_t* idx_dev, float* dist_dev, void* stream);
 
+/* ---- Saliency finishing (python/xfr/show.py:196-222 create_save_smap, :131-137 processSaliency, :46-129 blend_saliency_map).  An additive entry
+ * point, ABI version 7. -----------------------------------------------------------------------------------------------------------------------
+ * What the generator does to every map between producing it and storing it, for n float32 maps of h x w and probes of out_h x out_w:
+ *     float32 head     s = m - min(m);  total = the float32 nearest to the sum of s, accumulated in float64 in a fixed order (totals_host[i] instead,
+ *                      where given: numpy's own float32 sum);  s = s / total, a correctly rounded float32 quotient.  total == 0 (a constant map)
+ *                      gives the all-zero map; numpy's 0 / 0 makes it NaN
+ *     normalise        a = (double)s - min;  a = a / (max + 1e-9)
+ *     resize           scipy.ndimage.zoom(a, order=3, mode='grid-constant', cval=0, grid_mode=True) in closed form -- 12 zeros on every side, the
+ *                      B-spline prefilter with pole sqrt(3) - 2 along axis 0 then axis 1, 16 taps at x = (o + 0.5) (in / out) - 0.5 + 12 -- clipped
+ *                      to [min(a.min, 0), max(a.max, 0)].  out_h x out_w == h x w: a itself, bit for bit
+ *     overlay          only with probes (uint8, n x out_h x out_w x 3, img = k / 255.0): att = v - min(v) over the finished map; max(att) <= 0: the
+ *                      image; else att /= max, alpha = att^0.8, colour = table[min(int(att * 256), 255)] (255 at att >= 1), and the byte is
+ *                      uint8(clip((1 - alpha) img + alpha colour, 0, 1) * 255), truncated.  jet_lut_host: the 256 x 3 float64 table, HOST memory
+ * Float64 throughout behind the head, no operation contracted; a map's bits depend on the map alone, not on n, its place in the batch or the launch.
+ * maps_dev, probes_u8_dev and the outputs are on the engine's device; totals_host and jet_lut_host are read before the call returns; the work is
+ * enqueued on `stream`.  The engine lends its device and its error text and owns the call's workspace: no weights are needed.
+ * XFR_INVALID_ARG before anything is launched, with a text naming the value: a null engine, maps or sal_out_dev; n outside [1, XFR_FINISH_MAX_MAPS];
+ * an axis outside [1, XFR_FINISH_MAX_DIM]; a shrinking axis (out < in: the Gaussian pre-filter path stays on the host); an output size the zoom's
+ * own rounding would not produce; probes without a table or without overlay_out_dev, or an overlay output without probes; a total that is negative
+ * or not finite; buffers that overlap (by the sizes the counts imply). */
+#define XFR_FINISH_MAX_MAPS 65535
+#define XFR_FINISH_MAX_DIM 4096
+xfr_status XFR_EX xfr_finish_saliency(xfr_engine* e, const float* maps_dev, int32_t n, int32_t h, int32_t w, int32_t out_h, int32_t out_w,
+                                      const float* totals_host, const uint8_t* probes_u8_dev, const double* jet_lut_host, double* sal_out_dev,
+                                      uint8_t* overlay_out_dev, void* stream);
+
 /* Debug / parity: after an xfr_ebp call made while tracing is enabled, the per-firing trace
  * sum(P[i]) (what the golden fixtures store for every entry of Whitebox.P, whitebox.py:394).
  * xfr_engine_set_trace(e, 1) makes xfr_ebp record it (slower).  `sums` receives n_firings x S x N doubles

@@ -54,8 +54,13 @@ def main():
                     help='group mode: job groups in flight per GPU -- that many engines, each on its own host thread and stream; a second one fills the launch '
                          'gaps and host synchronisation points of the first (bench.py: 82 -> 121 jobs/s; an engine for 128 images is ~95 GB of workspace)')
     ap.add_argument('--native-subtree', action='store_true', help='weighted subtree EBP as one engine call (xfr_weighted_subtree_ebp)')
+    ap.add_argument('--native-finish', action='store_true',
+                    help='group mode with --output-dir: the maps of a job group are normalised, resized and overlaid in one device call '
+                         '(xfr_finish_saliency) on the probes as uint8, and written by saliency_io.save_finished; default: create_save_smap per map on the host')
     ap.add_argument('--numpy-inputs', action='store_true', help='uint8 H x W x 3 images through convert_from_numpy (PIL) per call, like the reference')
     args = ap.parse_args()
+    if args.native_finish and not (args.group > 1 and args.output_dir):
+        ap.error('--native-finish finishes the maps of a job group: it needs --group above 1 and --output-dir')
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -145,11 +150,19 @@ def main():
                                       timings=phase if (args.phases and len(wbs) == 1) else None, native_subtree=args.native_subtree)
             torch.cuda.current_stream(dev).synchronize()
             dt_g = time.perf_counter() - t1
+            finished = None
+            if args.native_finish:      # every map of the group in one call, each on its job's probe
+                maps = np.stack([np.asarray(res[key][i], dtype=np.float32) for i in range(len(todo)) for key in names])
+                probes = [(displayable(jobs[i][2]) * 255).astype(np.uint8) for i in range(len(todo)) for _ in names]
+                finished = [t.cpu().numpy() for t in SIO.finish_maps(wbs[w].net._engine, maps, probes)]
             for i, (job, odir) in enumerate(todo):
-                for key, nm in names.items():
+                for j, (key, nm) in enumerate(names.items()):
                     m = np.asarray(res[key][i])
                     assert m.shape == (112, 112) and np.isfinite(m).all() and abs(float(m.sum()) - 1.0) < 1e-3
-                    if odir:
+                    if finished is not None:
+                        SIO.save_finished(odir, '%05d' % job, nm, finished[0][i * len(names) + j], finished[1][i * len(names) + j])
+                        wr += 1
+                    elif odir:
                         wr += int(SIO.create_save_smap(nm, odir, True, lambda m=m: m, '%05d' % job, displayable(jobs[i][2])))
         with lock:
             counts['written'] += wr

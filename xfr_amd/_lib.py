@@ -58,6 +58,7 @@ class InpaintOptions(ctypes.Structure):
 
 INPAINT_MAX_BLUR_RADIUS = 64      # XFR_INPAINT_MAX_BLUR_RADIUS
 MATCH_MAX_K, MATCH_MAX_D = 64, 4096      # XFR_MATCH_MAX_K, XFR_MATCH_MAX_D
+FINISH_MAX_MAPS, FINISH_MAX_DIM = 65535, 4096      # XFR_FINISH_MAX_MAPS, XFR_FINISH_MAX_DIM
 
 
 class XfrError(RuntimeError):
@@ -141,6 +142,7 @@ SYMBOLS = [
     ('xfr_embed_templates', _I, [_P, _P, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _I, _P, _P]),
     ('xfr_pair_dists', _I, [_P, _P, _I, _P, _I, _I, ctypes.POINTER(_I), _I, _P, _P]),
     ('xfr_nearest_rows', _I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    ('xfr_finish_saliency', _I, [_P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(_F), _P, ctypes.POINTER(_D), _P, _P, _P]),
     ('xfr_ebp_store_firing', _I, [_P, _P, _I, _I, _P, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _P]),
     ('xfr_engine_set_trace', _I, [_P, _I]),
     ('xfr_engine_trace_size', _I, [_P, ctypes.POINTER(_I)]),

@@ -543,3 +543,21 @@ void launch_pair_dists(const float* A, const float* B, int D, const int* pairs, 
 // idx, dist [nq][k]: the k nearest rows of G [ng][D] to every row of Q [nq][D] by that distance, ascending, equal distances by lower index;
 // exclude_same_index: query i skips gallery row i.  1 <= k <= MATCH_MAX_K, 1 <= D <= MATCH_MAX_D
 void launch_nearest_rows(const float* Q, long nq, const float* G, long ng, int D, int k, int exclude_same_index, int* idx, float* dist, hipStream_t s);
+
+// ---- saliency finishing (finish.hip; python/xfr/show.py:196-222, :131-137, :46-129) ----
+constexpr int FINISH_MAX_DIM = 4096;       // the longest axis of a map or of a probe
+constexpr int FINISH_MAX_MAPS = 65535;     // maps per call: a grid dimension
+constexpr int FINISH_PAD = 12;             // zeros on every side of a map before the spline prefilter
+constexpr int FINISH_STATS = 8;            // doubles of per-map statistics
+constexpr size_t finish_plane_doubles(int h, int w) { return (size_t)(h + 2 * FINISH_PAD) * (size_t)(w + 2 * FINISH_PAD); }
+// stats [n][FINISH_STATS] of float32 maps [n][n_px]: the minimum, the total of the shifted map (totals [n] when given, else the float32 nearest to the
+// float64 sum), and what the normalisation and the clip need.  One workgroup per map
+void launch_finish_head(const float* maps, int n, long n_px, const float* totals, double* stats, hipStream_t s);
+// planes [n][h + 24][w + 24]: the B-spline coefficients of the zero-padded normalised maps (axis 0, then axis 1)
+void launch_finish_prefilter(const float* maps, int n, int h, int w, const double* stats, double* planes, hipStream_t s);
+// sal [n][H][W], H >= h and W >= w: the 16-tap tensor product at every output pixel, clipped
+void launch_finish_resize(const double* planes, int n, int h, int w, int H, int W, const double* stats, double* sal, hipStream_t s);
+// sal [n][n_px] = the normalised maps themselves (the probe's size is the map's)
+void launch_finish_identity(const float* maps, int n, long n_px, const double* stats, double* sal, hipStream_t s);
+// out [n][n_px][3] uint8: the jet overlay of sal on probes [n][n_px][3]; lut [256][3] float64 on the device; writes the maps' ranges into stats
+void launch_finish_overlay(const double* sal, const uint8_t* probes, int n, long n_px, double* stats, const double* lut, uint8_t* out, hipStream_t s);

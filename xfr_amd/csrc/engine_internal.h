@@ -10,6 +10,7 @@
 //   strise_abi.hip     the C ABI: STRise blackbox saliency
 //   inpaint_abi.hip    the C ABI: inpainting-game scoring
 //   match_abi.hip      the C ABI: match calibration (templates, pair distances, nearest rows)
+//   finish_abi.hip     the C ABI: saliency finishing (normalise, spline resize, jet overlay)
 //   comm.hip           the C ABI: the RCCL binding
 //   plan_describe.hip  the C ABI: xfr_plan_describe
 #pragma once
@@ -268,6 +269,7 @@ struct xfr_engine {
     struct StriseState* strise = nullptr;   // xfr_strise_*: the family's own buffers, built on first use (strise_abi.hip)
     struct InpaintState* inpaint = nullptr; // xfr_inpaint_*: the same for inpainting-game scoring (inpaint_abi.hip)
     struct MatchState* match = nullptr;     // xfr_embed_templates / xfr_pair_dists: the device copy of the caller's index table (match_abi.hip)
+    struct FinishState* finish = nullptr;   // xfr_finish_saliency: the coefficient planes, the statistics, the colour table (finish_abi.hip)
 
     float* t_bank = nullptr;       // when set, true activations live in this bank (gallery forward of a triplet step)
     float* ws_enc = nullptr;       // second bank of true activations (T region only), allocated on first use
@@ -383,5 +385,8 @@ void inpaint_release(xfr_engine* e);
 
 // match_abi.hip
 void match_release(xfr_engine* e);
+
+// finish_abi.hip
+void finish_release(xfr_engine* e);
 
 }  // namespace xfr

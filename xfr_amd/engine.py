@@ -828,6 +828,46 @@ class Engine(object):
                    idx.data_ptr(), dist.data_ptr())
         return idx, dist
 
+    # -- saliency finishing (include/xfr_amd.h: xfr_finish_saliency) ---------------------------------------------
+    def _finish_call(self, *args):
+        """xfr_finish_saliency on this engine's device and the current stream; a refused call raises XfrError with the library's text."""
+        with torch.cuda.device(self.device):
+            status = self.lib.xfr_finish_saliency(self._h, *(args + (_stream_ptr(self.device),)))
+        if status != _lib.XFR_OK:
+            raise _lib.XfrError(status, self.lib.xfr_last_error().decode('utf-8', 'replace'))
+
+    def finish_saliency(self, maps, out_hw, probes_u8=None, totals=None):
+        """xfr_finish_saliency: create_save_smap's arithmetic for n maps at once.  maps float32 n x h x w (host or device), out_hw the probes' (H, W),
+        probes_u8 uint8 n x H x W x 3 or None, totals n float32 sums of the shifted maps or None (the device's own: the float32 nearest to the sum).
+        -> (sal float64 n x H x W, overlay uint8 n x H x W x 3 or None), device tensors."""
+        from .saliency_io import jet
+        maps = torch.as_tensor(maps)
+        if maps.dim() == 2:
+            maps = maps.unsqueeze(0)
+        if maps.dim() != 3 or maps.dtype != torch.float32:
+            raise ValueError('expected float32 maps n x h x w, got %s of %s' % (maps.dtype, tuple(maps.shape)))
+        maps = maps.detach().to(self.device).contiguous()
+        n, (H, W) = maps.shape[0], (int(out_hw[0]), int(out_hw[1]))
+        tp = None
+        if totals is not None:
+            totals = np.ascontiguousarray(np.asarray(totals, dtype=np.float32).ravel())
+            if totals.size != n:
+                raise ValueError('expected %d totals, got %d' % (n, totals.size))
+            tp = totals.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        sal = torch.empty((n, H, W), device=self.device, dtype=torch.float64)
+        probes = overlay = lut = lp = None
+        if probes_u8 is not None:
+            probes = torch.as_tensor(probes_u8)
+            if probes.dtype != torch.uint8 or tuple(probes.shape) != (n, H, W, 3):
+                raise ValueError('expected uint8 probes %s, got %s of %s' % ((n, H, W, 3), probes.dtype, tuple(probes.shape)))
+            probes = probes.detach().to(self.device).contiguous()
+            overlay = torch.empty((n, H, W, 3), device=self.device, dtype=torch.uint8)
+            lut = np.ascontiguousarray(jet(np.arange(256) / 256.0), dtype=np.float64)      # saliency_io's own table, row by row
+            lp = lut.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        self._finish_call(maps.data_ptr(), n, maps.shape[1], maps.shape[2], H, W, tp, probes.data_ptr() if probes is not None else None, lp,
+                          sal.data_ptr(), overlay.data_ptr() if overlay is not None else None)
+        return sal, overlay
+
     # ------------------------------------------------------------------------------------------------
     def set_trace(self, on):
         _lib.check(self.lib.xfr_engine_set_trace(self._h, 1 if on else 0))

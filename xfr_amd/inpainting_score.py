@@ -82,6 +82,11 @@ def _is_native(snet):
     return isinstance(snet, Whitebox)
 
 
+def _is_device_tensor(maps):
+    import torch
+    return isinstance(maps, torch.Tensor) and maps.is_cuda
+
+
 def _device_levels(threshold_method, percentiles, thresholds):
     """(method name, levels) when the device implements the request, else None.  'percent-pixels' stands for any other method name without
     thresholds (:57): its levels are the percentiles, which _pixel_thresholds turns into explicit thresholds per map."""
@@ -147,17 +152,27 @@ def _network_format(snet, *images):
 def score_maps(wb, orig_imT, inpaint_imT, gal_orig, gal_inp, maps, percentiles=None, thresholds=None, mask_threshold_method='percent-density',
                seed=None, max_noise=1e-9, include_zero_elements=True, mask_blur_sigma=None):
     """Additive: the game of several maps (n_maps x H x W) of one probe in one native call.
-    -> (classified_as_twin bool, pg_dist float64, pr_dist float64), each n_maps x n_levels."""
+    -> (classified_as_twin bool, pg_dist float64, pr_dist float64), each n_maps x n_levels.
+    `maps` may be a float64 device tensor (what Engine.finish_saliency returns): under 'percent-density' and explicit thresholds the engine reads it
+    where it lies, without a host copy; 'percent-pixels' takes its thresholds from numpy's percentile of the map, so the tensor is copied to the
+    host first, as a host array is used today."""
     levels = _device_levels(mask_threshold_method, percentiles, thresholds)
     if levels is None:
         raise ValueError('score_maps runs on the device: percent-density or percent-pixels with sorted percentiles in [0, 100], or non-increasing '
                          'explicit thresholds, at most 255 levels')
-    blur = _device_blur(mask_blur_sigma, np.shape(maps)[-2:], np.asarray(maps).dtype, percentiles, len(levels[1]))
+    on_device = _is_device_tensor(maps)
+    if on_device and str(maps.dtype) != 'torch.float64':
+        raise ValueError('score_maps takes a device tensor as float64 maps (Engine.finish_saliency returns them), got %s' % maps.dtype)
+    if on_device and levels[0] == 'percent-pixels':
+        maps, on_device = maps.cpu().numpy(), False
+    blur = _device_blur(mask_blur_sigma, tuple(maps.shape)[-2:] if on_device else np.shape(maps)[-2:], np.float64 if on_device else np.asarray(maps).dtype,
+                        percentiles, len(levels[1]))
     if blur is False:
         raise ValueError('score_maps blurs on the device: float64 maps, percentiles given, a radius int(4 sigma_px + 0.5) of 1 to 64')
-    maps = np.asarray(maps, dtype=np.float64)
-    if maps.ndim == 2:
-        maps = maps[np.newaxis]
+    if not on_device:
+        maps = np.asarray(maps, dtype=np.float64)
+    if len(maps.shape) == 2:
+        maps = maps[None]
     np.random.seed(seed)
     noise = np.random.rand(*maps.shape[1:])
     eng = wb._engine(wb.batch_size)

@@ -7,7 +7,8 @@ Mirrors, by name and argument meaning:
     shorten_subtree_mode, method_name
                             python/xfr/inpainting_game/generate_whitebox_saliency.py:216-219, 295-399 (file stems)
 
-Host-side glue around the device maps (numpy/scipy/PIL); nothing here is on the EBP hot path.
+Host-side glue around the device maps (numpy/scipy/PIL); nothing here is on the EBP hot path.  finish_maps / save_finished (additive) split
+create_save_smap into its arithmetic, run on the device for a batch of maps (xfr_finish_saliency), and its file writes.
 
 Resize note -- parity unpinned, restatement stated precisely: the reference calls `skimage.transform.resize(attMap,
 img.shape[:2], order=3, mode='constant')` (show.py:136) and skimage is not installed in this image, so there is nothing to
@@ -29,7 +30,7 @@ import numpy as np
 import scipy.ndimage as ndi
 
 __all__ = ['processSaliency', 'resize_linear', 'blend_saliency_map', 'create_save_smap', 'load_smap', 'shorten_subtree_mode', 'method_name',
-           'saliency_paths', 'jet']
+           'saliency_paths', 'jet', 'finish_maps', 'save_finished']
 
 
 # ---- resize ------------------------------------------------------------------------------------------------------
@@ -177,6 +178,40 @@ def create_save_smap(method, output_dir, overwrite, smap_fn, mask_id, probe_im, 
     if verbose:
         print('Created:\n %s\n' % overlay_filename)
     return True
+
+
+def finish_maps(engine, maps, probe_ims):
+    """Additive: the arithmetic half of create_save_smap for n maps at once, on the device (Engine.finish_saliency, xfr_finish_saliency): the float32
+    min-shift and division by the sum, processSaliency and blend_saliency_map with its defaults.  maps n x h x w (host or device), probe_ims n uint8
+    H x W x 3 probes of one size, no smaller than the maps.  -> (smaps float64 n x H x W, overlays uint8 n x H x W x 3), device tensors.
+    The division uses the float32 nearest to the exact sum where numpy's float32 sum() is a few ulp off."""
+    import torch
+    if not all(isinstance(p, torch.Tensor) for p in probe_ims):
+        probe_ims = [np.asarray(p) for p in probe_ims]
+    shapes = set(tuple(p.shape) for p in probe_ims)
+    if len(shapes) != 1 or len(next(iter(shapes))) != 3 or next(iter(shapes))[2] != 3 or any(str(p.dtype).split('.')[-1] != 'uint8' for p in probe_ims):
+        raise ValueError('finish_maps takes uint8 H x W x 3 probes of one size; float or mixed-size probes go through create_save_smap')
+    probes = torch.stack(list(probe_ims)) if isinstance(probe_ims[0], torch.Tensor) else torch.from_numpy(np.stack(probe_ims))
+    maps = maps if isinstance(maps, torch.Tensor) else torch.from_numpy(np.array(maps, dtype=np.float32))
+    if maps.dim() != 3 or maps.shape[0] != probes.shape[0]:
+        raise ValueError('finish_maps takes n maps and n probes, got %s and %s; use create_save_smap' % (tuple(maps.shape), tuple(probes.shape)))
+    if probes.shape[1] < maps.shape[1] or probes.shape[2] < maps.shape[2]:
+        raise ValueError('finish_maps does not shrink a map (%s to %s); use create_save_smap' % (tuple(maps.shape[1:]), tuple(probes.shape[1:3])))
+    return engine.finish_saliency(maps.float(), probes.shape[1:3], probes_u8=probes)
+
+
+def save_finished(output_dir, mask_id, method, smap, overlay):
+    """Additive: the file half of create_save_smap for one finished map (a row of finish_maps' results, host or device): the overlay PNG, then the
+    npz, atomically -- the same names, the same order, the same key."""
+    overlay_filename, npz_filename = saliency_paths(output_dir, mask_id, method)
+    to_host = lambda t: t.cpu().numpy() if hasattr(t, 'cpu') else np.asarray(t)      # noqa: E731
+    smap, overlay = to_host(smap), to_host(overlay)
+    os.makedirs(output_dir, exist_ok=True)
+    import PIL.Image
+    PIL.Image.fromarray(overlay).save(overlay_filename)
+    tmp = npz_filename + '.tmp.npz'
+    np.savez_compressed(tmp, saliency_map=smap)
+    os.replace(tmp, npz_filename)
 
 
 def load_smap(output_dir, mask_id, method):
