@@ -279,7 +279,7 @@ xfr_status xfr_engine_set_tail_balance(xfr_engine* e, int32_t enable);
  * prepare_lightCNN_image) before it is copied to the device as fp32.  Here the uint8 images go to the device as they are -- a quarter of the bytes --
  * and the layout kernel in front of the first convolution does that arithmetic, in float64 like numpy does, bit for bit the reference's tensor
  * (tests/test_gpu_entry.py on the four bundled JPEGs): kind SUB_MEAN: out[c] = (float)((double)u8[c] - mean[c]); kind LUMINANCE (3-channel image,
- * 1-channel network): (float)((r / 255) w[0] + (g / 255) w[1] + (b / 255) w[2]).  Resizing / cropping stays with the caller, as in the reference.
+ * 1-channel network): (float)((r / 255) w[0] + (g / 255) w[1] + (b / 255) w[2]).  Resizing / cropping is xfr_intake_u8 below, or the caller's.
  * x_u8_dev: n images, each in_h x in_w x channels, contiguous.  Everything else is xfr_forward / xfr_triplet_contrastive. */
 enum { XFR_U8_SUB_MEAN = 0, XFR_U8_LUMINANCE = 1 };
 typedef struct xfr_u8_preprocess {
@@ -704,6 +704,56 @@ xfr_status XFR_EX xfr_nearest_rows(xfr_engine* e, const float* q_dev, int32_t nq
 xfr_status XFR_EX xfr_finish_saliency(xfr_engine* e, const float* maps_dev, int32_t n, int32_t h, int32_t w, int32_t out_h, int32_t out_w,
                                       const float* totals_host, const uint8_t* probes_u8_dev, const double* jet_lut_host, double* sal_out_dev,
                                       uint8_t* overlay_out_dev, void* stream);
+
+/* ---- Image intake (python/xfr/models/whitebox.py:787-806 convert_from_numpy behind python/xfr/utils.py:39-202 image_loader).  Additive entry
+ * points, ABI version 7. -----------------------------------------------------------------------------------------------------------------------
+ * From decoded uint8 crops of unequal sizes to the network-size uint8 batch that xfr_forward_u8 and xfr_triplet_contrastive_u8[_host] take.  For
+ * a crop u of h x w x channels bytes (rows row_stride bytes apart, the first at `offset` of the source buffer) and an output of out_h x out_w:
+ *     head        XFR_INTAKE_HEAD_F64 (files, DataFrame rows): a = (double)u / 255.0;  XFR_INTAKE_HEAD_F32 (uint8 arrays handed to
+ *                 convert_from_numpy): a = (double)((float)u / 255.0f)
+ *     same size   h x w == out_h x out_w: no resize, the byte is uint8(a * 255.0), in float32 up to the truncation under the F32 head
+ *     pre-filter  only on an axis whose factor f = in / out exceeds 1, axis 0 then axis 1: scipy.ndimage.gaussian_filter(mode='mirror'),
+ *                 sigma = (f - 1) / 2 (no pass at sigma <= 1e-15), radius int(4 sigma + 0.5), weights exp(-0.5 / sigma^2 x^2) / their sum, summed
+ *                 from the outermost pair inwards around the centre term
+ *     zoom        scipy.ndimage.zoom(order=1, mode='mirror', grid_mode=True): cc = (o + 0.5) (in / out) - 0.5, c = |cc|, taps floor(c) and the
+ *                 next, mirrored at the far edge, weights 1 - (c - floor(c)) and its complement, the four products added row by row
+ *     clip, byte  clipped to [min a, max a] over all channels of the crop (alpha included), then uint8(v * 255.0), truncated
+ *     channels    one channel is replicated to three, a fourth is dropped (PIL's convert('RGB'))
+ *     tap tables  row_tab (final_h entries over out_h) and col_tab (final_w entries over out_w), both or neither, HOST memory: Pillow's integer
+ *                 bilinear resize and crop of those bytes, the horizontal pass first and rounded to uint8 (lightcnn.py:27-31 Resize + CenterCrop;
+ *                 the entries are those of xfr_strise_options).  final_h and final_w are ignored without tables
+ * out_dev is n x out_h x out_w x 3 bytes, or n x final_h x final_w x 3 with tables.  Float64 throughout, no operation contracted, one thread per
+ * output element: a crop's bytes depend on the crop alone, not on n, its place in the batch or the launch.  They equal the host chain's
+ * (saliency_io.resize_linear + truncation) byte for byte given the same Gaussian weights; the weights are libm's exp under numpy's summation, or the
+ * caller's own where xfr_intake_set_kernels states them (numpy's vectorised exp differs from libm's in the last bit of about one weight in twenty).
+ * The engine lends its device, its error text, its copy stream and the workspace (at most 512 MB of pre-filter planes per chunk of crops, more
+ * only for a single crop that needs it): no weights are needed and n is not bound by max_batch.  The work is enqueued on `stream`; items_host and
+ * the tables are read before the call returns.
+ * xfr_intake_u8_host: the same for a source in HOST memory, read before the call returns: copied to pinned memory, uploaded on the engine's copy
+ * stream, and `stream` waits for that upload alone.
+ * XFR_INVALID_ARG before anything is launched, with a text naming the value: a null engine, source, items or output; n outside
+ * [1, XFR_INTAKE_MAX_ITEMS]; channels outside {1, 3, 4}; an unknown head; an axis of a crop, of the output or of the final size outside
+ * [1, XFR_INTAKE_MAX_DIM]; a row stride shorter than a row; an item that leaves [0, src_bytes); a pre-filter radius above XFR_INTAKE_MAX_RADIUS
+ * (64: factors up to 33.1); an output size the zoom's own rounding, round(in * (1 / (in / out))), would not produce; one table without the other;
+ * table entries xfr_strise_score_ex would refuse; an output that overlaps the source. */
+#define XFR_INTAKE_MAX_ITEMS 65535
+#define XFR_INTAKE_MAX_DIM 4096
+#define XFR_INTAKE_MAX_RADIUS 64
+enum { XFR_INTAKE_HEAD_F64 = 0, XFR_INTAKE_HEAD_F32 = 1 };
+typedef struct {
+    int64_t offset;                     /* the crop's first byte in the source buffer */
+    int32_t h, w, row_stride, channels, head;
+} xfr_intake_item;
+xfr_status XFR_EX xfr_intake_u8(xfr_engine* e, const uint8_t* src_dev, size_t src_bytes, const xfr_intake_item* items_host, int32_t n, int32_t out_h,
+                                int32_t out_w, const xfr_strise_tap* row_tab, const xfr_strise_tap* col_tab, int32_t final_h, int32_t final_w,
+                                uint8_t* out_dev, void* stream);
+xfr_status XFR_EX xfr_intake_u8_host(xfr_engine* e, const uint8_t* src_host, size_t src_bytes, const xfr_intake_item* items_host, int32_t n,
+                                     int32_t out_h, int32_t out_w, const xfr_strise_tap* row_tab, const xfr_strise_tap* col_tab, int32_t final_h,
+                                     int32_t final_w, uint8_t* out_dev, void* stream);
+/* The caller's own Gaussian kernels for the pre-filter, replacing those stated before (count 0: none): kernel i serves every axis whose sigma and
+ * radius are exactly sigmas_host[i] and radii_host[i]; weights_host is count x (XFR_INTAKE_MAX_RADIUS + 1) doubles, row i holding the normalised
+ * weights of x = -radius .. 0.  A Python caller states numpy's kernels here so that the bytes equal scipy's on any host. */
+xfr_status XFR_EX xfr_intake_set_kernels(xfr_engine* e, const double* sigmas_host, const int32_t* radii_host, const double* weights_host, int32_t count);
 
 /* Debug / parity: after an xfr_ebp call made while tracing is enabled, the per-firing trace
  * sum(P[i]) (what the golden fixtures store for every entry of Whitebox.P, whitebox.py:394).

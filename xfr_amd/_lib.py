@@ -59,6 +59,7 @@ class InpaintOptions(ctypes.Structure):
 INPAINT_MAX_BLUR_RADIUS = 64      # XFR_INPAINT_MAX_BLUR_RADIUS
 MATCH_MAX_K, MATCH_MAX_D = 64, 4096      # XFR_MATCH_MAX_K, XFR_MATCH_MAX_D
 FINISH_MAX_MAPS, FINISH_MAX_DIM = 65535, 4096      # XFR_FINISH_MAX_MAPS, XFR_FINISH_MAX_DIM
+INTAKE_MAX_ITEMS, INTAKE_MAX_DIM, INTAKE_MAX_RADIUS = 65535, 4096, 64      # XFR_INTAKE_MAX_ITEMS, XFR_INTAKE_MAX_DIM, XFR_INTAKE_MAX_RADIUS
 
 
 class XfrError(RuntimeError):
@@ -143,6 +144,9 @@ SYMBOLS = [
     ('xfr_pair_dists', _I, [_P, _P, _I, _P, _I, _I, ctypes.POINTER(_I), _I, _P, _P]),
     ('xfr_nearest_rows', _I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     ('xfr_finish_saliency', _I, [_P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(_F), _P, ctypes.POINTER(_D), _P, _P, _P]),
+    ('xfr_intake_u8', _I, [_P, _P, ctypes.c_size_t, _P, _I, _I, _I, ctypes.POINTER(StriseTap), ctypes.POINTER(StriseTap), _I, _I, _P, _P]),
+    ('xfr_intake_u8_host', _I, [_P, _P, ctypes.c_size_t, _P, _I, _I, _I, ctypes.POINTER(StriseTap), ctypes.POINTER(StriseTap), _I, _I, _P, _P]),
+    ('xfr_intake_set_kernels', _I, [_P, ctypes.POINTER(_D), ctypes.POINTER(_I), ctypes.POINTER(_D), _I]),
     ('xfr_ebp_store_firing', _I, [_P, _P, _I, _I, _P, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _P]),
     ('xfr_engine_set_trace', _I, [_P, _I]),
     ('xfr_engine_trace_size', _I, [_P, ctypes.POINTER(_I)]),

@@ -41,11 +41,18 @@ def _is_native(net):
 
 
 # ---- the device path's two ends ---------------------------------------------------------------------------------------------------------
-def _network_images(wb, images):
-    """What Whitebox.embeddings makes of its argument (whitebox.py:747-766), one network-format tensor per image."""
+def _network_images(wb, images, intake='host'):
+    """What Whitebox.embeddings makes of its argument (whitebox.py:747-766), one network-format tensor per image -- or, where the device intake
+    takes the images (intake 'auto' or 'device'; Whitebox.intake), one uint8 H x W x 3 device tensor per image, the bytes that tensor is made of
+    (_device_encodings takes either)."""
     import torch
     from .image_loader import image_loader
     from .models.whitebox import _is_dataframe
+    loaded = _is_dataframe(images) or (not isinstance(images, torch.Tensor) and len(images) > 0 and isinstance(images[0], str))
+    if loaded:
+        u8 = wb._intake_or_none(images, intake)
+        if u8 is not None:
+            return list(u8)
     if _is_dataframe(images):
         return [wb.convert_from_numpy(im)[0] for im in image_loader(images)]
     if isinstance(images, torch.Tensor):
@@ -65,11 +72,19 @@ def _device_encodings(wb, images):
     eng, mark = wb._engine(wb.batch_size), wb.net._mark('encode')
     out, chunk = [], []
 
+    def is_u8(im):
+        return isinstance(im, torch.Tensor) and im.dtype == torch.uint8
+
     def flush():
-        x = torch.stack([torch.as_tensor(im, dtype=torch.float32) for im in chunk])
-        out.append(eng.forward(x, mark).reshape(len(chunk), -1))
+        if is_u8(chunk[0]):                  # the device intake's bytes: the engine's own pixel arithmetic in front of the same forward
+            out.append(eng.forward_u8(torch.stack(chunk), mark).reshape(len(chunk), -1))
+        else:
+            x = torch.stack([torch.as_tensor(im, dtype=torch.float32) for im in chunk])
+            out.append(eng.forward(x, mark).reshape(len(chunk), -1))
         del chunk[:]
     for im in images:
+        if chunk and is_u8(im) != is_u8(chunk[0]):      # a list that mixes the two kinds: no chunk does
+            flush()
         chunk.append(im)
         if len(chunk) == wb.batch_size:
             flush()
@@ -129,7 +144,7 @@ def mate_nonmate_dists(net, batches):
     return d[starts], d[keep]
 
 
-def calc_mate_nonmate_dists(net, num_subjects, seed, output_dir, ijbc_path):
+def calc_mate_nonmate_dists(net, num_subjects, seed, output_dir, ijbc_path, intake='auto'):
     """Drop-in for net_mate_nonmate_dists.py:55-144: distances of mated pairs and of non-mated pairs over IJB-C, the same metadata filter and the
     same draws in the same order.  -> (mate_dists float32 [S], nonmate_dists float32 [S * 2 * 64])."""
     import pandas as pd
@@ -168,7 +183,7 @@ def calc_mate_nonmate_dists(net, num_subjects, seed, output_dir, ijbc_path):
 
     def batches():
         for chosen in chosen_frames:
-            images = _network_images(net, chosen)
+            images = _network_images(net, chosen, intake)
             yield images[:2], images[2:]
     return mate_nonmate_dists(net, batches())
 
@@ -248,7 +263,7 @@ def _decide(pr_dist, pg_dist, tpr_dist, tpg_dist, thr):
     return mate_correct, mate_diff, twin_correct, twin_diff
 
 
-def _separability(snet, probe_images, mate_images, masks):
+def _separability(snet, probe_images, mate_images, masks, intake='auto'):
     """:105-181 with average_nonmates for one subject; masks: a list of (twin probe images, non-mate images).  -> one 4-tuple per mask."""
     thr = snet.match_threshold
     if not _is_native(snet):
@@ -276,11 +291,11 @@ def _separability(snet, probe_images, mate_images, masks):
         return out
     # one embedding pass: probes, mates, then per mask its twins and its non-mates; templates: every probe and twin alone, the mates and each
     # mask's non-mates as one group each
-    probes, mates = _network_images(snet, probe_images), _network_images(snet, mate_images)
+    probes, mates = _network_images(snet, probe_images, intake), _network_images(snet, mate_images, intake)
     P = len(probes)
     images, offsets = probes + mates, list(range(P + 1)) + [P + len(mates)]
     for twin_probe_images, nonmate_images in masks:
-        twins, nonmates = _network_images(snet, twin_probe_images), _network_images(snet, nonmate_images)
+        twins, nonmates = _network_images(snet, twin_probe_images, intake), _network_images(snet, nonmate_images, intake)
         if len(twins) != P:
             raise ValueError('%d twin probes of %d probes' % (len(twins), P))
         base = offsets[-1]
@@ -298,14 +313,14 @@ def _separability(snet, probe_images, mate_images, masks):
     return [_decide(d[0], d[1 + 3 * k], d[3 + 3 * k], d[2 + 3 * k], thr) for k in range(len(masks))]
 
 
-def triplet_separability(snet, probe_images, mate_images, twin_probe_images, nonmate_images):
+def triplet_separability(snet, probe_images, mate_images, twin_probe_images, nonmate_images, intake='auto'):
     """filter_inpaintinggame_for_net.py:105-181 with average_nonmates=True for one subject and one mask: is every probe nearer to the mean of its
     mates than to the mean of the inpainted non-mates and under snet.match_threshold, and every inpainted twin the other way round.
     -> (mate_correct bool, mate_diff float32, twin_correct bool, twin_diff float32), each P x 1; the differences are positive where separable."""
-    return _separability(snet, probe_images, mate_images, [(twin_probe_images, nonmate_images)])[0]
+    return _separability(snet, probe_images, mate_images, [(twin_probe_images, nonmate_images)], intake)[0]
 
 
-def separability_table(snet, inpaintgame_dir, mask_ids=MASK_IDS, net_name='net', return_subject_data=False):
+def separability_table(snet, inpaintgame_dir, mask_ids=MASK_IDS, net_name='net', return_subject_data=False, intake='auto'):
     """The reference's `separability` DataFrame (:87-250) of one network over every subj-*.csv of the game's directory, one row per (probe, mask):
     the 13 columns of :236-250, cells as the reference leaves them (CorrectlyCls / OrigTripletSim ... hold arrays of one element).
     return_subject_data: also the concatenated subject tables (`all_subj_data`, :234) that include_masks_by_thresholds takes."""
@@ -325,7 +340,7 @@ def separability_table(snet, inpaintgame_dir, mask_ids=MASK_IDS, net_name='net',
             twin_probe_fns = [inpainting_pattern.format(**dict(d, MASK_ID=mask_id)) for d in rows if d['TRIPLET_SET'] == 'PROBE']
             nonmate_fns = [inpainting_pattern.format(**dict(d, MASK_ID=mask_id)) for d in rows if d['TRIPLET_SET'] != 'PROBE']
             masks.append((twin_probe_fns, nonmate_fns))
-        results = _separability(snet, probe_fns, mate_fns, masks)
+        results = _separability(snet, probe_fns, mate_fns, masks, intake)
         for mask_id, (mate_correct, mate_diff, twin_correct, twin_diff) in zip(mask_ids, results):
             for i, d in enumerate(d for d in rows if d['TRIPLET_SET'] == 'PROBE'):
                 d = dict(d, MASK_ID=mask_id)

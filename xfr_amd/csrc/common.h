@@ -496,6 +496,13 @@ void launch_strise_quant_u8(const uint8_t* probe, const double* fill, const int*
 // one output row or column of PIL's 8-bit bilinear resize: pixels [first, first + count) weighted by coef in 2^-22 (xfr_strise_tap)
 constexpr int STRISE_MAX_TAPS = 8;
 struct StriseTap { int first, count; int coef[STRISE_MAX_TAPS]; };
+// one pass of PIL's 8-bit resampling (Resample.c, ImagingResampleHorizontal_8bpc): clip8((2^21 + sum pixel * coef) >> 22), pixels `stride` apart
+__device__ inline int resample_u8(const uint8_t* __restrict__ px, int stride, const StriseTap& t)
+{
+    int acc = 1 << 21;
+    for (int i = 0; i < t.count; ++i) acc += (int)px[i * stride] * t.coef[i];
+    return min(max(acc >> 22, 0), 255);
+}
 constexpr int STRISE_LUM_BAND = 16;      // output rows per workgroup of the luminance kernel
 constexpr size_t strise_lum_lds_bytes(int rows_max, int W, int in_w) { return (size_t)rows_max * (size_t)(W + in_w) * 3; }
 // out [n][1][in_h][in_w] = rgb2gray of the resized and cropped q; row_tab [in_h], col_tab [in_w] on the device; rows_max: the most probe rows one
@@ -561,3 +568,28 @@ void launch_finish_resize(const double* planes, int n, int h, int w, int H, int 
 void launch_finish_identity(const float* maps, int n, long n_px, const double* stats, double* sal, hipStream_t s);
 // out [n][n_px][3] uint8: the jet overlay of sal on probes [n][n_px][3]; lut [256][3] float64 on the device; writes the maps' ranges into stats
 void launch_finish_overlay(const double* sal, const uint8_t* probes, int n, long n_px, double* stats, const double* lut, uint8_t* out, hipStream_t s);
+
+// ---- image intake (intake.hip; python/xfr/models/whitebox.py:787-806 convert_from_numpy, python/xfr/utils.py:39-202) ----
+constexpr int INTAKE_MAX_DIM = 4096;       // the longest axis of a crop or of an output
+constexpr int INTAKE_MAX_ITEMS = 65535;    // crops per call: a grid dimension
+constexpr int INTAKE_MAX_RADIUS = 64;      // the Gaussian pre-filter's radius int(4 sigma + 0.5), sigma = (factor - 1) / 2: factors up to 33.1
+constexpr int INTAKE_WEIGHTS = INTAKE_MAX_RADIUS + 1;      // doubles of one kernel: w[0 .. r], w[r] the centre
+enum { INTAKE_HEAD_F64 = 0, INTAKE_HEAD_F32 = 1 };
+enum { INTAKE_FROM_U8 = 0, INTAKE_FROM_A = 1, INTAKE_FROM_B = 2 };
+// one crop of a chunk as the kernels see it.  src: the crop's first byte in the source buffer; ws: its first double in either workspace plane
+// (h x w x C doubles each); ry, rx: the radii of the two pre-filter passes, 0 = that axis is skipped; zoom_from: what the zoom reads;
+// identity: the output's size is the crop's, no resize; sy, sx = h / H, w / W
+struct IntakeItem { long src, ws; int h, w, stride, C, head, ry, rx, zoom_from, identity, pad; double sy, sx; };
+// lohi [n][2] = the head of the least and of the largest byte of every crop, all channels
+void launch_intake_range(const uint8_t* src, const IntakeItem* items, int n, double* lohi, hipStream_t s);
+// the pre-filter passes of a chunk: axis 0 from the bytes into plane A (ry > 0), axis 1 from the bytes into A (ry == 0 < rx), axis 1 from A into B
+// (both); wts [n][2][INTAKE_WEIGHTS]; max_elems: the largest h * w * C of the chunk; which: bit p set = some crop takes pass p
+void launch_intake_prefilter(const uint8_t* src, const IntakeItem* items, int n, const double* wts, double* plane_a, double* plane_b, long max_elems, int which,
+                             hipStream_t s);
+// out [n][H][W][3] uint8: zoom, clip, truncate; one channel replicated, a fourth dropped
+void launch_intake_zoom(const uint8_t* src, const IntakeItem* items, int n, const double* lohi, const double* plane_a, const double* plane_b, int H, int W,
+                        uint8_t* out, hipStream_t s);
+// out [n][fh][fw][3] = PIL's 8-bit bilinear resize + crop of q [n][H][W][3] by tap tables on the device (row_tab [fh], col_tab [fw]): the horizontal
+// pass into mid [n][H][fw][3], rounded to uint8, then the vertical one
+void launch_intake_taps(const uint8_t* q, int n, int H, int W, const StriseTap* row_tab, const StriseTap* col_tab, int fh, int fw, uint8_t* mid, uint8_t* out,
+                        hipStream_t s);

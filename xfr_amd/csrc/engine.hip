@@ -236,6 +236,7 @@ xfr_status xfr_engine_destroy(xfr_engine* e)
     inpaint_release(e);
     match_release(e);
     finish_release(e);
+    intake_release(e);
     sweep_release(e);
     for (int i = 0; i < 3; ++i) { if (e->seedbuf[i]) (void)hipFree(e->seedbuf[i]); if (e->ev_slot_done[i]) (void)hipEventDestroy(e->ev_slot_done[i]); }
     for (int i = 0; i < 3; ++i) {

@@ -11,6 +11,7 @@
 //   inpaint_abi.hip    the C ABI: inpainting-game scoring
 //   match_abi.hip      the C ABI: match calibration (templates, pair distances, nearest rows)
 //   finish_abi.hip     the C ABI: saliency finishing (normalise, spline resize, jet overlay)
+//   intake_abi.hip     the C ABI: image intake (crop, Gaussian pre-filter, linear resize, bytes)
 //   comm.hip           the C ABI: the RCCL binding
 //   plan_describe.hip  the C ABI: xfr_plan_describe
 #pragma once
@@ -269,6 +270,7 @@ struct xfr_engine {
     struct StriseState* strise = nullptr;   // xfr_strise_*: the family's own buffers, built on first use (strise_abi.hip)
     struct InpaintState* inpaint = nullptr; // xfr_inpaint_*: the same for inpainting-game scoring (inpaint_abi.hip)
     struct MatchState* match = nullptr;     // xfr_embed_templates / xfr_pair_dists: the device copy of the caller's index table (match_abi.hip)
+    struct IntakeState* intake = nullptr;   // xfr_intake_u8[_host]: the items, weights, planes and staging buffers of the running call (intake_abi.hip)
     struct FinishState* finish = nullptr;   // xfr_finish_saliency: the coefficient planes, the statistics, the colour table (finish_abi.hip)
 
     float* t_bank = nullptr;       // when set, true activations live in this bank (gallery forward of a triplet step)
@@ -379,6 +381,7 @@ xfr_status grow(T** p, size_t* cap, size_t need)
 
 // strise_abi.hip
 void strise_release(xfr_engine* e);
+xfr_status check_taps(const xfr_strise_tap* tab, int entries, int n, const char* what, const char* who);
 
 // inpaint_abi.hip
 void inpaint_release(xfr_engine* e);
@@ -388,5 +391,8 @@ void match_release(xfr_engine* e);
 
 // finish_abi.hip
 void finish_release(xfr_engine* e);
+
+// intake_abi.hip
+void intake_release(xfr_engine* e);
 
 }  // namespace xfr

@@ -352,14 +352,6 @@ __global__ __launch_bounds__(1024) void strise_normalize_kernel(double* __restri
     for (int i = threadIdx.x; i < n; i += 1024) sal[i] = (sal[i] - mn) / top;
 }
 
-// one pass of PIL's 8-bit resampling (Resample.c, ImagingResampleHorizontal_8bpc): clip8((2^21 + sum pixel * coef) >> 22), pixels `stride` apart
-__device__ inline int resample_u8(const uint8_t* __restrict__ px, int stride, const StriseTap& t)
-{
-    int acc = 1 << 21;
-    for (int i = 0; i < t.count; ++i) acc += (int)px[i * stride] * t.coef[i];
-    return min(max(acc >> 22, 0), 255);
-}
-
 // K_strise_quant_lum: the quantised chain for XFR_U8_LUMINANCE networks (Light-CNN, lightcnn.py:19-31): q at probe resolution, PIL's bilinear
 // Resize + CenterCrop as two integer passes from the caller's cropped tap tables (columns first, rounded to uint8, then rows), then rgb2gray as
 // u8hwc_to_cnhw_kernel states it, into the 1 x in_h x in_w input.  One workgroup per (image, band of STRISE_LUM_BAND output rows): q of the

@@ -24,6 +24,27 @@ void strise_release(xfr_engine* e)
     e->strise = nullptr;
 }
 
+
+// one tap table of Pillow's 8-bit resampling against the axis of n pixels it reads; `who` names the calling family in the text
+xfr_status check_taps(const xfr_strise_tap* tab, int entries, int n, const char* what, const char* who)
+{
+    for (int i = 0; i < entries; ++i) {
+        const xfr_strise_tap& t = tab[i];
+        if (t.count < 1 || t.count > XFR_STRISE_MAX_TAPS)
+            return fail(XFR_INVALID_ARG, "%s: %s table entry %d has count %d, outside [1, %d]", who, what, i, t.count, XFR_STRISE_MAX_TAPS);
+        if (t.first < 0 || (long)t.first + t.count > n)
+            return fail(XFR_INVALID_ARG, "%s: %s table entry %d reads [%d, %d + %d), a window outside the probe's %d", who, what, i, t.first, t.first, t.count, n);
+        long sum = 0;
+        for (int j = 0; j < t.count; ++j) {
+            if (t.coef[j] < 0) return fail(XFR_INVALID_ARG, "%s: %s table entry %d has the negative coefficient %d", who, what, i, t.coef[j]);
+            sum += t.coef[j];
+        }
+        if (sum * 255 + (1L << 21) > 2147483647L)
+            return fail(XFR_INVALID_ARG, "%s: %s table entry %d: 255 x the coefficient sum %ld overflows int32", who, what, i, sum);
+    }
+    return XFR_OK;
+}
+
 }  // namespace xfr
 
 namespace {
@@ -86,26 +107,6 @@ xfr_status check_masks(xfr_engine* e, const int32_t* cells, const int32_t* shift
     return XFR_OK;
 }
 
-// one tap table of a luminance engine against the probe's axis of n pixels
-xfr_status check_taps(const xfr_strise_tap* tab, int entries, int n, const char* what)
-{
-    for (int i = 0; i < entries; ++i) {
-        const xfr_strise_tap& t = tab[i];
-        if (t.count < 1 || t.count > XFR_STRISE_MAX_TAPS)
-            return fail(XFR_INVALID_ARG, "strise: %s table entry %d has count %d, outside [1, %d]", what, i, t.count, XFR_STRISE_MAX_TAPS);
-        if (t.first < 0 || (long)t.first + t.count > n)
-            return fail(XFR_INVALID_ARG, "strise: %s table entry %d reads [%d, %d + %d), a window outside the probe's %d", what, i, t.first, t.first, t.count, n);
-        long sum = 0;
-        for (int j = 0; j < t.count; ++j) {
-            if (t.coef[j] < 0) return fail(XFR_INVALID_ARG, "strise: %s table entry %d has the negative coefficient %d", what, i, t.coef[j]);
-            sum += t.coef[j];
-        }
-        if (sum * 255 + (1L << 21) > 2147483647L)
-            return fail(XFR_INVALID_ARG, "strise: %s table entry %d: 255 x the coefficient sum %ld overflows int32", what, i, sum);
-    }
-    return XFR_OK;
-}
-
 // what the network input needs of the engine.  quantize 0: only the arithmetic of convert_resnet101v4_image is built into the masked-probe kernel;
 // quantize 1: the engine's own uint8 preprocessing, sub-mean at the probe's size or luminance behind the caller's resampling tables
 xfr_status check_u8(xfr_engine* e, StriseOpt* o)
@@ -117,9 +118,9 @@ xfr_status check_u8(xfr_engine* e, StriseOpt* o)
             return fail(XFR_INVALID_ARG, "strise: XFR_U8_LUMINANCE of %d-channel images into a %d-channel network; 3 and 1 are built", e->u8_pre.channels, e->in_c);
         if (!o->row_tab || !o->col_tab)
             return fail(XFR_INVALID_ARG, "strise: an XFR_U8_LUMINANCE engine needs the resampling tables row_tab and col_tab");
-        xfr_status rc = check_taps(o->row_tab, e->in_h, o->H, "row");
+        xfr_status rc = check_taps(o->row_tab, e->in_h, o->H, "row", "strise");
         if (rc != XFR_OK) return rc;
-        rc = check_taps(o->col_tab, e->in_w, o->W, "column");
+        rc = check_taps(o->col_tab, e->in_w, o->W, "column", "strise");
         if (rc != XFR_OK) return rc;
         for (int oy0 = 0; oy0 < e->in_h; oy0 += STRISE_LUM_BAND) {      // the kernel's own walk over a band
             int lo = o->H, hi = 0;

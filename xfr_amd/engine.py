@@ -11,6 +11,20 @@ from .program import LAYER_NAMES, OpKind
 MODES = {'affineonly': 0, 'affineonly_with_prior': 1, 'norelu': 2, 'all': 3}
 
 
+def _tap_array(tab):
+    """One table of xfr_amd.models.blackbox.pil_bilinear_tables (first, count, coef) as an array of xfr_strise_tap."""
+    n = len(tab['first'])
+    coef = np.asarray(tab['coef'], dtype=np.int32).reshape(n, -1)
+    if coef.shape[1] > _lib.STRISE_MAX_TAPS and (coef[:, _lib.STRISE_MAX_TAPS:] != 0).any():
+        raise ValueError('a resampling table with more than %d taps' % _lib.STRISE_MAX_TAPS)
+    arr = (_lib.StriseTap * n)()
+    for i in range(n):
+        arr[i].first, arr[i].count = int(tab['first'][i]), int(tab['count'][i])
+        for j, v in enumerate(coef[i, :_lib.STRISE_MAX_TAPS]):
+            arr[i].coef[j] = int(v)
+    return arr
+
+
 def _stream_ptr(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -534,15 +548,7 @@ class Engine(object):
         keep = [opt]
         if tables is not None:
             for name, tab in zip(('row_tab', 'col_tab'), tables):
-                n = len(tab['first'])
-                coef = np.asarray(tab['coef'], dtype=np.int32).reshape(n, -1)
-                if coef.shape[1] > _lib.STRISE_MAX_TAPS and (coef[:, _lib.STRISE_MAX_TAPS:] != 0).any():
-                    raise ValueError('a resampling table with more than %d taps' % _lib.STRISE_MAX_TAPS)
-                arr = (_lib.StriseTap * n)()
-                for i in range(n):
-                    arr[i].first, arr[i].count = int(tab['first'][i]), int(tab['count'][i])
-                    for j, v in enumerate(coef[i, :_lib.STRISE_MAX_TAPS]):
-                        arr[i].coef[j] = int(v)
+                arr = _tap_array(tab)
                 setattr(opt, name, arr)
                 keep.append(arr)
         return ctypes.byref(opt), (h, w), keep
@@ -867,6 +873,48 @@ class Engine(object):
         self._finish_call(maps.data_ptr(), n, maps.shape[1], maps.shape[2], H, W, tp, probes.data_ptr() if probes is not None else None, lp,
                           sal.data_ptr(), overlay.data_ptr() if overlay is not None else None)
         return sal, overlay
+
+    # -- image intake (include/xfr_amd.h: xfr_intake_u8, xfr_intake_u8_host, xfr_intake_set_kernels) ---------------
+    def intake_set_kernels(self, sigmas, radii, weights):
+        """xfr_intake_set_kernels: the caller's Gaussian kernels for the pre-filter (xfr_amd.intake.stated_kernels: numpy's), replacing those stated
+        before.  weights: n x (INTAKE_MAX_RADIUS + 1), row i the normalised weights of x = -radii[i] .. 0."""
+        sigmas = np.ascontiguousarray(sigmas, dtype=np.float64).ravel()
+        radii = np.ascontiguousarray(radii, dtype=np.int32).ravel()
+        weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1, _lib.INTAKE_MAX_RADIUS + 1)
+        if not (sigmas.size == radii.size == weights.shape[0]):
+            raise ValueError('expected as many sigmas, radii and rows of weights, got %d, %d and %d' % (sigmas.size, radii.size, weights.shape[0]))
+        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
+        _lib.check(self.lib.xfr_intake_set_kernels(self._h, sigmas.ctypes.data_as(dp), radii.ctypes.data_as(ip), weights.ctypes.data_as(dp), sigmas.size))
+
+    def intake_u8(self, src, items, out_hw, tables=None):
+        """xfr_intake_u8 (src a uint8 device tensor) or xfr_intake_u8_host (src a uint8 numpy array or host tensor): the crops `items` (an array of
+        xfr_amd.intake.Item inside src) resized to out_hw as convert_from_numpy does it, then, with tables = (row, column) of pil_bilinear_tables,
+        through Pillow's integer resize and crop.  -> uint8 device tensor n x H x W x 3 (n x len(row) x len(column) x 3 with tables).  A refused
+        call raises XfrError with the library's text."""
+        n = len(items)
+        H, W = int(out_hw[0]), int(out_hw[1])
+        row = col = None
+        fh, fw = H, W
+        if tables is not None:
+            row, col = _tap_array(tables[0]), _tap_array(tables[1])
+            fh, fw = len(row), len(col)
+        on_device = isinstance(src, torch.Tensor) and src.is_cuda
+        if on_device:
+            if src.dtype != torch.uint8:
+                raise ValueError('expected a uint8 source, got %s' % src.dtype)
+            src = src.detach().to(self.device).contiguous()
+            ptr, nbytes, fn = src.data_ptr(), src.numel(), self.lib.xfr_intake_u8
+        else:
+            src = np.ascontiguousarray(src.numpy() if isinstance(src, torch.Tensor) else src)
+            if src.dtype != np.uint8:
+                raise ValueError('expected a uint8 source, got %s' % src.dtype)
+            ptr, nbytes, fn = src.ctypes.data, src.size, self.lib.xfr_intake_u8_host
+        out = torch.empty((max(n, 0), fh, fw, 3), device=self.device, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            status = fn(self._h, ptr, nbytes, ctypes.cast(items, ctypes.c_void_p), n, H, W, row, col, fh, fw, out.data_ptr(), _stream_ptr(self.device))
+        if status != _lib.XFR_OK:
+            raise _lib.XfrError(status, self.lib.xfr_last_error().decode('utf-8', 'replace'))
+        return out
 
     # ------------------------------------------------------------------------------------------------
     def set_trace(self, on):

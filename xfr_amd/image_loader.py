@@ -90,6 +90,40 @@ def crop_example_no_name(ex, data_root=''):
     return img, ex['SubjectID'], ex['Filename'], ex['SubjectID']
 
 
+def intake_items(images):
+    """Additive: what image_loader + Whitebox.convert_from_numpy read of every image, as the device intake takes it (xfr_amd.intake): the uint8
+    crop (a view of the decoded pixels, h x w or h x w x C) and the head that states the / 255 its caller applies -- HEAD_F64 for DataFrame rows
+    (decoded, float64 / 255, cropped to the row's box) and file names (decoded, float64 / 255, the centred square), HEAD_F32 for uint8
+    H x W x 3 arrays (convert_from_numpy's float32 / 255).  Float arrays yield None: their chain stays on the host."""
+    from .intake import HEAD_F32, HEAD_F64
+    try:
+        import pandas as pd
+        is_frame = isinstance(images, pd.DataFrame)
+    except ImportError:
+        is_frame = False
+    if is_frame:
+        for _, ex in images.iterrows():
+            img = imread(ex['Filename'])
+            try:
+                top, bottom, left, right = crop_box(img.shape, ex['XMin'], ex['YMin'], ex['Width'], ex['Height'])
+                img = img[top:bottom, left:right]
+            except KeyError:
+                pass
+            yield img, HEAD_F64
+        return
+    for img in images:
+        if isinstance(img, np.ndarray):
+            assert img.ndim == 3 and img.shape[2] == 3
+            yield (img, HEAD_F32) if img.dtype == np.uint8 else None
+        elif isinstance(img, str):
+            img = imread(img)
+            side = min(img.shape[:2])
+            y0, x0 = (img.shape[0] - side) // 2, (img.shape[1] - side) // 2
+            yield img[y0:y0 + side, x0:x0 + side], HEAD_F64
+        else:
+            raise NotImplementedError('Unhandled type %s' % type(img))
+
+
 def image_loader(images, returnImageIndex=False, returnFileName=False, repeats=1):
     """utils.py:39-109: iterate displayable images (float H x W x 3) over a DataFrame (columns Filename, SubjectID [, XMin, YMin, Width,
     Height]), a sequence of file names (decoded, / 255, centre-cropped to 224 x 224) or of H x W x 3 arrays (passed through, fn None).

@@ -12,6 +12,7 @@ xfr_amd.models.whitebox.Whitebox.  The drop-in functions encode the k mate and k
 the reference (ENCODE_ONE_BY_ONE below), so they reproduce its arithmetic; run_jobs_batched is the fast, additive path that
 batches the encodes.  `net_name` is accepted for signature compatibility and unused, as in the reference.
 """
+import numpy as np
 import torch
 
 # ebp_version -> (do_max_subtree, do_mated_similarity_gating) of weighted_subtree_ebp: generate_whitebox_saliency.py:171-194;
@@ -27,13 +28,30 @@ SUBTREE_VERSIONS = {7: (True, True), 8: (False, True), 9: (True, False), 10: (Tr
 ENCODE_ONE_BY_ONE = True
 
 
-def mean_encoding(wb, images, device):
-    """Unit-normalised mean of the encodings of `images` (:87-98): 1 x D tensor on `device`."""
-    x = torch.cat([wb.convert_from_numpy(im) for im in images], dim=0).to(device)
-    if ENCODE_ONE_BY_ONE:
-        enc = torch.cat([wb.encode(x[i:i + 1]).detach() for i in range(x.shape[0])], dim=0)
+def encode_images(wb, images, device, step, intake='auto'):
+    """Additive: the raw encodings of H x W x 3 images, `step` images per forward (None: all at once), on `device`.  intake 'host': every image
+    through wb.convert_from_numpy, as the reference does it; 'device': cropped, resized and truncated on the device (Whitebox.intake) and encoded
+    from the bytes (encode_u8); 'auto': the device for uint8 arrays on a network that states its uint8 preprocessing, else the host.  The same
+    bytes reach the network either way."""
+    from .intake import IntakeRefused
+    images = list(images)
+    u8 = None
+    takes = hasattr(wb, '_intake_or_none') and all(isinstance(im, np.ndarray) and im.dtype == np.uint8 for im in images)
+    if intake != 'host' and not takes:
+        if intake == 'device':
+            raise IntakeRefused('the device intake takes uint8 arrays on an xfr_amd Whitebox')
     else:
-        enc = wb.encode(x).detach()
+        u8 = wb._intake_or_none(images, intake) if takes else None
+    if u8 is None:
+        u8 = torch.cat([wb.convert_from_numpy(im) for im in images], dim=0).to(device)
+    encode = wb.net.encode_u8 if u8.dtype == torch.uint8 else wb.encode
+    step = step or u8.shape[0]
+    return torch.cat([encode(u8[i:i + step]).detach() for i in range(0, u8.shape[0], step)], dim=0).to(device)
+
+
+def mean_encoding(wb, images, device, intake='auto'):
+    """Unit-normalised mean of the encodings of `images` (:87-98): 1 x D tensor on `device`."""
+    enc = encode_images(wb, images, device, 1 if ENCODE_ONE_BY_ONE else None, intake)
     avg = torch.mean(enc.reshape(enc.shape[0], 1, -1), axis=0)
     return avg / torch.norm(avg)
 
@@ -45,10 +63,10 @@ def mean_ebp(wb, probe_im, net_name, ebp_version, device):
     return wb.ebp(x_probe, P)
 
 
-def run_contrastive_triplet_ebp(wb, im_mates, im_nonmates, probe_im, net_name, ebp_version, truncate_percent, device):
+def run_contrastive_triplet_ebp(wb, im_mates, im_nonmates, probe_im, net_name, ebp_version, truncate_percent, device, intake='auto'):
     """Contrastive (truncate_percent None) or truncated contrastive EBP of the probe against the averaged mates / non-mates."""
-    avg_x_mate = mean_encoding(wb, im_mates, device)
-    avg_x_nonmate = mean_encoding(wb, im_nonmates, device)
+    avg_x_mate = mean_encoding(wb, im_mates, device, intake)
+    avg_x_nonmate = mean_encoding(wb, im_nonmates, device, intake)
     img_probe = wb.convert_from_numpy(probe_im).to(device)
     wb.net.set_triplet_classifier((1.0 / 2500.0) * avg_x_mate, (1.0 / 2500.0) * avg_x_nonmate)
     if truncate_percent is None:
@@ -57,11 +75,11 @@ def run_contrastive_triplet_ebp(wb, im_mates, im_nonmates, probe_im, net_name, e
 
 
 def run_weighted_subtree_triplet_ebp(wb, im_mates, im_nonmates, probe_im, net_name, subtree_mode_weighted, ebp_version, device,
-                                     topk=1):
+                                     topk=1, intake='auto'):
     """Weighted subtree EBP with the parameterisation `ebp_version` selects; the classifier rows are the unit-norm averages
     themselves here (no 1/2500 factor, :134)."""
-    avg_x_mate = mean_encoding(wb, im_mates, device)
-    avg_x_nonmate = mean_encoding(wb, im_nonmates, device)
+    avg_x_mate = mean_encoding(wb, im_mates, device, intake)
+    avg_x_nonmate = mean_encoding(wb, im_nonmates, device, intake)
     img_probe = wb.convert_from_numpy(probe_im).to(device)
     wb.net.set_triplet_classifier(avg_x_mate, avg_x_nonmate)
     do_max_subtree, do_mated_similarity_gating = SUBTREE_VERSIONS.get(ebp_version, (False, False))
@@ -71,7 +89,8 @@ def run_weighted_subtree_triplet_ebp(wb, im_mates, im_nonmates, probe_im, net_na
     return img_subtree
 
 
-def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, device, topk=32, methods=None, timings=None, native_subtree=False):
+def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, device, topk=32, methods=None, timings=None, native_subtree=False,
+                     intake='auto'):
     """Additive: the four saliency methods of generate_wb_smaps (:295-399) for a GROUP of independent jobs in shared launches.
     jobs: list of (im_mates, im_nonmates, probe_im).  Per job the calls of mean_ebp (always over the HOOKED N-way classifier,
     which is what the generator's job loop has installed at that point; the drop-in mean_ebp uses whatever classifier is
@@ -82,7 +101,8 @@ def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, dev
     'meanEBP', 'contrastive', 'truncated', 'weighted-subtree'.  Needs the hooked classifier for meanEBP (restored afterwards)
     and ebp_version 6 maps (float32) for the batched tails.  The three triplet methods run the same probes through the
     network: they share one forward pass (xfr_engine_hold_forward).  timings: optional dict that receives seconds per phase
-    (synchronises the device between phases).  native_subtree: the weighted subtree method as one engine call (xfr_weighted_subtree_ebp)."""
+    (synchronises the device between phases).  native_subtree: the weighted subtree method as one engine call (xfr_weighted_subtree_ebp).
+    intake: where the gallery images become bytes (encode_images above)."""
     import time
     methods = methods or ('meanEBP', 'contrastive', 'truncated', 'weighted-subtree')
     n = len(jobs)
@@ -109,8 +129,7 @@ def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, dev
         return out
     km = [len(j[0]) for j in jobs]
     kn = [len(j[1]) for j in jobs]
-    gallery = torch.cat([wb.convert_from_numpy(im) for j in jobs for im in list(j[0]) + list(j[1])], dim=0).to(device)
-    enc = torch.cat([wb.encode(gallery[i:i + wb.batch_size]).detach() for i in range(0, gallery.shape[0], wb.batch_size)], dim=0)
+    enc = encode_images(wb, [im for j in jobs for im in list(j[0]) + list(j[1])], device, wb.batch_size, intake)
     xm, xn, o = [], [], 0
     for a, b in zip(km, kn):
         m_ = enc[o:o + a].mean(dim=0, keepdim=True)

@@ -743,26 +743,68 @@ class Whitebox(object):
     def encode(self, x):
         return self.net.encode(x)
 
-    def embeddings(self, images, norm=True):
+    def intake(self, images):
+        """Additive: the uint8 device batch n x in_h x in_w x 3 that `encode_u8` takes, for a DataFrame or a list of file names / uint8 H x W x 3
+        arrays: image_loader's crops resized, truncated and (Light-CNN) resampled on the device (xfr_amd.intake, xfr_intake_u8_host) -- byte for
+        byte what convert_from_numpy hands to the network's `preprocess`, and what that does up to its pixel arithmetic.  Raises
+        xfr_amd.intake.IntakeRefused for what stays on the host: a network without u8_preprocess_spec, float arrays, a crop the call refuses."""
+        from .. import intake as _intake
+        from ..image_loader import NET_SIDE, intake_items
+        from .blackbox import STRISE_MAX_TAPS, WhiteboxBlackBox
+        spec = self.net.u8_preprocess_spec()
+        if spec is None:
+            raise _intake.IntakeRefused('the network states no uint8 preprocessing (u8_preprocess_spec)')
+        tables = WhiteboxBlackBox(self).resample_tables((NET_SIDE, NET_SIDE))
+        if tables is not None and max(int(t['count'].max()) for t in tables) > STRISE_MAX_TAPS:
+            raise _intake.IntakeRefused('a resampling table has more than %d taps' % STRISE_MAX_TAPS)
+        if tables is None and tuple(self.net.net.in_shape[1:]) != (NET_SIDE, NET_SIDE):
+            raise _intake.IntakeRefused('the network input is not %d x %d' % (NET_SIDE, NET_SIDE))
+        items = list(intake_items(images))
+        if not items or any(it is None for it in items):
+            raise _intake.IntakeRefused('float arrays (or no image at all): their chain stays on the host')
+        return _intake.device_bytes(self.net.engine(min(len(items), self.batch_size)), items, (NET_SIDE, NET_SIDE), tables)
+
+    def _intake_or_none(self, images, intake):
+        """The device batch of `intake`, or None where the host chain runs: intake 'host', or 'auto' and a refusal."""
+        from ..intake import IntakeRefused
+        if intake not in ('auto', 'host', 'device'):
+            raise ValueError("intake must be 'auto', 'host' or 'device', got %r" % (intake,))
+        if intake == 'host':
+            return None
+        try:
+            return self.intake(images)
+        except IntakeRefused:
+            if intake == 'device':
+                raise
+            return None
+
+    def embeddings(self, images, norm=True, intake='auto'):
         """whitebox.py:747-785: tensors / numpy arrays already in network format, or -- through xfr_amd.image_loader, the restatement of
-        xfr.utils.image_loader -- an inpainting-game DataFrame or a list of file names / H x W x 3 arrays."""
+        xfr.utils.image_loader -- an inpainting-game DataFrame or a list of file names / H x W x 3 arrays.  intake (additive): where the loader's
+        images are cropped, resized and truncated to bytes -- 'host' as convert_from_numpy does it, one image at a time; 'device' through
+        Whitebox.intake and encode_u8; 'auto' the device where it takes the images, else the host.  The same bytes either way."""
         from ..image_loader import image_loader
+        u8 = None
         if _is_dataframe(images):
-            imagesT = [self.convert_from_numpy(im)[0] for im in image_loader(images)]
+            u8 = self._intake_or_none(images, intake)
+            imagesT = [self.convert_from_numpy(im)[0] for im in image_loader(images)] if u8 is None else None
         elif isinstance(images[0], torch.Tensor):
             assert images[0].ndim == 3
             imagesT = images
-        elif isinstance(images[0], np.ndarray):
+        elif isinstance(images[0], np.ndarray) and not (images[0].ndim == 3 and images[0].shape[0] not in (1, 3) and images[0].shape[2] == 3):
             assert images[0].shape[0] in (1, 3)
             imagesT = [torch.from_numpy(im).float() for im in images]
         else:
-            imagesT = [self.convert_from_numpy(im)[0] for im in image_loader(images)]
-        if not isinstance(imagesT, torch.Tensor):
-            imagesT = torch.stack(list(imagesT))
-        batches = torch.split(imagesT, self.batch_size, dim=0)
+            u8 = self._intake_or_none(images, intake)
+            imagesT = [self.convert_from_numpy(im)[0] for im in image_loader(images)] if u8 is None else None
         # the reference moves every batch to the host as it goes (:776); here the encodings stay on the device until the last batch
         # is enqueued -- one synchronisation per call instead of one per batch (6500 masked probes per image at RISE scale)
-        embeds = [self.encode(batch).detach() for batch in batches]
+        if u8 is not None:
+            embeds = [self.net.encode_u8(batch).detach() for batch in torch.split(u8, self.batch_size, dim=0)]
+        else:
+            if not isinstance(imagesT, torch.Tensor):
+                imagesT = torch.stack(list(imagesT))
+            embeds = [self.encode(batch).detach() for batch in torch.split(imagesT, self.batch_size, dim=0)]
         embeds = torch.cat(embeds, dim=0).cpu().numpy()
         if norm:
             embeds = (embeds.reshape((embeds.shape[0], -1)) /
