@@ -783,7 +783,10 @@ xfr_status XFR_EX xfr_debug_contrast_tail(xfr_engine* e, const float* p_dev, int
  * in_dev/out_dev are CNHW device tensors ([C][NB][H][W]); w_host/bias_host are PyTorch-layout host arrays.
  * cfg % 100: 0 lets the launcher pick the tile configuration, 4 / 5 force the 16- / 32-deep 64x64 configuration;
  * (cfg / 10000) % 100: tail balancing 0 = heuristic, 1 = off, S >= 2 = S parts per tail tile; cfg / 1000000 = n in 2..4: the
- * launches go to n streams at once (aggregate rate of co-running launches; *ms_out is then the time per launch).  The kernel is run
+ * launches go to n streams at once (aggregate rate of co-running launches; *ms_out is then the time per launch).
+ * (cfg / 100) % 10 == 1: the lean probe-forward launch of a convolution behind BatchNorm (scale 1, shift 0) + ReLU -- the W and relu(W)
+ * tiles in one workgroup; the input must be non-negative (relu_in 0), nb * OH * OW a multiple of 4, and out_dev holds TWO tensors:
+ * relu(conv(W) + b), then q = relu(conv(W) + b) / (relu(conv(relu W) + b) + 1e-16) with its sign bit set where the first is <= 0.  The kernel is run
  * `reps` times after one untimed launch; *ms_out receives the average duration (HIP events on the null stream). */
 xfr_status xfr_debug_conv(const float* in_dev, const float* w_host, const float* bias_host, float* out_dev, int32_t cin,
                           int32_t h, int32_t w, int32_t nb, int32_t cout, int32_t kh, int32_t kw, int32_t stride,

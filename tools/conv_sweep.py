@@ -108,6 +108,8 @@ def main():
     ap.add_argument('--passes', type=int, default=2, help='measure the configuration list this many times per shape and report the fastest pass of each (order effects: clocks, caches)')
     ap.add_argument('--stamps', action='store_true', help='per-wave phase stamps of ONE launch per (shape, cfg): where the time goes')
     ap.add_argument('--clock', action='store_true', help='stamps ON during the timed launches: the effective shader clock (s_memtime cycles / s_memrealtime) over the workgroup records left in the buffer')
+    ap.add_argument('--lean', action='store_true', help='the lean two-accumulator launches (W and relu(W) tiles in one workgroup, xfr_debug_conv cfg + 100) of the 1x1 '
+                                                        'layers that take them in the ResNet-101 step, non-negative inputs; use with --nb 32; FLOPs counted twice')
     args = ap.parse_args()
     import torch
     from xfr_amd import _lib
@@ -115,6 +117,8 @@ def main():
     dev = torch.device('cuda', 0)
     cfgs = [int(c) for c in args.cfgs.split(',')]
     shapes = {'r101': R101, 'lcnn': LCNN, 'all': R101 + LCNN}[args.set]
+    if args.lean:      # 1024 <- 256 (M = 196 nb), 2048 <- 512 (49 nb), 128 <- 512 (784 nb)
+        shapes = [(256, 14, 14, 1024, 1, 1, 0), (512, 7, 7, 2048, 1, 1, 0), (512, 28, 28, 128, 1, 1, 0)]
     if args.only:
         shapes = [shapes[int(i)] for i in args.only.split(',')]
     nb = args.nb
@@ -124,14 +128,16 @@ def main():
         nbb = nb * 2 if (cin, h) == (1, 128) else nb
         g = torch.Generator().manual_seed(0)
         x = torch.randn((cin, nbb, h, w), generator=g).to(dev)
+        if args.lean:
+            x = x.clamp_min(0)
         wt = (torch.randn((cout, cin, k, k), generator=g) / (cin * k * k) ** 0.5).contiguous()
         b = torch.randn((cout,), generator=g)
         oh, ow = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-        flop = 2.0 * cin * k * k * cout * nbb * oh * ow
+        flop = 2.0 * cin * k * k * cout * nbb * oh * ow * (2 if args.lean else 1)
         first = None
         cells = []
         for c in cfgs:
-            out = torch.zeros((cout, nbb, oh, ow), device=dev)
+            out = torch.zeros(((2 if args.lean else 1) * cout, nbb, oh, ow), device=dev)      # lean: relu(conv) and, behind it, the stored quotient
             ms = ctypes.c_float()
             if args.clock:
                 nwg = 16384
@@ -140,7 +146,7 @@ def main():
             best = None
             for _ in range(max(1, args.passes if not (args.clock or args.stamps) else 1)):
                 _lib.check(lib.xfr_debug_conv(x.data_ptr(), wt.data_ptr(), b.data_ptr(), out.data_ptr(), cin, h, w, nbb, cout, k, k, stride,
-                                              pad, 0, c, args.reps, ctypes.byref(ms)))
+                                              pad, 0, c + (100 if args.lean else 0), args.reps, ctypes.byref(ms)))
                 torch.cuda.synchronize()
                 best = ms.value if best is None else min(best, ms.value)
             ms.value = best

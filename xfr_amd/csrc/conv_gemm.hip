@@ -900,6 +900,8 @@ static int pick_cfg_impl(const ConvParams& p_in, bool allow_split)
     // A dual-accumulator launch does the work of the dual (W / relu(W)) launch of the same layer with half the workgroups, twice as long each: it
     // takes the kernel that launch takes (the rules below see the dual launch's tile count), never the 32 x 128 tile.
     ConvParams p = p_in;
+    // bf16x6 first: the covered slab layers have a two-accumulator instantiation there (conv_gemm_split.hip DUAL; the grid rule counts ITS tiles)
+    if (p.dualacc && allow_split && p.split_ok && conv_gemm_split_wanted(p)) return CFG_BF16X6;
     if (p.dualacc) { p.nhalves = 2; p.dualacc = 0; const int c = pick_cfg_impl(p, false); return c == CFG_ROW32 ? CFG_K16 : c; }
     // Measured on MI355X over the ResNet-101 / ResNet-50 / Light-CNN GEMM shapes (M = 1.5k..400k, K = 64..4608,
     // Cout = 64..2048): the 64x64 tile wins or ties everywhere -- these grids are small (1-12 workgroups per CU), so

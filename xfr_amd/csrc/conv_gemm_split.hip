@@ -28,7 +28,8 @@ namespace {
 //     result registers with v_pk_add_f32, every other pass (patch mode: channel block) negated -- see `fold`;
 //   * the loop is unrolled by three (static X stage / register-set indices; up to two steps past the end multiply zeros), one counted wait and one raw
 //     barrier per step.
-// Layers: stride-1 convolutions (1x1 and tap-major KxK) with Cin % 16 == 0, 128 | Cout, no dual-accumulator launch, dense output.
+// Layers: stride-1 convolutions (1x1 and tap-major KxK) with Cin % 16 == 0, 128 | Cout, dense output; the lean two-accumulator launches of the slab
+// layers among them (DUAL, below).
 //
 // Why eight waves (round 6; profiles/r6/experiments/).  Round 5's kernel ran the tile on four waves, one per SIMD, and that wave issued its DMA (~150
 // cycles per instruction in a busy step), waited for its fragment reads and then fed 24 MFMAs, one thing after the other: ~1900 cycles per K-step for 768
@@ -95,10 +96,28 @@ __device__ __forceinline__ void sp8_wait_barrier()
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
+// CHAIN == 4 (DUAL, ConvParams::dualacc; slab mode): the lean probe-forward launch.  The workgroup accumulates the W tile AND the relu(W) tile from one W
+// DMA, one X staging and one set of B fragments -- four accumulator tiles per wave, 24 MFMAs per K-step.  The relu(W) A fragments are made from the W
+// fragments in registers (relu_pieces): no second pack is read.  Same passes, same product order, same sign phases per tile: the W tile gets the sums
+// the non-dual launch of the layer gets.  No K-parts (the exchange would have to park both tiles).
+typedef short v8s __attribute__((ext_vector_type(8)));
+// The pieces of relu(W) from the pieces of W.  p0 is the round-to-nearest bf16 of W and carries W's sign (W = 0: every piece 0), so with
+// m = all ones where p0 < 0 (v_pk_ashrrev_i16 by 15) the pieces of relu(W) are p_i & ~m.  NOT max(p_i, 0) piece by piece: p1 and p2 are signed
+// remainders -- a positive weight can have a negative p1 -- and clamping each by its own sign gives another number (tests/test_split_dual_arith.py).
+__device__ __forceinline__ void relu_pieces(const v8bf (&af)[3], v8bf (&ar)[3])
+{
+    const v8s keep = ~(__builtin_bit_cast(v8s, af[0]) >> 15);
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc) ar[pc] = __builtin_bit_cast(v8bf, (v8s)(__builtin_bit_cast(v8s, af[pc]) & keep));
+}
+
 template <bool RELU, int CHAIN, bool PATCH>
 __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParams p, const uint16_t* __restrict__ ws0, const uint16_t* __restrict__ ws1,
                                                                   const int n_co_tiles, const int n_m_tiles)
 {
+    constexpr bool DUAL = CHAIN == 4;
+    constexpr int NA = DUAL ? 4 : 2;              // accumulator tiles per wave: [0, 1] of W, DUAL: [2, 3] of relu(W), same columns
+    static_assert(!DUAL || (!RELU && !PATCH), "the dual-accumulator instantiation: slab mode, an input that is already clamped");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned char* lds = reinterpret_cast<unsigned char*>(smem);
     // W ring: NST stages, DMA issued D = NST - 1 steps ahead (round 6, NST 3 / 4 / 5 on the same box: 1592 / 1550 / 1480 maps/s -- the DMA's latency is not
@@ -198,9 +217,9 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
     const unsigned char* a_lane = lds + (lhi * SP_T + wr4 * 32 + l31) * 16;
     const unsigned char* b_plane = lds + XBASE + lhi * PS;
 
-    v16f acc[2], pipe[2];
+    v16f acc[NA], pipe[NA];
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < NA; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc[j][r] = 0.f; pipe[j][r] = 0.f; }
 
@@ -222,6 +241,10 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
     auto fold = [&](bool negated) {
         if (negated) { acc[0] -= pipe[0]; acc[1] -= pipe[1]; }
         else { acc[0] += pipe[0]; acc[1] += pipe[1]; }
+        if constexpr (DUAL) {
+            if (negated) { acc[2] -= pipe[2]; acc[3] -= pipe[3]; }
+            else { acc[2] += pipe[2]; acc[3] += pipe[3]; }
+        }
     };
     auto mfmas = [&](const v8bf (&af)[3], const v8bf (&bf)[3][2], auto FIRST) {
         constexpr int TA[6] = {2, 1, 0, 1, 0, 0}, TB[6] = {0, 1, 2, 0, 1, 0};
@@ -233,6 +256,16 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
 #pragma unroll
             for (int j = 0; j < 2; ++j)
                 pipe[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[TA[t]], bf[TB[t]][j], (t == 0 && decltype(FIRST)::value) ? zero : pipe[j], 0, 0, 0);
+        if constexpr (DUAL) {
+            // the relu(W) tiles behind the W tiles: the clamped fragments are made here, just before their MFMAs, under the twelve already issued
+            v8bf ar[3];
+            relu_pieces(af, ar);
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    pipe[2 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[TA[t]], bf[TB[t]][j], (t == 0 && decltype(FIRST)::value) ? zero : pipe[2 + j], 0, 0, 0);
+        }
     };
     std::integral_constant<int, 0> S0; std::integral_constant<int, 1> S1; std::integral_constant<int, 2> S2;
     std::integral_constant<bool, true> first; std::integral_constant<bool, false> later;
@@ -470,7 +503,14 @@ __global__ __launch_bounds__(NT8, 2) void conv_gemm_split_kernel(const ConvParam
     for (int c = 0; c < 2; ++c) {
         v16f t = acc[0];
         const int wq = (wr4 & 1) * 2 + c;
-        block_epilogue<CHAIN>(p, t, smem + (wave8 - wq) * (32 * 36), tid & 255, lane, wq, co0 + (wr4 >> 1) * 64, m0 + wc * 64, half, -1, 0, 1, osel, bsel, nullptr);
+        if constexpr (DUAL) {
+            // the compiled lean probe-forward epilogue of the fp32 two-accumulator kernels: bias on the W tile, bias_pos on the relu(W) tile
+            v16f tp = acc[2];
+            block_epilogue<4>(p, t, smem + (wave8 - wq) * (32 * 36), tid & 255, lane, wq, co0 + (wr4 >> 1) * 64, m0 + wc * 64, half, -1, 0, 1, osel, bsel, &tp);
+            acc[2] = acc[3];
+        } else {
+            block_epilogue<CHAIN>(p, t, smem + (wave8 - wq) * (32 * 36), tid & 255, lane, wq, co0 + (wr4 >> 1) * 64, m0 + wc * 64, half, -1, 0, 1, osel, bsel, nullptr);
+        }
         acc[0] = acc[1];
     }
     if (wave8 < 4) stamp(p, wave8, lane, 4);
@@ -508,9 +548,20 @@ bool split_patch_ok(const ConvParams& p)
 }
 
 // what the kernel can run at all (xfr_debug_conv with cfg 9 asks for exactly this) ...
+// A/B runs: XFR_SPLIT_DUAL=1 / 0 sends the lean two-accumulator launches (ConvParams::dualacc) of covered slab layers to the DUAL instantiation /
+// keeps them on the fp32 lean kernels, whatever the default below says.  Read once per process.
+constexpr bool SPLIT_DUAL_DEFAULT = true;
+bool split_dual_on()
+{
+    static const bool on = [] { const char* e = getenv("XFR_SPLIT_DUAL"); return e ? atoi(e) != 0 : SPLIT_DUAL_DEFAULT; }();
+    return on;
+}
 bool split_can_run(const ConvParams& p)
 {
-    if (p.dualacc || p.out_stride != 1 || p.as_strided || p.co_pair > 0 || p.stride != 1) return false;
+    if (p.out_stride != 1 || p.as_strided || p.co_pair > 0 || p.stride != 1) return false;
+    // two accumulator tiles: one pack, an input that is already clamped, behind a compiled lean epilogue (launch_split checks the signature), 1x1 layers
+    // only (KxK layers are staged as a patch, which has no two-accumulator form; their slab fallback was never measured with one)
+    if (p.dualacc && (!split_dual_on() || p.nhalves != 1 || p.relu_in || p.chain.n == 0 || p.kh != 1 || p.kw != 1)) return false;
     if ((p.Cin % SP_BK) != 0 || (p.K % SP_BK) != 0 || (p.CoutTot % SP_T) != 0) return false;
     if (p.kh == 1 && p.kw == 1) return p.pad == 0;
     return p.tap_major == 1 && p.kh * p.kw <= 64;
@@ -562,7 +613,7 @@ bool split_layer_ok(const ConvParams& p)
 // the workspace (64 KB per part) and the arrival counters (one per tile).  tail_force: 1 = none, S >= 2 = that many (tests, tools/conv_sweep.py).
 int split_pick_parts(const ConvParams& p)
 {
-    if (!p.tail_ws || !p.tail_cnt || p.tail_force == 1) return 1;
+    if (!p.tail_ws || !p.tail_cnt || p.tail_force == 1 || p.dualacc) return 1;      // (dualacc: the exchange parks one tile per part)
     const long tiles = (long)(p.CoutTot / SP_T) * p.nhalves * ((p.M + SP_T - 1) / SP_T);
     if (tiles > XFR_TAIL_MAX_TILES) return 1;
     const bool patch = split_patch_ok(p);
@@ -621,14 +672,18 @@ void launch_split_inst(const ConvParams& q, const uint16_t* w0, const uint16_t* 
     (void)hipGetDevice(&dev);
     const unsigned long long bit = 1ull << (dev & 63);
     constexpr int PATCH_LDS_MAX = 3 * SP_A_BYTES + 2 * 6 * (SP_T + 2 * SPP_MAX_HALO + 1) * 16;
+    constexpr bool HAS_PATCH = CHAIN != 4;      // the two-accumulator instantiation is slab only (split_can_run)
     if (!(done.load(std::memory_order_relaxed) & bit)) {
         (void)hipFuncSetAttribute((const void*)conv_gemm_split_kernel<RELU, CHAIN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SP_LDS);
-        (void)hipFuncSetAttribute((const void*)conv_gemm_split_kernel<RELU, CHAIN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PATCH_LDS_MAX);
+        if constexpr (HAS_PATCH)
+            (void)hipFuncSetAttribute((const void*)conv_gemm_split_kernel<RELU, CHAIN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PATCH_LDS_MAX);
         done.fetch_or(bit);
     }
     const dim3 grid(n_co * n_m * (q.tail_s > 1 ? q.tail_s : 1));
-    if (patch) hipLaunchKernelGGL((conv_gemm_split_kernel<RELU, CHAIN, true>), grid, dim3(NT8), spp_lds_bytes(q), s, q, w0, w1, n_co, n_m);
-    else hipLaunchKernelGGL((conv_gemm_split_kernel<RELU, CHAIN, false>), grid, dim3(NT8), SP_LDS, s, q, w0, w1, n_co, n_m);
+    if constexpr (HAS_PATCH) {
+        if (patch) { hipLaunchKernelGGL((conv_gemm_split_kernel<RELU, CHAIN, true>), grid, dim3(NT8), spp_lds_bytes(q), s, q, w0, w1, n_co, n_m); return; }
+    }
+    hipLaunchKernelGGL((conv_gemm_split_kernel<RELU, CHAIN, false>), grid, dim3(NT8), SP_LDS, s, q, w0, w1, n_co, n_m);
 }
 
 // false: the launch is not one the split kernel covers (or its pack is not registered) -- the caller takes the fp32 kernel the rules give
@@ -639,12 +694,12 @@ bool launch_split(const ConvParams& p, hipStream_t s)
     ConvParams q = p;
     q.tail_q = 0;
     q.tail_s = split_pick_parts(p);        // K-parts per tile (1: none)
-    int family = p.relu_in ? -1 : 0;       // -1: relu on the input, 0: plain epilogue, 1 / 3: compiled chain (3: MaxFeatureMap), 2: interpreted
+    int family = p.relu_in ? -1 : 0;       // -1: relu on the input, 0: plain epilogue, 1 / 3: compiled chain (3: MaxFeatureMap), 2: interpreted, 4: lean (two tiles)
     if (q.chain.n > 0) {
-        if (conv_gemm_plan_chain(q)) return false;
-        if (q.chain_sig >= 0 && chain_sig_is_dual(q.chain_sig)) return false;      // (only ever with dualacc, which the layer test excludes)
-        family = q.chain_sig < 0 ? 2 : (chain_sig_is_mfm(q.chain_sig) ? 3 : 1);
+        if (conv_gemm_plan_chain(q)) return false;      // (lean steps <=> dualacc: checked there)
+        family = q.chain_sig < 0 ? 2 : (chain_sig_is_dual(q.chain_sig) ? 4 : (chain_sig_is_mfm(q.chain_sig) ? 3 : 1));
     }
+    if ((family == 4) != (p.dualacc != 0)) return false;
     const bool patch = split_patch_ok(p);
     const int taps = patch ? p.kh * p.kw : 1;
     const uint16_t* w0 = split_planes(p.w, p.K, p.CoutTot, p.ldw, taps, s);
@@ -664,6 +719,7 @@ bool launch_split(const ConvParams& p, hipStream_t s)
         case 0: launch_split_inst<false, 0>(q, w0, w1, n_co, n_m, s, patch); break;
         case 1: launch_split_inst<false, 1>(q, w0, w1, n_co, n_m, s, patch); break;
         case 2: launch_split_inst<false, 2>(q, w0, w1, n_co, n_m, s, patch); break;
+        case 4: launch_split_inst<false, 4>(q, w0, w1, n_co, n_m, s, patch); break;
         default: launch_split_inst<false, 3>(q, w0, w1, n_co, n_m, s, patch); break;
     }
     return true;

@@ -1004,6 +1004,26 @@ xfr_status xfr_debug_conv(const float* in_dev, const float* w_host, const float*
     p.tail_ws = tws; p.tail_ws_bytes = XFR_TAIL_WS_BYTES;
     p.tail_cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(tws) + XFR_TAIL_WS_BYTES);
     p.tail_force = (cfg / 10000) % 100;  // 0 heuristic, 1 off, S >= 2 forced
+    // (cfg / 100) % 10 == 1: the lean probe-forward launch of a convolution behind BatchNorm + ReLU (forward.hip fuse_probe_forward) -- two accumulator
+    // tiles (ConvParams::dualacc), the chain LEAN_Q, AFFINE_C (scale 1, shift 0), RELU, LEAN_STORE.  out_dev then holds TWO tensors: relu(conv(W) + b),
+    // and behind it the stored quotient relu(conv(W) + b) / (relu(conv(relu W) + b) + 1e-16), sign bit set where the first is <= 0
+    const bool lean = (cfg / 100) % 10 == 1;
+    float* affine = nullptr;
+    if (lean) {
+        if (relu_in || (p.M & 3)) return fail(XFR_INVALID_ARG, "xfr_debug_conv: a lean launch reads a clamped input and needs M %% 4 == 0");
+        std::vector<float> ab(2 * (size_t)cout, 0.f);
+        std::fill(ab.begin(), ab.begin() + cout, 1.f);
+        HIP_TRY(hipMalloc(&affine, ab.size() * sizeof(float)));
+        HIP_TRY(hipMemcpy(affine, ab.data(), ab.size() * sizeof(float), hipMemcpyHostToDevice));
+        p.dualacc = 1; p.bias_pos = bd; p.chain_B = nb; p.chain_eps = 1e-16f;
+        EwChain& ch = p.chain;
+        auto push = [&](int type) -> EwStep& { EwStep& q = ch.s[ch.n++]; memset(&q, 0, sizeof(q)); q.type = type; q.prior_sb = -1; return q; };
+        push(EW_LEAN_Q);
+        { EwStep& q = push(EW_AFFINE_C); q.p0 = affine; q.p1 = affine + cout; }
+        push(EW_RELU);
+        { EwStep& q = push(EW_LEAN_STORE); q.action = 0; q.pstore = out_dev + (size_t)cout * p.M; }
+        if (conv_gemm_cannot_launch(p)) { (void)hipFree(affine); return fail(XFR_UNSUPPORTED_LAYER, "xfr_debug_conv: the lean chain has no compiled epilogue"); }
+    }
     const bool split = (cfg % 100) == CFG_BF16X6;  // the bf16x6 kernel (layers it does not cover run the fp32 kernel the rules give, like in the engine)
     hipEvent_t a, b;
     HIP_TRY(hipEventCreate(&a));
@@ -1057,6 +1077,7 @@ xfr_status xfr_debug_conv(const float* in_dev, const float* w_host, const float*
     if (split) conv_gemm_forget_split(wd, host.size() * sizeof(float));
     (void)hipFree(wd);
     if (bd) (void)hipFree(bd);
+    if (affine) (void)hipFree(affine);
     HIP_TRY(hipGetLastError());
     return XFR_OK;
 }
