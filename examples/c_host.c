@@ -2,7 +2,8 @@
  *
  * Builds a three-layer program (Conv 3x3 -> BatchNorm -> in-place ReLU -> Linear over the map -> L2 normalise), loads seeded
  * weights, and -- when a HIP device is visible -- encodes two images and runs one contrastive EBP (what Whitebox.contrastive_ebp,
- * python/xfr/models/whitebox.py:506-527, does through its hooks).  Without a device it prints the planner's schedule
+ * python/xfr/models/whitebox.py:506-527, does through its hooks), then the same probe as a Whitebox of ebp_version 5 converts it
+ * (whitebox.py:451-454: uint8 levels, Pillow's blur, uint8 levels) -- xfr_contrastive_u8.  Without a device it prints the planner's schedule
  * (xfr_plan_describe needs none) and the engine's loud refusal to run on the CPU.
  *
  *   gcc -std=c99 -Iinclude -Iexamples examples/c_host.c -Lxfr_amd/csrc -lxfr_amd -Wl,-rpath,$PWD/xfr_amd/csrc -lm -o c_host && ./c_host
@@ -100,6 +101,25 @@ int main(void)
     }
     const double rel = dmax / rmax, cosine = dot / sqrt(na * nb);
     printf("-- against the reference: encodings max|d| %.2e, map max|d|/max %.3e, cosine %.8f\n", enc_err, rel, cosine);
+    /* ---- the version-5 leg: the uint8 map of the same triplet in one call, and in two (the raw contrast, then its conversion): the same bytes */
+    static unsigned char sal5[IMG * IMG], sal5b[IMG * IMG];
+    float* d_raw = NULL;
+    unsigned char *d_sal5 = NULL, *d_sal5b = NULL;
+    hipMalloc_((void**)&d_raw, sizeof(sal)); hipMalloc_((void**)&d_sal5, sizeof(sal5)); hipMalloc_((void**)&d_sal5b, sizeof(sal5b));
+    if (xfr_contrastive_u8(e, d_img + 2 * IMG * IMG, 1, encode_tensor, d_seed, -1.0f, d_sal5, NULL) != XFR_OK ||
+        xfr_contrastive_raw(e, d_img + 2 * IMG * IMG, 1, encode_tensor, d_seed, -1.0f, d_raw, NULL) != XFR_OK ||
+        xfr_mwp_to_saliency_u8(e, d_raw, NULL, 1, IMG, IMG, d_sal5b, NULL) != XFR_OK) { fprintf(stderr, "%s\n", xfr_last_error()); return 1; }
+    hipDeviceSynchronize_();
+    hipMemcpy_(sal5, d_sal5, sizeof(sal5), 2);
+    hipMemcpy_(sal5b, d_sal5b, sizeof(sal5b), 2);
+    int mx5 = 0, mn5 = 255, arg5 = 0, differ = 0;
+    for (int i = 0; i < IMG * IMG; ++i) {
+        if (sal5[i] > mx5) { mx5 = sal5[i]; arg5 = i; }
+        if (sal5[i] < mn5) mn5 = sal5[i];
+        differ += sal5[i] != sal5b[i];
+    }
+    printf("-- ebp_version 5: uint8 saliency map %dx%d: levels %d..%d, max at (%d, %d); %d bytes differ from raw + xfr_mwp_to_saliency_u8\n", IMG, IMG,
+           mn5, mx5, arg5 / IMG, arg5 % IMG, differ);
     xfr_engine_destroy(e);
-    return (fabs(sum - 1.0) < 1e-3 && enc_err < 1e-5 && rel <= 1e-3 && cosine >= 0.99999) ? 0 : 1;
+    return (fabs(sum - 1.0) < 1e-3 && enc_err < 1e-5 && rel <= 1e-3 && cosine >= 0.99999 && mn5 == 0 && mx5 == 255 && differ == 0) ? 0 : 1;
 }

@@ -191,10 +191,17 @@ xfr_status xfr_contrastive(xfr_engine* e, const float* x_dev, int32_t n,
                            float* sal_dev, void* stream);
 
 /* As xfr_contrastive, but stops before _mwp_to_saliency: contrast_dev (N x H1 x W1) receives `mwp_contrastive` /
- * `mwp_truncated_contrastive` (whitebox.py:526 / :557), for callers that apply the uint8 + PIL blur of ebp_version != 6
- * (whitebox.py:451-454) on the host. */
+ * `mwp_truncated_contrastive` (whitebox.py:526 / :557).  The saliency conversion of ebp_version != 6 (whitebox.py:451-454) of these maps is
+ * xfr_mwp_to_saliency_u8; xfr_contrastive_u8 is both in one call. */
 xfr_status xfr_contrastive_raw(xfr_engine* e, const float* x_dev, int32_t n, int32_t seed_tensor, const float* seed_dev,
                                float percentile, float* contrast_dev, void* stream);
+
+/* xfr_contrastive for ebp_version != 6 (5 and 7-12: demo/test_whitebox.py:150,178, eval/eccv20.py:380,440,494): xfr_contrastive_raw followed on
+ * the same stream, without a host round trip, by xfr_mwp_to_saliency_u8 of the contrast maps (float32 form).  sal_dev: N x H1 x W1 bytes, the
+ * uint8 image Whitebox.contrastive_ebp / truncated_contrastive_ebp return for those versions.  Obeys the pipeline levels as xfr_contrastive_raw
+ * does; H1 x W1 <= 65536.  ABI version 7, additive. */
+xfr_status xfr_contrastive_u8(xfr_engine* e, const float* x_dev, int32_t n, int32_t seed_tensor, const float* seed_dev,
+                              float percentile, uint8_t* sal_dev, void* stream);
 
 /* One whole triplet step for N independent (mate, non-mate, probe) triplets -- demo/test_whitebox.py:124-133:
  *     x_mate = encode(mate); x_nonmate = encode(nonmate)                         (:71-72)
@@ -208,6 +215,12 @@ xfr_status xfr_contrastive_raw(xfr_engine* e, const float* x_dev, int32_t n, int
 xfr_status xfr_triplet_contrastive(xfr_engine* e, const float* probes_dev, const float* gallery_dev, int32_t n,
                                    int32_t encode_tensor, float scale, float percentile, float* sal_dev, void* stream,
                                    int32_t inputs_ready);
+/* The same step with the saliency conversion of ebp_version != 6 (xfr_mwp_to_saliency_u8, float32 form) in place of version 6's: float32 images
+ * in, sal_dev N x H1 x W1 BYTES out.  ("u8tail": the uint8 is the OUTPUT; xfr_triplet_contrastive_u8 / _u8_host below take uint8 INPUT images
+ * and return float maps.)  Everything else -- streams, pipelining, inputs_ready -- as xfr_triplet_contrastive.  ABI version 7, additive. */
+xfr_status xfr_triplet_contrastive_u8tail(xfr_engine* e, const float* probes_dev, const float* gallery_dev, int32_t n,
+                                          int32_t encode_tensor, float scale, float percentile, uint8_t* sal_dev, void* stream,
+                                          int32_t inputs_ready);
 
 /* Cross-call pipelining of xfr_triplet_contrastive (off by default).  When enabled, the engine keeps two forward slots
  * and the forwards of call i+1 start as soon as the slot they overwrite is free, i.e. they overlap the backward
@@ -354,6 +367,27 @@ xfr_status xfr_engine_set_forward_split(xfr_engine* e, int32_t enable);
 xfr_status xfr_mwp_to_saliency(xfr_engine* e, const float* pooled_dev, int32_t n, int32_t h, int32_t w,
                                float* sal_dev, void* stream);
 
+/* _mwp_to_saliency of every other ebp_version (whitebox.py:451-454) on N maps of h x w, one launch, one workgroup per map, to the byte what
+ * NumPy 2 and Pillow give:
+ *     img = np.uint8(255*((img-np.min(img))/(self.eps+(np.max(img)-np.min(img)))))         stage A
+ *     img = np.array(PIL.Image.fromarray(img).filter(PIL.ImageFilter.GaussianBlur(radius=2)))
+ *     img = np.uint8(255*((img-np.min(img))/(self.eps+(np.max(img)-np.min(img)))))         stage B
+ * Exactly one of the two inputs is non-NULL and selects the form of stage A:
+ *   pooled_dev  N x h x w float32 (a pooled MWP, a contrast map, a top-k subtree map): every operation a rounded float32 operation, with
+ *               float32(eps) -- (uint8)(255.0f * ((v - min) / (eps + (max - min)))), no fused multiply-add, no reciprocal;
+ *   levels_dev  N x h x w uint8 (the merged subtree map of XFR_SUBTREE_UINT8): NumPy evaluates the same expression in float64,
+ *               (uint8)(255.0 * ((double)(v - min) / (eps + (double)(max - min)))), and so does the call, literally: at eps = 1e-12 the levels
+ *               0..255 come back one lower (maximum 254), which no integer floor(255 v / d) reproduces.
+ * The blur is Pillow's: three extended box passes per axis (box radius 1, weights 4473924 / 2^24 for the three centre pixels and 1677722 / 2^24
+ * for the two at distance 2, replicated edges, + 2^23 >> 24 to bytes after every pass), rows then columns.  Stage B is the uint8 form on the blurred
+ * bytes.  A constant map gives zeros.  eps is the engine's (xfr_engine_set_mode, a float): the float32 form uses it as it is, the uint8 form widened
+ * to double -- for 1e-16 and 1e-12, the values the reference uses, eps + d rounds for every d = 1..255 as it does with the double literal.
+ * Inputs must be finite with a finite max - min (the reference is undefined otherwise, and so is the result here).  n, h, w >= 1 and
+ * h * w <= 65536 (a map lives in one workgroup's LDS), else XFR_INVALID_ARG; the reference's blur_radius is 2 everywhere and there is no other.
+ * sal_dev: N x h x w bytes.  Does not synchronise.  ABI version 7, additive. */
+xfr_status xfr_mwp_to_saliency_u8(xfr_engine* e, const float* pooled_dev, const uint8_t* levels_dev, int32_t n, int32_t h, int32_t w,
+                                  uint8_t* sal_dev, void* stream);
+
 /* ---- "next" row: layerwise_ebp / weighted_subtree_ebp (whitebox.py:561-581, 647-737) ------------------------------------
  * Firing indices are positions in Whitebox.P (reference order); the last one computed here is P[-2]. */
 
@@ -409,15 +443,19 @@ xfr_status xfr_layerwise_ebp(xfr_engine* e, const float* x_dev, int32_t n, int32
  *      output MWP:      / max(sum, eps);
  *      output SALIENCY: as MWP, then _mwp_to_saliency (ebp_version 6: gaussian blur, clamp, normalise) of the merged AND the top-k maps;
  *      output UINT8:    the levels of np.uint8(255 * (m - min) / (eps + max - min)) (ebp_version != 6, whitebox.py:726), stored as floats;
- *                       the reference's PIL blur of those versions stays with the caller.
- * smap_dev: N x H1 x W1.  top_dev (may be NULL): N x topk x H1 x W1, probe b's valid maps (pooled, or blurred for SALIENCY) in slots
+ *                       the top-k maps stay pooled float32 maps (do_mwp_to_saliency = False of those versions);
+ *      output UINT8_SALIENCY: as UINT8, then _mwp_to_saliency of those versions (xfr_mwp_to_saliency_u8: uint8 stretch, Pillow's
+ *                       GaussianBlur(2), uint8 stretch) of the merged map -- the uint8 form, its input being levels -- AND of the top-k maps --
+ *                       the float32 form; both stored as floats holding the exact integers 0..255.  Needs H1 x W1 <= 65536.
+ * smap_dev: N x H1 x W1.  top_dev (may be NULL): N x topk x H1 x W1, probe b's valid maps (pooled, or converted for the SALIENCY kinds) in slots
  * 0 .. n_valid[b]-1, zero beyond.  w_valid_host / k_valid_host: N x topk host arrays, the weights and firings of those maps in the same
  * ascending-weight order, padded with 0 / -1; n_valid_host: N.  A probe without any valid subtree fails the call with XFR_STATE_ERROR
  * and the reference's message (whitebox.py:710-715).  Synchronises `stream`. */
 typedef enum {
     XFR_SUBTREE_MWP = 0,
     XFR_SUBTREE_SALIENCY = 1,
-    XFR_SUBTREE_UINT8 = 2
+    XFR_SUBTREE_UINT8 = 2,
+    XFR_SUBTREE_UINT8_SALIENCY = 3
 } xfr_subtree_output;
 
 typedef int32_t (*xfr_subtree_order_fn)(const float* w, int32_t n_firings, int32_t probe, int32_t* order, void* user);

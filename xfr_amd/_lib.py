@@ -22,7 +22,7 @@ class U8Preprocess(ctypes.Structure):
 # xfr_weighted_subtree_ebp: the visiting-order callback, its arguments and its output modes (xfr_subtree_output)
 SUBTREE_ORDER_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_int32,
                                     ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p)
-SUBTREE_MWP, SUBTREE_SALIENCY, SUBTREE_UINT8 = range(3)
+SUBTREE_MWP, SUBTREE_SALIENCY, SUBTREE_UINT8, SUBTREE_UINT8_SALIENCY = range(4)
 INPAINT_PERCENT_DENSITY, INPAINT_THRESHOLDS = range(2)      # xfr_inpaint_method
 
 
@@ -92,6 +92,8 @@ SYMBOLS = [
     ('xfr_contrastive', _I, [_P, _P, _I, _I, _P, _F, _P, _P]),
     ('xfr_contrastive_raw', _I, [_P, _P, _I, _I, _P, _F, _P, _P]),
     ('xfr_triplet_contrastive', _I, [_P, _P, _P, _I, _I, _F, _F, _P, _P, _I]),
+    ('xfr_contrastive_u8', _I, [_P, _P, _I, _I, _P, _F, _P, _P]),
+    ('xfr_triplet_contrastive_u8tail', _I, [_P, _P, _P, _I, _I, _F, _F, _P, _P, _I]),
     ('xfr_engine_set_u8_preprocess', _I, [_P, ctypes.POINTER(U8Preprocess)]),
     ('xfr_forward_u8', _I, [_P, _P, _I, _I, _P, _P]),
     ('xfr_triplet_contrastive_u8', _I, [_P, _P, _P, _I, _I, _F, _F, _P, _P, _I]),
@@ -110,6 +112,7 @@ SYMBOLS = [
     ('xfr_engine_hold_forward', _I, [_P, _I]),
     ('xfr_engine_set_epilogue_fusion', _I, [_P, _I]),
     ('xfr_mwp_to_saliency', _I, [_P, _P, _I, _I, _I, _P, _P]),
+    ('xfr_mwp_to_saliency_u8', _I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     ('xfr_firing_count', _I, [_P, _I, ctypes.POINTER(_I)]),
     ('xfr_firing_kinds', _I, [_P, _I, ctypes.POINTER(_I), _I]),
     ('xfr_subtree_weights', _I, [_P, _P, _I, _I, _P, _I, ctypes.POINTER(_F), ctypes.POINTER(_I), _I, _P]),

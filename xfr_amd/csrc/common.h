@@ -425,6 +425,13 @@ void launch_reverse_slots(float* store, const int* cnt_dev, int N, int topk, int
 void launch_subtree_merge(const float* store, const SubtreeSlot* tab_dev, const int* cnt_dev, float* out, int N, int topk, int HW, int do_max,
                           int mode_u8, float eps, hipStream_t s);
 
+// _mwp_to_saliency of ebp_version != 6 (u8_tail.hip): stretch to uint8 levels, Pillow's GaussianBlur(2), stretch again; one workgroup per map of
+// H x W <= U8_TAIL_MAX_HW pixels.  Input: float32 maps (in_f), uint8 levels (in_b), or levels held as floats (in_f with levels_as_float); output:
+// bytes (out_b) or the levels as floats (out_f, which may be in_f).
+constexpr int U8_TAIL_MAX_HW = 65536;
+void launch_u8_tail(const float* in_f, const unsigned char* in_b, bool levels_as_float, unsigned char* out_b, float* out_f, int N, int H, int W,
+                    float eps, hipStream_t s);
+
 // ---- wavefront (64-lane) shuffle reductions of saliency.hip and strise.hip: the result is complete in lane 0 -------------------
 __device__ inline double wave_sum(double v)
 {

@@ -476,7 +476,9 @@ static xfr_status ensure_streams(xfr_engine* e)
     return XFR_OK;
 }
 
-static xfr_status contrastive_tail(xfr_engine* e, int n, float percentile, float* sal_dev, hipStream_t s, bool raw = false)
+enum ContrastTail { TAIL_V6 = 0, TAIL_RAW = 1, TAIL_U8 = 2 };      // _mwp_to_saliency of ebp_version 6 (float maps) / none / of the other versions (bytes)
+
+static xfr_status contrastive_tail(xfr_engine* e, int n, float percentile, void* out_dev, hipStream_t s, ContrastTail tail = TAIL_V6)
 {
     const Tensor& t1 = e->tens[1];
     const float* P = e->ws + e->tap_off;
@@ -487,26 +489,40 @@ static xfr_status contrastive_tail(xfr_engine* e, int n, float percentile, float
         thr = e->ws + e->thr_off;
         launch_truncation_threshold(P, sums, percentile, thr, e->trunc_ws, t1.C, n, t1.HW(), s);
     }
-    float* contrast = raw ? sal_dev : e->ws + e->blur_a_off;
+    float* contrast = tail == TAIL_RAW ? static_cast<float*>(out_dev) : e->ws + e->blur_a_off;
     launch_contrast(P, sums, thr, contrast, t1.C, n, t1.HW(), s);
-    if (!raw) launch_saliency_blur(contrast, e->ws + e->blur_b_off, sal_dev, n, t1.H, t1.W, e->eps, s);
+    if (tail == TAIL_V6) launch_saliency_blur(contrast, e->ws + e->blur_b_off, static_cast<float*>(out_dev), n, t1.H, t1.W, e->eps, s);
+    if (tail == TAIL_U8) launch_u8_tail(contrast, nullptr, false, static_cast<unsigned char*>(out_dev), nullptr, n, t1.H, t1.W, e->eps, s);
     HIP_TRY(hipGetLastError());
     return XFR_OK;
 }
 
-// xfr_contrastive / xfr_contrastive_raw: raw = the truncated contrast itself, without the saliency blur
+// the uint8 tail keeps a whole map in one workgroup's LDS
+static xfr_status check_u8_tail(xfr_engine* e, const char* who)
+{
+    const Tensor& t1 = e->tens[1];
+    if ((long)t1.H * t1.W > U8_TAIL_MAX_HW)
+        return fail(XFR_INVALID_ARG, "%s: maps of %d x %d exceed the %d pixels of the uint8 tail", who, t1.H, t1.W, U8_TAIL_MAX_HW);
+    return XFR_OK;
+}
+
+// xfr_contrastive / xfr_contrastive_raw / xfr_contrastive_u8: raw = the truncated contrast itself, without the saliency blur
 static xfr_status contrastive(xfr_engine* e, const float* x_dev, int32_t n, int32_t seed_tensor, const float* seed_dev, float percentile,
-                              float* out_dev, void* stream, bool raw)
+                              void* out_dev, void* stream, ContrastTail tail)
 {
     xfr_status st = check_run(e, x_dev, n);
     if (st != XFR_OK) return st;
     if (!out_dev) return fail(XFR_INVALID_ARG, "null output");
+    if (tail == TAIL_U8) {
+        st = check_u8_tail(e, "xfr_contrastive_u8");
+        if (st != XFR_OK) return st;
+    }
     if (percentile > 100.f) return fail(XFR_INVALID_ARG, "percentile must be <= 100 (or < 0 for plain contrastive)");
     hipStream_t s = (hipStream_t)stream;
     prof_begin(e);
     st = ebp_core(e, x_dev, n, 2, seed_tensor, seed_dev, s);
     if (st != XFR_OK) return st;
-    st = contrastive_tail(e, n, percentile, out_dev, s, raw);
+    st = contrastive_tail(e, n, percentile, out_dev, s, tail);
     if (st != XFR_OK) return st;
     return prof_end(e, s);
 }
@@ -514,22 +530,33 @@ static xfr_status contrastive(xfr_engine* e, const float* x_dev, int32_t n, int3
 xfr_status xfr_contrastive(xfr_engine* e, const float* x_dev, int32_t n, int32_t seed_tensor, const float* seed_dev,
                            float percentile, float* sal_dev, void* stream)
 {
-    return contrastive(e, x_dev, n, seed_tensor, seed_dev, percentile, sal_dev, stream, false);
+    return contrastive(e, x_dev, n, seed_tensor, seed_dev, percentile, sal_dev, stream, TAIL_V6);
 }
 
 xfr_status xfr_contrastive_raw(xfr_engine* e, const float* x_dev, int32_t n, int32_t seed_tensor, const float* seed_dev,
                                float percentile, float* contrast_dev, void* stream)
 {
-    return contrastive(e, x_dev, n, seed_tensor, seed_dev, percentile, contrast_dev, stream, true);
+    return contrastive(e, x_dev, n, seed_tensor, seed_dev, percentile, contrast_dev, stream, TAIL_RAW);
 }
 
-xfr_status xfr_triplet_contrastive(xfr_engine* e, const float* probes_dev, const float* gallery_dev, int32_t n,
-                                   int32_t encode_tensor, float scale, float percentile, float* sal_dev, void* stream,
-                                   int32_t inputs_ready)
+xfr_status xfr_contrastive_u8(xfr_engine* e, const float* x_dev, int32_t n, int32_t seed_tensor, const float* seed_dev,
+                              float percentile, uint8_t* sal_dev, void* stream)
+{
+    return contrastive(e, x_dev, n, seed_tensor, seed_dev, percentile, sal_dev, stream, TAIL_U8);
+}
+
+// xfr_triplet_contrastive (float maps, the ebp_version 6 tail) and xfr_triplet_contrastive_u8tail (bytes, the tail of the other versions)
+static xfr_status triplet_contrastive(xfr_engine* e, const float* probes_dev, const float* gallery_dev, int32_t n,
+                                      int32_t encode_tensor, float scale, float percentile, void* sal_dev, void* stream,
+                                      int32_t inputs_ready, ContrastTail tail)
 {
     xfr_status st = check_run(e, probes_dev, n);
     if (st != XFR_OK) return st;
     if (!gallery_dev || !sal_dev) return fail(XFR_INVALID_ARG, "null argument");
+    if (tail == TAIL_U8) {
+        st = check_u8_tail(e, "xfr_triplet_contrastive_u8tail");
+        if (st != XFR_OK) return st;
+    }
     if (2 * n > e->max_batch) return fail(XFR_INVALID_ARG, "triplet batch %d needs max_batch >= %d (the gallery forward runs 2n images)", n, 2 * n);
     if (percentile > 100.f) return fail(XFR_INVALID_ARG, "percentile must be <= 100 (or < 0 for plain contrastive)");
     if (encode_tensor < 2 || encode_tensor >= (int)e->tens.size()) return fail(XFR_INVALID_ARG, "bad encode tensor %d", encode_tensor);
@@ -605,7 +632,7 @@ xfr_status xfr_triplet_contrastive(xfr_engine* e, const float* probes_dev, const
     if (pipe) launch_copy_acc(seed_dst, e->G(encode_tensor), (long)sd.per_n() * 2 * n, 0, s);
     st = run_backward(e, *plan, n, 2, s);
     if (st != XFR_OK) return st;
-    st = contrastive_tail(e, n, percentile, sal_dev, s);
+    st = contrastive_tail(e, n, percentile, sal_dev, s, tail);
     if (st != XFR_OK) return st;
     if (pipe) {
         HIP_TRY(hipEventRecord(e->ev_slot_done[slot], s));
@@ -613,6 +640,20 @@ xfr_status xfr_triplet_contrastive(xfr_engine* e, const float* probes_dev, const
     }
     e->cur_slot = 0;
     return prof_end(e, s);
+}
+
+xfr_status xfr_triplet_contrastive(xfr_engine* e, const float* probes_dev, const float* gallery_dev, int32_t n,
+                                   int32_t encode_tensor, float scale, float percentile, float* sal_dev, void* stream,
+                                   int32_t inputs_ready)
+{
+    return triplet_contrastive(e, probes_dev, gallery_dev, n, encode_tensor, scale, percentile, sal_dev, stream, inputs_ready, TAIL_V6);
+}
+
+xfr_status xfr_triplet_contrastive_u8tail(xfr_engine* e, const float* probes_dev, const float* gallery_dev, int32_t n,
+                                          int32_t encode_tensor, float scale, float percentile, uint8_t* sal_dev, void* stream,
+                                          int32_t inputs_ready)
+{
+    return triplet_contrastive(e, probes_dev, gallery_dev, n, encode_tensor, scale, percentile, sal_dev, stream, inputs_ready, TAIL_U8);
 }
 
 xfr_status xfr_engine_set_u8_preprocess(xfr_engine* e, const xfr_u8_preprocess* p)
@@ -898,6 +939,20 @@ xfr_status xfr_mwp_to_saliency(xfr_engine* e, const float* pooled_dev, int32_t n
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     launch_saliency_blur(pooled_dev, e->ws + e->blur_b_off, sal_dev, n, h, w, e->eps, s);
+    HIP_TRY(hipGetLastError());
+    return XFR_OK;
+}
+
+xfr_status xfr_mwp_to_saliency_u8(xfr_engine* e, const float* pooled_dev, const uint8_t* levels_dev, int32_t n, int32_t h, int32_t w,
+                                  uint8_t* sal_dev, void* stream)
+{
+    if (!e || !sal_dev) return fail(XFR_INVALID_ARG, "xfr_mwp_to_saliency_u8: null argument");
+    if ((pooled_dev != nullptr) == (levels_dev != nullptr))
+        return fail(XFR_INVALID_ARG, "xfr_mwp_to_saliency_u8: exactly one of pooled_dev and levels_dev must be given, got %s", pooled_dev ? "both" : "neither");
+    if (n < 1 || h < 1 || w < 1 || (long)h * w > U8_TAIL_MAX_HW)
+        return fail(XFR_INVALID_ARG, "xfr_mwp_to_saliency_u8: n %d, h %d, w %d: need n, h, w >= 1 and h * w <= %d", n, h, w, U8_TAIL_MAX_HW);
+    HIP_TRY(hipSetDevice(e->device));
+    launch_u8_tail(pooled_dev, levels_dev, false, sal_dev, nullptr, n, h, w, e->eps, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return XFR_OK;
 }

@@ -269,8 +269,11 @@ xfr_status xfr_weighted_subtree_ebp(xfr_engine* e, const float* x_dev, int32_t n
     if (!seed_dev || !args || !smap_dev || !w_valid_host || !k_valid_host || !n_valid_host) return fail(XFR_INVALID_ARG, "null argument");
     const int topk = args->topk;
     if (topk < 1) return fail(XFR_INVALID_ARG, "xfr_weighted_subtree_ebp: topk %d, must be >= 1", topk);
-    if (args->output < XFR_SUBTREE_MWP || args->output > XFR_SUBTREE_UINT8)
+    if (args->output < XFR_SUBTREE_MWP || args->output > XFR_SUBTREE_UINT8_SALIENCY)
         return fail(XFR_INVALID_ARG, "xfr_weighted_subtree_ebp: output %d is not an xfr_subtree_output", args->output);
+    if (args->output == XFR_SUBTREE_UINT8_SALIENCY && (long)e->tens[1].H * e->tens[1].W > U8_TAIL_MAX_HW)
+        return fail(XFR_INVALID_ARG, "xfr_weighted_subtree_ebp: maps of %d x %d exceed the %d pixels of the uint8 tail", e->tens[1].H, e->tens[1].W,
+                    U8_TAIL_MAX_HW);
     if (args->sweep_batch < 0) return fail(XFR_INVALID_ARG, "xfr_weighted_subtree_ebp: sweep_batch %d < 0", args->sweep_batch);
     if (seed_tensor < 2 || seed_tensor >= (int)e->tens.size()) return fail(XFR_INVALID_ARG, "bad seed tensor %d", seed_tensor);
     // whitebox.py's first round: min(2 * max_batch / N, max(8, 2 * topk)) candidates per probe
@@ -440,7 +443,7 @@ xfr_status xfr_weighted_subtree_ebp(xfr_engine* e, const float* x_dev, int32_t n
     HIP_TRY(hipMemcpyAsync(e->wst_tab_d, e->wst_tab_h, (size_t)n * topk * sizeof(SubtreeSlot), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(e->wst_cnt_d, e->wst_cnt_h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
     launch_subtree_merge(store, e->wst_tab_d, e->wst_cnt_d, smap_dev, n, topk, HW, args->do_max_subtree ? 1 : 0,
-                         args->output == XFR_SUBTREE_UINT8 ? 1 : 0, e->eps, s);
+                         (args->output == XFR_SUBTREE_UINT8 || args->output == XFR_SUBTREE_UINT8_SALIENCY) ? 1 : 0, e->eps, s);
     if (top_dev) launch_reverse_slots(top_dev, e->wst_cnt_d, n, topk, HW, s);
     // 8. _mwp_to_saliency (ebp_version 6) of the merged map and the top-k maps, in place
     if (args->output == XFR_SUBTREE_SALIENCY) {
@@ -451,6 +454,12 @@ xfr_status xfr_weighted_subtree_ebp(xfr_engine* e, const float* x_dev, int32_t n
             for (long r0 = 0; r0 < maps; r0 += cap)
                 launch_saliency_blur(top_dev + r0 * HW, tmp, top_dev + r0 * HW, (int)std::min(cap, maps - r0), t1.H, t1.W, e->eps, s);
         }
+    }
+    // ... and of the other versions (whitebox.py:451-454), in place: the merged map holds uint8 levels and takes the uint8 form of the first
+    // stretch, the top-k maps are float32 maps (an empty slot is constant, hence stays zero); both come back as levels held in floats
+    if (args->output == XFR_SUBTREE_UINT8_SALIENCY) {
+        launch_u8_tail(smap_dev, nullptr, true, nullptr, smap_dev, n, t1.H, t1.W, e->eps, s);
+        if (top_dev) launch_u8_tail(top_dev, nullptr, false, nullptr, top_dev, n * topk, t1.H, t1.W, e->eps, s);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));

@@ -161,9 +161,11 @@ class Engine(object):
                                         pooled.data_ptr() if want_pooled else None, _stream_ptr(self.device)))
         return mwp, pooled
 
-    def contrastive(self, x, seed_tensor, seed, percentile=None, raw=False, inputs_ready=False):
+    def contrastive(self, x, seed_tensor, seed, percentile=None, raw=False, inputs_ready=False, tail='v6'):
         """seed: 2 x N x D (mate, non-mate).  Returns N x H1 x W1 saliency maps (raw=True: the contrastive MWP before
-        _mwp_to_saliency)."""
+        _mwp_to_saliency; tail='u8': the uint8 maps of ebp_version != 6, xfr_contrastive_u8)."""
+        if tail not in ('v6', 'u8') or (raw and tail != 'v6'):
+            raise ValueError("tail must be 'v6' or 'u8' (and 'v6' with raw=True), got %r" % (tail,))
         x, fresh = self._prep(x)
         self._declare_ready(inputs_ready and not fresh)
         n = x.shape[0]
@@ -172,17 +174,20 @@ class Engine(object):
         if tuple(seed.shape) != (2, n, d):
             raise ValueError('seed must be 2 x %d x %d, got %s' % (n, d, tuple(seed.shape)))
         c1, h1, w1 = self.tensor_shape(1)
-        sal = torch.empty((n, h1, w1), device=self.device)
+        sal = torch.empty((n, h1, w1), device=self.device, dtype=torch.uint8 if tail == 'u8' else torch.float32)
         pct = -1.0 if percentile is None else float(percentile)
         with torch.cuda.device(self.device):
-            fn = self.lib.xfr_contrastive_raw if raw else self.lib.xfr_contrastive
+            fn = self.lib.xfr_contrastive_raw if raw else (self.lib.xfr_contrastive_u8 if tail == 'u8' else self.lib.xfr_contrastive)
             _lib.check(fn(self._h, x.data_ptr(), n, int(seed_tensor), seed.data_ptr(), pct, sal.data_ptr(), _stream_ptr(self.device)))
         return sal
 
-    def triplet_contrastive(self, probes, gallery, encode_tensor, scale=1.0 / 2500.0, percentile=None, inputs_ready=False):
-        """probes N x C x H x W, gallery 2N x C x H x W (mates then non-mates) -> N x H1 x W1 saliency maps.
+    def triplet_contrastive(self, probes, gallery, encode_tensor, scale=1.0 / 2500.0, percentile=None, inputs_ready=False, tail='v6'):
+        """probes N x C x H x W, gallery 2N x C x H x W (mates then non-mates) -> N x H1 x W1 saliency maps (tail='u8': the uint8 maps of
+        ebp_version != 6, xfr_triplet_contrastive_u8tail).
         inputs_ready=True: both tensors are already valid on the device (not pending on the current stream) and will not be
         modified or freed until the result has been consumed -- required for cross-call pipelining (set_pipeline)."""
+        if tail not in ('v6', 'u8'):
+            raise ValueError("tail must be 'v6' or 'u8', got %r" % (tail,))
         probes, fresh = self._prep(probes)
         n = probes.shape[0]
         g_in = gallery
@@ -192,12 +197,12 @@ class Engine(object):
         if tuple(gallery.shape) != (2 * n,) + tuple(self.program.in_shape):
             raise ValueError('gallery must be %d x %s, got %s' % (2 * n, self.program.in_shape, tuple(gallery.shape)))
         c1, h1, w1 = self.tensor_shape(1)
-        sal = torch.empty((n, h1, w1), device=self.device)
+        sal = torch.empty((n, h1, w1), device=self.device, dtype=torch.uint8 if tail == 'u8' else torch.float32)
         pct = -1.0 if percentile is None else float(percentile)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.xfr_triplet_contrastive(self._h, probes.data_ptr(), gallery.data_ptr(), n, int(encode_tensor),
-                                                        float(scale), pct, sal.data_ptr(), _stream_ptr(self.device),
-                                                        1 if inputs_ready else 0))
+            fn = self.lib.xfr_triplet_contrastive_u8tail if tail == 'u8' else self.lib.xfr_triplet_contrastive
+            _lib.check(fn(self._h, probes.data_ptr(), gallery.data_ptr(), n, int(encode_tensor), float(scale), pct, sal.data_ptr(),
+                          _stream_ptr(self.device), 1 if inputs_ready else 0))
         return sal
 
     # -- uint8 inputs (include/xfr_amd.h: xfr_forward_u8 / xfr_triplet_contrastive_u8) ---------------------------------
@@ -364,6 +369,28 @@ class Engine(object):
                                                     _stream_ptr(self.device)))
         return out
 
+    def mwp_to_saliency_u8(self, t):
+        """_mwp_to_saliency of ebp_version != 6 (xfr_mwp_to_saliency_u8: uint8 stretch, Pillow's GaussianBlur(2), uint8 stretch) of N x H x W
+        maps -- float32 maps, or uint8 levels, which take NumPy's float64 form of the first stretch -> uint8 device tensor N x H x W.  Chunked
+        like the callers of mwp_to_saliency chunk: 2 x max_batch maps a call."""
+        t = t.detach()
+        if t.dtype != torch.uint8:
+            t = t.to(torch.float32)
+        t = t.to(self.device).contiguous()
+        if t.dim() != 3:
+            raise ValueError('expected maps as N x H x W, got %s' % (tuple(t.shape),))
+        n, h, w = t.shape
+        out = torch.empty((n, h, w), device=self.device, dtype=torch.uint8)
+        cap = max(1, 2 * self.max_batch)
+        with torch.cuda.device(self.device):
+            for i in range(0, max(n, 1), cap):
+                m = min(cap, n - i)
+                p = t[i:i + m].data_ptr() if m > 0 else None
+                f, b = (None, p) if t.dtype == torch.uint8 else (p, None)
+                _lib.check(self.lib.xfr_mwp_to_saliency_u8(self._h, f, b, m, h, w, out[i:i + m].data_ptr() if m > 0 else None,
+                                                           _stream_ptr(self.device)))
+        return out
+
     def contrast_tail(self, P, percentile=None):
         """Parity hook (xfr_debug_contrast_tail): the tail of contrastive(raw=True) on the caller's P, C x 2N x HW float32 in the engine's internal
         layout (rows 0 .. N-1 the mate sweep, N .. 2N-1 the non-mate sweep) -> (sums 2N float64, thr N float32 or None for the plain contrastive
@@ -456,12 +483,14 @@ class Engine(object):
                                                   _stream_ptr(self.device)))
         return out if (n > 1 or dense_prior is None) else out[:, 0]
 
-    SUBTREE_OUTPUTS = {'mwp': _lib.SUBTREE_MWP, 'saliency': _lib.SUBTREE_SALIENCY, 'uint8': _lib.SUBTREE_UINT8}
+    SUBTREE_OUTPUTS = {'mwp': _lib.SUBTREE_MWP, 'saliency': _lib.SUBTREE_SALIENCY, 'uint8': _lib.SUBTREE_UINT8,
+                       'uint8_saliency': _lib.SUBTREE_UINT8_SALIENCY}
 
     def weighted_subtree(self, x, seed_tensor, seeds, topk, gate_ge0=True, do_max_subtree=False, output='saliency', sweep_batch=None,
                          order='numpy', want_top=True):
         """weighted_subtree_ebp of N probes in one engine call (xfr_weighted_subtree_ebp, include/xfr_amd.h).  seeds: 3 x N x D (gate
-        output, non-mate output, EBP channel).  output: 'mwp', 'saliency' (ebp_version 6) or 'uint8' (the levels, as floats).
+        output, non-mate output, EBP channel).  output: 'mwp', 'saliency' (ebp_version 6), 'uint8' (the levels, as floats) or 'uint8_saliency'
+        (the saliency conversion of ebp_version != 6 of the merged and the top-k maps, levels as floats).
         order: 'numpy' -- np.argsort(w.astype(np.float64)), the reference's own call, through a callback; 'engine' -- the engine's rule
         (stable: ties ascend by firing index); or a callable f(w, probe) -> ascending order of the n_firings float32 weights w.
         Returns (smap N x H1 x W1, top N x topk x H1 x W1 or None -- both device tensors, slots in ascending weight order --, w_valid

@@ -90,7 +90,7 @@ def run_weighted_subtree_triplet_ebp(wb, im_mates, im_nonmates, probe_im, net_na
 
 
 def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, device, topk=32, methods=None, timings=None, native_subtree=False,
-                     intake='auto'):
+                     intake='auto', tail='v6'):
     """Additive: the four saliency methods of generate_wb_smaps (:295-399) for a GROUP of independent jobs in shared launches.
     jobs: list of (im_mates, im_nonmates, probe_im).  Per job the calls of mean_ebp (always over the HOOKED N-way classifier,
     which is what the generator's job loop has installed at that point; the drop-in mean_ebp uses whatever classifier is
@@ -98,8 +98,10 @@ def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, dev
     galleries encoded as batches (last-bit differences in the encodings, see ENCODE_ONE_BY_ONE); here all probes form one batch, all mate /
     non-mate images one encode batch, and each method one (or a few) engine calls: Whitebox.ebp at N probes,
     contrastive_triplet_ebp_batch, weighted_subtree_ebp_batch.  Returns {method: [map per job]} with the method keys
-    'meanEBP', 'contrastive', 'truncated', 'weighted-subtree'.  Needs the hooked classifier for meanEBP (restored afterwards)
-    and ebp_version 6 maps (float32) for the batched tails.  The three triplet methods run the same probes through the
+    'meanEBP', 'contrastive', 'truncated', 'weighted-subtree'.  Needs the hooked classifier for meanEBP (restored afterwards).
+    tail: the saliency conversion of the batched triplet methods (Whitebox._tail_is_uint8) -- 'v6' (the default) float32 maps of ebp_version 6
+    for 'contrastive' / 'truncated', 'uint8' the uint8 maps of the other versions, 'version' what wb's ebp_version prescribes, converted on the
+    device either way; meanEBP always follows wb's version, and so does the weighted subtree under 'v6' (as it always has).  The three triplet methods run the same probes through the
     network: they share one forward pass (xfr_engine_hold_forward).  timings: optional dict that receives seconds per phase
     (synchronises the device between phases).  native_subtree: the weighted subtree method as one engine call (xfr_weighted_subtree_ebp).
     intake: where the gallery images become bytes (encode_images above)."""
@@ -144,16 +146,16 @@ def run_jobs_batched(wb, jobs, net_name, subtree_mode_weighted, ebp_version, dev
     eng.hold_forward(True)
     try:
         if 'contrastive' in methods:
-            out['contrastive'] = list(wb.contrastive_triplet_ebp_batch(probes, xm / 2500.0, xn / 2500.0).cpu().numpy())
+            out['contrastive'] = list(wb.contrastive_triplet_ebp_batch(probes, xm / 2500.0, xn / 2500.0, tail=tail).cpu().numpy())
             lap('contrastive')
         if 'truncated' in methods:
-            out['truncated'] = list(wb.contrastive_triplet_ebp_batch(probes, xm / 2500.0, xn / 2500.0, percentile=20).cpu().numpy())
+            out['truncated'] = list(wb.contrastive_triplet_ebp_batch(probes, xm / 2500.0, xn / 2500.0, percentile=20, tail=tail).cpu().numpy())
             lap('truncated')
         if 'weighted-subtree' in methods:
             do_max_subtree, gating = SUBTREE_VERSIONS.get(ebp_version, (False, False))
             res = wb.weighted_subtree_ebp_batch(probes, xm, xn, k_poschannel=0, topk=topk, do_max_subtree=do_max_subtree,
                                                 do_mated_similarity_gating=gating, subtree_mode=subtree_mode_weighted,
-                                                native=native_subtree)
+                                                native=native_subtree, tail=tail)
             out['weighted-subtree'] = [r[0] for r in res]
             lap('weighted-subtree')
     finally:

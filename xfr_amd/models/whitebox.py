@@ -316,8 +316,9 @@ class Whitebox(object):
         return (img - np.min(img)) / (self.eps + (np.max(img) - np.min(img)))
 
     def _mwp_to_saliency(self, P, blur_radius=2):
-        """whitebox.py:448-460.  ebp_ver 6: HIP blur (gaussian sigma=2, nearest) + clamp + /sum.  Other versions:
-        the uint8 PIL path of the reference, on the host (not on the hot path)."""
+        """whitebox.py:448-460.  ebp_ver 6: HIP blur (gaussian sigma=2, nearest) + clamp + /sum.  Other versions: the uint8 PIL path of the
+        reference, on the host -- P is a host array here (plain `ebp`, direct calls); the methods whose maps are on the device convert them
+        there (Engine.mwp_to_saliency_u8, xfr_contrastive_u8, output 'uint8_saliency' of the native weighted subtree), to the same bytes."""
         img = P
         if self.convert_saliency_uint8:
             img = np.uint8(255 * ((img - np.min(img)) / (self.eps + (np.max(img) - np.min(img)))))
@@ -389,9 +390,8 @@ class Whitebox(object):
         n = img_probe.shape[0]
         eng = self._engine(n)
         seed_tensor, seeds = self._class_seeds(n, k_poschannel, k_negchannel)
-        if self.convert_saliency_uint8:      # ebp_version != 6: uint8 + PIL blur on the host (whitebox.py:451-454)
-            raw = eng.contrastive(img_probe, seed_tensor, seeds, None, raw=True).cpu().numpy()
-            out = np.stack([self._mwp_to_saliency(r) for r in raw])
+        if self.convert_saliency_uint8:      # ebp_version != 6: uint8 stretch, PIL blur, uint8 stretch (whitebox.py:451-454) -- xfr_contrastive_u8
+            out = eng.contrastive(img_probe, seed_tensor, seeds, None, tail='u8').cpu().numpy()
             return out[0] if n == 1 else out
         return self._squeeze(eng.contrastive(img_probe, seed_tensor, seeds, None))
 
@@ -401,35 +401,44 @@ class Whitebox(object):
         eng = self._engine(n)
         seed_tensor, seeds = self._class_seeds(n, k_poschannel, k_negchannel)
         if self.convert_saliency_uint8:
-            raw = eng.contrastive(img_probe, seed_tensor, seeds, float(percentile), raw=True).cpu().numpy()
-            out = np.stack([self._mwp_to_saliency(r) for r in raw])
+            out = eng.contrastive(img_probe, seed_tensor, seeds, float(percentile), tail='u8').cpu().numpy()
             return out[0] if n == 1 else out
         return self._squeeze(eng.contrastive(img_probe, seed_tensor, seeds, float(percentile)))
 
     # -- additive batched API --------------------------------------------------------------------------------
-    def contrastive_triplet_ebp_batch(self, img_probes, x_mates, x_nonmates, percentile=None):
+    def _tail_is_uint8(self, tail):
+        """The `tail` keyword of the batched API: 'v6' -- the float32 maps of ebp_version 6 (the default: what these calls have always returned);
+        'uint8' -- the uint8 maps of every other version (whitebox.py:451-454); 'version' -- whichever this Whitebox's ebp_version prescribes."""
+        if tail not in ('v6', 'uint8', 'version'):
+            raise ValueError("tail must be 'v6', 'uint8' or 'version', got %r" % (tail,))
+        return tail == 'uint8' or (tail == 'version' and self.convert_saliency_uint8)
+
+    def contrastive_triplet_ebp_batch(self, img_probes, x_mates, x_nonmates, percentile=None, tail='v6'):
         """N independent (mate, non-mate, probe) triplets in one call: for sample i equivalent to
         set_triplet_classifier(x_mates[i], x_nonmates[i]); (truncated_)contrastive_ebp(img_probes[i:i+1], 0, 1).
         x_mates / x_nonmates: N x D classifier rows (already scaled, e.g. encoding/2500:
-        demo/test_whitebox.py:129).  Returns N x H x W float32 (torch, on the engine device)."""
+        demo/test_whitebox.py:129).  Returns N x H x W float32 (torch, on the engine device); uint8 under tail 'uint8' / 'version'
+        (_tail_is_uint8)."""
         n = img_probes.shape[0]
         eng = self._engine(n)
         prog_marks = self.net._program.marks
         seeds = torch.stack((torch.as_tensor(x_mates, dtype=torch.float32).reshape(n, -1),
                              torch.as_tensor(x_nonmates, dtype=torch.float32).reshape(n, -1)), dim=0)
-        return eng.contrastive(img_probes, prog_marks['encode'], seeds, percentile)
+        return eng.contrastive(img_probes, prog_marks['encode'], seeds, percentile, tail='u8' if self._tail_is_uint8(tail) else 'v6')
 
     def triplet_images_ebp_batch(self, img_probes, img_mates, img_nonmates, scale=1.0 / 2500.0, percentile=None,
-                                 gallery=None, inputs_ready=False):
+                                 gallery=None, inputs_ready=False, tail='v6'):
         """The whole triplet step of demo/test_whitebox.py:124-133 for N triplets given as images: encode the mates and
         non-mates, install scale*encoding as the per-triplet 2-way classifier, (truncated) contrastive EBP of the probes.
-        Returns N x H x W float32 (torch, on the engine device)."""
+        Returns N x H x W float32 (torch, on the engine device); uint8 under tail 'uint8' / 'version' (_tail_is_uint8)."""
+        u8 = self._tail_is_uint8(tail)
         n = img_probes.shape[0]
         self.net.default_max_batch = max(self.net.default_max_batch, 2 * n)
         eng = self._engine(2 * n)
         if gallery is None:       # [mates; non-mates] as one 2N-image batch (pass `gallery` to avoid the copy)
             gallery = torch.cat((img_mates.to(eng.device), img_nonmates.to(eng.device)), dim=0)
-        return eng.triplet_contrastive(img_probes, gallery, self.net._program.marks['encode'], scale, percentile, inputs_ready)
+        return eng.triplet_contrastive(img_probes, gallery, self.net._program.marks['encode'], scale, percentile, inputs_ready,
+                                       tail='u8' if u8 else 'v6')
 
     def triplet_images_ebp_batch_u8(self, probes_u8, mates_u8, nonmates_u8, scale=1.0 / 2500.0, percentile=None, inputs_ready=False):
         """triplet_images_ebp_batch on uint8 N x H x W x C crops: a quarter of the input bytes cross the bus, the engine preprocesses."""
@@ -565,12 +574,20 @@ class Whitebox(object):
 
     def weighted_subtree_ebp_batch(self, img_probes, x_mates, x_nonmates, k_poschannel=0, topk=1, do_max_subtree=False,
                                    do_mated_similarity_gating=True, subtree_mode='norelu', do_mwp_to_saliency=True,
-                                   sweep_batch=None, native=False):
+                                   sweep_batch=None, native=False, tail='v6'):
         """Additive: weighted_subtree_ebp for N independent probes in shared launches (native=True: in one engine call).  For probe i equivalent to
         set_triplet_classifier(x_mates[i], x_nonmates[i]); weighted_subtree_ebp(img_probes[i:i+1], k_poschannel, 1 - k_poschannel...)
         with channel 0 the mate and channel 1 the non-mate.  The N forwards run once; the layer-weight pass carries 2N gradient
         streams, the capture pass N, and every round of layerwise sweeps J x N (J * N <= 2 * max_batch).  Returns a list of N
-        (smap, P_img_valid, P_subtree_valid, k_subtree_valid) tuples."""
+        (smap, P_img_valid, P_subtree_valid, k_subtree_valid) tuples.  tail: this method has always converted as the Whitebox's ebp_version
+        prescribes, and 'v6' (the default) and 'version' both leave it at that; 'uint8' gives the uint8 maps on a version-6 Whitebox too."""
+        if self._tail_is_uint8(tail) and not self.convert_saliency_uint8:
+            self.convert_saliency_uint8 = True
+            try:
+                return self.weighted_subtree_ebp_batch(img_probes, x_mates, x_nonmates, k_poschannel, topk, do_max_subtree, do_mated_similarity_gating,
+                                                       subtree_mode, do_mwp_to_saliency, sweep_batch, native)
+            finally:
+                self.convert_saliency_uint8 = False
         n = img_probes.shape[0]
         self._ebp_subtree_mode = subtree_mode
         eng = self._engine(n)
@@ -594,9 +611,9 @@ class Whitebox(object):
                                  do_mwp_to_saliency, sweep_batch):
         """_weighted_subtree as one engine call: selection, merge and (ebp_version 6) saliency conversion on the device; the visiting
         order is NumPy's argsort of the layer weights, handed to the engine through a callback, so the selection is the reference's.  The
-        uint8 versions get the reference's PIL blur here on the host, as in _merge_subtrees."""
+        uint8 versions get their levels and (do_mwp_to_saliency) the reference's PIL blur from the engine too: output 'uint8_saliency'."""
         uint8 = self.convert_saliency_uint8
-        output = 'uint8' if uint8 else ('saliency' if do_mwp_to_saliency else 'mwp')
+        output = ('uint8_saliency' if do_mwp_to_saliency else 'uint8') if uint8 else ('saliency' if do_mwp_to_saliency else 'mwp')
         x, _ = eng._prep(x)
         seeds = torch.stack([torch.as_tensor(v, dtype=torch.float32).reshape(x.shape[0], -1).to(eng.device) for v in (s0, s1, sk)], dim=0)
         smap, top, w_valid, k_valid, n_valid = eng.weighted_subtree(x, seed_tensor, seeds, topk, gate_ge0=do_mated_similarity_gating,
@@ -608,11 +625,10 @@ class Whitebox(object):
             k = int(n_valid[b])
             P_img_valid = [top[b, i] for i in range(k)]
             m = smap[b]
-            if uint8:
+            if uint8:                                   # levels 0..255 held as floats
                 m = m.astype(np.uint8)
                 if do_mwp_to_saliency:
-                    m = self._mwp_to_saliency(m)
-                    P_img_valid = [self._mwp_to_saliency(P) for P in P_img_valid]
+                    P_img_valid = [P.astype(np.uint8) for P in P_img_valid]
             res.append((m, P_img_valid, [float(v) for v in w_valid[b, :k]], [int(v) for v in k_valid[b, :k]]))
         return res
 
