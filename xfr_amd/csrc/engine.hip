@@ -1,38 +1,26 @@
 // engine.hip -- the C ABI (include/xfr_amd.h) of the EBP engine: engine life cycle, weights, switches, the forward / EBP / contrastive / triplet
 // entry points with their stream choreography, the uint8 inputs and the profiling getters.  The planner is plan.hip + plan_fuse.hip, the executors
-// forward.hip + backward.hip; the layerwise / weighted-subtree entry points are in subtree.hip, RCCL in comm.hip, xfr_plan_describe in plan_describe.hip.
+// forward.hip + backward.hip; the packs of the weight arena are weights.hip's; the layerwise / weighted-subtree entry points are in subtree.hip, the
+// xfr_debug_* ones in debug_abi.hip, RCCL in comm.hip, xfr_plan_describe in plan_describe.hip.
 #include "engine_internal.h"
 
 namespace xfr {
-
-thread_local std::string g_err;
-
-xfr_status fail(xfr_status st, const char* fmt, ...)
-{
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return st;
-}
 
 static xfr_status allocate(xfr_engine* e)
 {
     xfr_status st = layout_arena(e);
     if (st != XFR_OK) return st;
-    HIP_TRY(hipMalloc(&e->arena, e->arena_floats * sizeof(float)));
+    XFR_TRY(e->arena.alloc(e->arena_floats));
     st = layout_workspace(e);
     if (st != XFR_OK) return st;
     const size_t B = (size_t)e->max_batch;
-    HIP_TRY(hipMalloc(&e->ws, e->ws_floats * sizeof(float)));
-    HIP_TRY(hipMalloc(&e->fwd_idx[0], e->idx_bytes));
+    XFR_TRY(e->ws.alloc(e->ws_floats));
+    XFR_TRY(e->fwd_idx[0].alloc(e->idx_bytes));
     size_t hooks = 0;
     for (auto& x : e->tens) hooks += x.hooks.size();
     e->trace_cap = hooks;
-    HIP_TRY(hipMalloc(&e->dbl_ws, sizeof(double) * (2 * B + hooks * 2 * B + 64)));
-    HIP_TRY(hipMalloc(&e->trunc_ws, truncation_scratch_bytes((int)B)));
+    XFR_TRY(e->dbl_ws.alloc(2 * B + hooks * 2 * B + 64));
+    XFR_TRY(e->trunc_ws.alloc(truncation_scratch_bytes((int)B)));
     return XFR_OK;
 }
 
@@ -75,6 +63,25 @@ static xfr_status prof_end(xfr_engine* e, hipStream_t s)
     return XFR_OK;
 }
 
+// The fork of the internal streams: `a` (and `b`, when given) start behind everything already on the caller's stream `s` ...
+static xfr_status fork_streams(xfr_engine* e, hipStream_t s, hipStream_t a, hipStream_t b = nullptr)
+{
+    HIP_TRY(hipEventRecord(e->ev_fork, s));
+    HIP_TRY(hipStreamWaitEvent(a, e->ev_fork, 0));
+    if (b) HIP_TRY(hipStreamWaitEvent(b, e->ev_fork, 0));
+    return XFR_OK;
+}
+
+// ... and the join: `s` goes on behind what `a` (when given) and `b` hold now
+static xfr_status join_streams(xfr_engine* e, hipStream_t s, hipStream_t a, hipStream_t b)
+{
+    if (a) HIP_TRY(hipEventRecord(e->ev_a, a));
+    HIP_TRY(hipEventRecord(e->ev_b, b));
+    if (a) HIP_TRY(hipStreamWaitEvent(s, e->ev_a, 0));
+    HIP_TRY(hipStreamWaitEvent(s, e->ev_b, 0));
+    return XFR_OK;
+}
+
 // Any run that used forward slot 0 outside the pipelined paths must fence it, or a later pipelined forward (internal
 // stream) could overwrite activations this run's kernels on `s` are still using.
 xfr_status fence_slot0(xfr_engine* e, hipStream_t s)
@@ -108,17 +115,13 @@ xfr_status ebp_core(xfr_engine* e, const float* x_dev, int n, int S, int seed_te
     if (pipe && !ready) {
         // x_dev may still be pending on the caller's stream (a cast, a copy): order the internal forward after it.  Callers
         // whose inputs are resident declare it with xfr_engine_set_inputs_ready and keep the cross-call overlap.
-        HIP_TRY(hipEventRecord(e->ev_fork, s));
-        HIP_TRY(hipStreamWaitEvent(sf, e->ev_fork, 0));
+        XFR_TRY(fork_streams(e, s, sf));
     }
     struct LeanGuard { xfr_engine* e; ~LeanGuard() { e->lean_cur = nullptr; } } lean_guard{e};
     e->lean_cur = lean_applies(e, *plan, n) ? plan : nullptr;
     st = forward_all(e, x_dev, n, seed_tensor, true, sf);
     if (st != XFR_OK) { e->cur_slot = 0; return st; }
-    if (pipe) {
-        HIP_TRY(hipEventRecord(e->ev_b, sf));
-        HIP_TRY(hipStreamWaitEvent(s, e->ev_b, 0));
-    }
+    if (pipe) XFR_TRY(join_streams(e, s, nullptr, sf));
     const Tensor& sd = e->tens[seed_tensor];
     launch_seed_to_cnhw(seed_dev, e->G(seed_tensor), S * n, sd.C, sd.HW(), s);
     st = run_backward(e, *plan, n, S, s);
@@ -132,39 +135,12 @@ xfr_status ebp_core(xfr_engine* e, const float* x_dev, int n, int S, int seed_te
     return st;
 }
 
-// bf16 planes (K17) of every pack the bf16x6 kernel may be asked to run, built when the weights arrive instead of at a pack's first launch (round 5:
-// the first step after a weight change stalled once per covered layer).  Layers, not launches: the geometry of one image decides.
-void presplit_weights(xfr_engine* e)
+// precondition of every uint8 entry point
+xfr_status require_u8(xfr_engine* e)
 {
-    if (!e->arena || !e->weights_loaded || !e->split_mask) return;        // (packs that have their planes keep them)
-    for (size_t k = 0; k < e->ops.size(); ++k) {
-        const OpRec& o = e->ops[k];
-        const xfr_op_desc& d = o.d;
-        if (d.kind != XFR_OP_CONV && d.kind != XFR_OP_LINEAR) continue;
-        ConvParams p;
-        conv_geometry(e, (int)k, 1, p);
-        p.CoutTot = d.cout; p.nhalves = 1;
-        if ((e->split_mask & 1) && conv_gemm_split_covers(p)) {
-            (void)conv_gemm_presplit(p, e->arena + o.w_true, 0);
-            (void)conv_gemm_presplit(p, e->arena + o.w_pos, 0);
-        }
-        if ((e->split_mask & 2) && k != 0 && d.stride == 1) {
-            // the backward-data GEMM of a stride-1 convolution (bwd_conv_params): a convolution with the flipped, transposed pack
-            const Tensor& a = e->tens[d.in0];
-            const Tensor& t = e->tens[d.out];
-            ConvParams q;
-            memset(&q, 0, sizeof(q));
-            q.Cin = t.C; q.H = t.H; q.W = t.W;
-            q.kh = d.kh; q.kw = d.kw; q.stride = 1; q.pad = d.kh - 1 - d.pad; q.pad_dw = d.kw - d.kh;
-            q.OH = a.H; q.OW = a.W; q.out_stride = 1;
-            q.tap_major = o.tap_bwd ? 1 : 0;
-            q.CoutTot = a.C; q.nhalves = 1; q.ldw = o.ldb; q.K = o.Kb;
-            if (conv_gemm_split_covers(q)) {
-                (void)conv_gemm_presplit(q, e->arena + o.w_bwd, 0);
-                (void)conv_gemm_presplit(q, e->arena + o.w_bwd_true, 0);
-            }
-        }
-    }
+    if (!e) return fail(XFR_INVALID_ARG, "null engine");
+    if (!e->u8_set) return fail(XFR_STATE_ERROR, "xfr_engine_set_u8_preprocess has not been called");
+    return XFR_OK;
 }
 
 }  // namespace xfr
@@ -202,56 +178,7 @@ xfr_status xfr_engine_destroy(xfr_engine* e)
 {
     if (!e) return XFR_OK;
     (void)hipSetDevice(e->device);
-    for (int i = 0; i < 3; ++i) {
-        if (e->fwd_ws[i]) (void)hipFree(e->fwd_ws[i]);
-        if (e->fwd_idx[i]) (void)hipFree(e->fwd_idx[i]);
-    }
-    if (e->arena) { conv_gemm_forget_split(e->arena, e->arena_floats * sizeof(float)); (void)hipFree(e->arena); }
-    if (e->dbl_ws) (void)hipFree(e->dbl_ws);
-    if (e->trunc_ws) (void)hipFree(e->trunc_ws);
-    if (e->ws_enc) (void)hipFree(e->ws_enc);
-    for (int i = 0; i < e->n_tail_ws; ++i) (void)hipFree(e->tail_ws[i].ws);
-    if (e->cap_dev) (void)hipFree(e->cap_dev);
-    if (e->tab_elem_d) (void)hipFree(e->tab_elem_d);
-    if (e->tab_val_d) (void)hipFree(e->tab_val_d);
-    if (e->tab_elem_h) (void)hipHostFree(e->tab_elem_h);
-    if (e->tab_val_h) (void)hipHostFree(e->tab_val_h);
-    if (e->ev_tab) (void)hipEventDestroy(e->ev_tab);
-    if (e->stat_v) (void)hipFree(e->stat_v);
-    if (e->stat_i) (void)hipFree(e->stat_i);
-    if (e->stat_scratch) (void)hipFree(e->stat_scratch);
-    if (e->stat_desc) (void)hipFree(e->stat_desc);
-    if (e->stat_f2u) (void)hipFree(e->stat_f2u);
-    if (e->store_dev) (void)hipFree(e->store_dev);
-    if (e->wst_key_d) (void)hipFree(e->wst_key_d);
-    if (e->wst_key_h) (void)hipHostFree(e->wst_key_h);
-    if (e->wst_pairs_d) (void)hipFree(e->wst_pairs_d);
-    if (e->wst_pairs_h) (void)hipHostFree(e->wst_pairs_h);
-    if (e->wst_tab_d) (void)hipFree(e->wst_tab_d);
-    if (e->wst_tab_h) (void)hipHostFree(e->wst_tab_h);
-    if (e->wst_cnt_d) (void)hipFree(e->wst_cnt_d);
-    if (e->wst_cnt_h) (void)hipHostFree(e->wst_cnt_h);
-    if (e->wst_store) (void)hipFree(e->wst_store);
-    strise_release(e);
-    inpaint_release(e);
-    match_release(e);
-    finish_release(e);
-    intake_release(e);
-    sweep_release(e);
-    for (int i = 0; i < 3; ++i) { if (e->seedbuf[i]) (void)hipFree(e->seedbuf[i]); if (e->ev_slot_done[i]) (void)hipEventDestroy(e->ev_slot_done[i]); }
-    for (int i = 0; i < 3; ++i) {
-        if (e->u8_stage[i]) (void)hipFree(e->u8_stage[i]);
-        if (e->ev_copied[i]) (void)hipEventDestroy(e->ev_copied[i]);
-        if (e->ev_stage_a[i]) (void)hipEventDestroy(e->ev_stage_a[i]);
-        if (e->ev_stage_b[i]) (void)hipEventDestroy(e->ev_stage_b[i]);
-    }
-    if (e->s_copy) (void)hipStreamDestroy(e->s_copy);
-    if (e->s_a) (void)hipStreamDestroy(e->s_a);
-    if (e->s_b) (void)hipStreamDestroy(e->s_b);
-    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    if (e->ev_a) (void)hipEventDestroy(e->ev_a);
-    if (e->ev_b) (void)hipEventDestroy(e->ev_b);
-    for (auto& ev : e->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+    if (e->arena) conv_gemm_forget_split(e->arena, e->arena_floats * sizeof(float));      // before the arena goes: its bf16 planes (K17)
     delete e;
     return XFR_OK;
 }
@@ -262,75 +189,9 @@ xfr_status xfr_engine_load_weights(xfr_engine* e, const xfr_tensor_view* w, int3
     if (!e || !w) return fail(XFR_INVALID_ARG, "null argument");
     if (n_weights != e->n_weights) return fail(XFR_INVALID_ARG, "expected %d weight views, got %d", e->n_weights, n_weights);
     HIP_TRY(hipSetDevice(e->device));
-    std::vector<float> host(e->arena_floats, 0.f);
-    for (size_t k = 0; k < e->ops.size(); ++k) {
-        const OpRec& o = e->ops[k];
-        const xfr_op_desc& d = o.d;
-        if (d.kind == XFR_OP_CONV || d.kind == XFR_OP_LINEAR) {
-            const xfr_tensor_view& wv = w[d.w_weight];
-            const int khw = d.kh * d.kw;
-            if (!wv.data || wv.numel != (int64_t)d.cout * o.Cin * khw)
-                return fail(XFR_INVALID_ARG, "op %zu: weight has %lld elements, expected %lld", k, (long long)wv.numel,
-                            (long long)d.cout * o.Cin * khw);
-            float* wt = host.data() + o.w_true;
-            float* wp = host.data() + o.w_pos;
-            // forward pack: [k][co], k = (ci,kh,kw) or tap-major (kh,kw,ci)
-            // column of output channel co in the forward pack: interleaved halves for MaxFeatureMap convolutions (OpRec::pair)
-            auto col_of = [&](int co) { return o.pair ? (co % o.pair) * 2 + co / o.pair : co; };
-            for (int co = 0; co < d.cout; ++co) {
-                const float* src = wv.data + (size_t)co * o.K;
-                const int col = col_of(co);
-                for (int ci = 0; ci < o.Cin; ++ci)
-                    for (int tp = 0; tp < khw; ++tp) {
-                        const float v = src[ci * khw + tp];
-                        const size_t kk = o.tap4_fwd ? (size_t)tp * 4 + ci : (o.tap_fwd ? (size_t)tp * o.Cin + ci : (size_t)ci * khw + tp);
-                        wt[kk * o.ldw + col] = v;
-                        wp[kk * o.ldw + col] = v > 0.f ? v : 0.f;   // relu(W): whitebox.py:319
-                    }
-            }
-            if (o.w_bwd >= 0) {
-                // backward-data pack of relu(W): [k' = (co, kh', kw')][ci] with the kernel flipped
-                float* wb = host.data() + o.w_bwd;
-                float* wbt = host.data() + o.w_bwd_true;
-                for (int co = 0; co < d.cout; ++co)
-                    for (int ci = 0; ci < o.Cin; ++ci)
-                        for (int a = 0; a < d.kh; ++a)
-                            for (int b = 0; b < d.kw; ++b) {
-                                const float v = wv.data[(((size_t)co * o.Cin + ci) * d.kh + a) * d.kw + b];
-                                const int a2 = d.kh - 1 - a, b2 = d.kw - 1 - b;
-                                const size_t kk = (o.tap_bwd && d.stride == 1) ? (size_t)(a2 * d.kw + b2) * d.cout + co
-                                                                               : (size_t)(co * d.kh + a2) * d.kw + b2;
-                                wb[kk * o.ldb + ci] = v > 0.f ? v : 0.f;
-                                wbt[kk * o.ldb + ci] = v;
-                            }
-            }
-            if (d.w_bias >= 0) {
-                const xfr_tensor_view& bv = w[d.w_bias];
-                if (!bv.data || bv.numel != d.cout) return fail(XFR_INVALID_ARG, "op %zu: bad bias size", k);
-                for (int co = 0; co < d.cout; ++co) {
-                    host[o.b_true + col_of(co)] = bv.data[co];
-                    host[o.b_pos + col_of(co)] = bv.data[co] > 0.f ? bv.data[co] : 0.f;   // whitebox.py:323 (with_bias)
-                }
-            }
-        } else if (d.kind == XFR_OP_BATCHNORM) {
-            const int C = e->tens[d.out].C;
-            const xfr_tensor_view &g = w[d.w_weight], &b = w[d.w_bias], &m = w[d.w_mean], &v = w[d.w_var];
-            if (!g.data || !b.data || !m.data || !v.data || g.numel != C || b.numel != C || m.numel != C || v.numel != C)
-                return fail(XFR_INVALID_ARG, "op %zu: bad batchnorm parameter sizes", k);
-            for (int c = 0; c < C; ++c) {
-                // at::native inference batch norm: alpha = w * invstd, beta = b - mean * alpha
-                const float invstd = 1.0f / sqrtf(v.data[c] + d.fparam);
-                const float gp = g.data[c] > 0.f ? g.data[c] : 0.f;            // relu(gamma): whitebox.py:317-320
-                const float bp = b.data[c] > 0.f ? b.data[c] : 0.f;
-                const float at = g.data[c] * invstd, ap = gp * invstd;
-                host[o.bn_alpha_t + c] = at;
-                host[o.bn_beta_t + c] = b.data[c] - m.data[c] * at;
-                host[o.bn_alpha_p + c] = ap;
-                host[o.bn_beta_p + c] = b.data[c] - m.data[c] * ap;
-                host[o.bn_beta_pb + c] = bp - m.data[c] * ap;
-            }
-        }
-    }
+    std::vector<float> host;
+    const xfr_status st = pack_weights(e, w, host);
+    if (st != XFR_OK) return st;
     conv_gemm_forget_split(e->arena, e->arena_floats * sizeof(float));          // bf16 planes of the old weights (K17)
     HIP_TRY(hipMemcpy(e->arena, host.data(), e->arena_floats * sizeof(float), hipMemcpyHostToDevice));
     e->weights_loaded = true;
@@ -396,23 +257,15 @@ xfr_status xfr_forward(xfr_engine* e, const float* x_dev, int32_t n, int32_t ten
     // activation region (the one the triplet step's gallery forward uses); images are independent, the halves meet on the caller's stream.
     const int n0 = (n / 2) & ~3;
     if (e->split_forward && !e->profile_on && !e->hold_forward && n >= 32 && n0 >= 8) {
-        if (!e->ws_enc) HIP_TRY(hipMalloc(&e->ws_enc, (e->t_region_floats + 4096) * sizeof(float)));
+        if (!e->ws_enc) XFR_TRY(e->ws_enc.alloc(e->t_region_floats + 4096));
         st = ensure_streams(e);
         if (st != XFR_OK) return st;
         const Tensor& t = e->tens[tensor_id];
         const size_t in_per_n = (size_t)e->in_c * e->in_h * e->in_w;
         struct BankGuard { xfr_engine* e; ~BankGuard() { e->t_bank = nullptr; } } bank_guard{e};
-        HIP_TRY(hipEventRecord(e->ev_fork, s));          // after everything already on the caller's stream (inputs, earlier sweeps)
-        HIP_TRY(hipStreamWaitEvent(e->s_a, e->ev_fork, 0));
-        HIP_TRY(hipStreamWaitEvent(e->s_b, e->ev_fork, 0));
+        XFR_TRY(fork_streams(e, s, e->s_a, e->s_b));      // after everything already on the caller's stream (inputs, earlier sweeps)
         // whatever was enqueued on the internal streams (also by a half that then failed) is ordered before anything the caller puts on s next
-        auto join = [&]() -> xfr_status {
-            HIP_TRY(hipEventRecord(e->ev_a, e->s_a));
-            HIP_TRY(hipEventRecord(e->ev_b, e->s_b));
-            HIP_TRY(hipStreamWaitEvent(s, e->ev_a, 0));
-            HIP_TRY(hipStreamWaitEvent(s, e->ev_b, 0));
-            return XFR_OK;
-        };
+        auto join = [&]() -> xfr_status { return join_streams(e, s, e->s_a, e->s_b); };
         e->t_bank = e->ws_enc;
         st = forward_all(e, x_dev, n0, tensor_id, false, e->s_a);
         if (st != XFR_OK) { const std::string why = g_err; join(); g_err = why; return st; }
@@ -461,18 +314,20 @@ xfr_status xfr_ebp(xfr_engine* e, const float* x_dev, int32_t n, int32_t n_strea
 static xfr_status ensure_streams(xfr_engine* e)
 {
     if (e->s_a) return XFR_OK;
-    {
-        // The internal streams run forwards -- in pipelined mode the NEXT call's -- while the caller's stream runs the backward
-        // sweep whose maps the caller waits for: the forwards take the lowest priority, so the dispatcher prefers the sweep's
-        // workgroups when both have some ready (measured on MI355X: 26.81 -> 26.69 ms per step; forwards at high priority: 27.3)
-        int lowest = 0, highest = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&lowest, &highest));
-        HIP_TRY(hipStreamCreateWithPriority(&e->s_a, hipStreamNonBlocking, lowest));
-        HIP_TRY(hipStreamCreateWithPriority(&e->s_b, hipStreamNonBlocking, lowest));
-    }
-    HIP_TRY(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&e->ev_a, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&e->ev_b, hipEventDisableTiming));
+    // The internal streams run forwards -- in pipelined mode the NEXT call's -- while the caller's stream runs the backward
+    // sweep whose maps the caller waits for: the forwards take the lowest priority, so the dispatcher prefers the sweep's
+    // workgroups when both have some ready (measured on MI355X: 26.81 -> 26.69 ms per step; forwards at high priority: 27.3)
+    int lowest = 0, highest = 0;
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&lowest, &highest));
+    Stream a, b;
+    Event fork, ev_a, ev_b;
+    XFR_TRY(a.create(lowest));
+    XFR_TRY(b.create(lowest));
+    XFR_TRY(fork.create());
+    XFR_TRY(ev_a.create());
+    XFR_TRY(ev_b.create());
+    e->s_a = std::move(a); e->s_b = std::move(b);
+    e->ev_fork = std::move(fork); e->ev_a = std::move(ev_a); e->ev_b = std::move(ev_b);
     return XFR_OK;
 }
 
@@ -561,7 +416,7 @@ static xfr_status triplet_contrastive(xfr_engine* e, const float* probes_dev, co
     if (percentile > 100.f) return fail(XFR_INVALID_ARG, "percentile must be <= 100 (or < 0 for plain contrastive)");
     if (encode_tensor < 2 || encode_tensor >= (int)e->tens.size()) return fail(XFR_INVALID_ARG, "bad encode tensor %d", encode_tensor);
     hipStream_t s = (hipStream_t)stream;
-    if (!e->ws_enc) HIP_TRY(hipMalloc(&e->ws_enc, (e->t_region_floats + 4096) * sizeof(float)));
+    if (!e->ws_enc) XFR_TRY(e->ws_enc.alloc(e->t_region_floats + 4096));
     {
         xfr_status es = ensure_streams(e);
         if (es != XFR_OK) return es;
@@ -595,9 +450,7 @@ static xfr_status triplet_contrastive(xfr_engine* e, const float* probes_dev, co
                 HIP_TRY(hipStreamWaitEvent(sb, e->ev_slot_done[slot], 0));
             }
         } else {                               // order the forwards after everything already on the caller's stream
-            HIP_TRY(hipEventRecord(e->ev_fork, s));
-            HIP_TRY(hipStreamWaitEvent(sa, e->ev_fork, 0));
-            HIP_TRY(hipStreamWaitEvent(sb, e->ev_fork, 0));
+            XFR_TRY(fork_streams(e, s, sa, sb));
         }
         if (in_ev) {
             HIP_TRY(hipStreamWaitEvent(sa, in_ev, 0));
@@ -618,12 +471,7 @@ static xfr_status triplet_contrastive(xfr_engine* e, const float* probes_dev, co
     e->lean_cur = lean_applies(e, *plan, n) ? plan : nullptr;
     st = forward_all(e, probes_dev, n, encode_tensor, true, sb);
     if (st != XFR_OK) return st;
-    if (fork) {
-        HIP_TRY(hipEventRecord(e->ev_a, sa));
-        HIP_TRY(hipEventRecord(e->ev_b, sb));
-        HIP_TRY(hipStreamWaitEvent(s, e->ev_a, 0));
-        HIP_TRY(hipStreamWaitEvent(s, e->ev_b, 0));
-    }
+    if (fork) XFR_TRY(join_streams(e, s, sa, sb));
     if (stage_slot >= 0) {                     // the staging buffer may be overwritten once both forwards have read it
         HIP_TRY(hipEventRecord(e->ev_stage_a[stage_slot], sa));
         HIP_TRY(hipEventRecord(e->ev_stage_b[stage_slot], sb));
@@ -676,14 +524,6 @@ namespace {
 struct U8Guard { xfr_engine* e; explicit U8Guard(xfr_engine* e_) : e(e_) { e->u8_on = true; } ~U8Guard() { e->u8_on = false; } };
 }
 
-// precondition of every uint8 entry point
-static xfr_status require_u8(xfr_engine* e)
-{
-    if (!e) return fail(XFR_INVALID_ARG, "null engine");
-    if (!e->u8_set) return fail(XFR_STATE_ERROR, "xfr_engine_set_u8_preprocess has not been called");
-    return XFR_OK;
-}
-
 xfr_status xfr_forward_u8(xfr_engine* e, const uint8_t* x_u8_dev, int32_t n, int32_t tensor_id, float* out_dev, void* stream)
 {
     xfr_status st = require_u8(e);
@@ -719,22 +559,27 @@ xfr_status xfr_triplet_contrastive_u8_host(xfr_engine* e, const uint8_t* probes_
     }
     const size_t img = (size_t)e->u8_pre.channels * e->tens[0].HW();
     const size_t need = (size_t)(e->max_batch + e->max_batch / 2 + 1) * img;
-    if (!e->s_copy) HIP_TRY(hipStreamCreateWithFlags(&e->s_copy, hipStreamNonBlocking));
+    if (!e->s_copy) XFR_TRY(e->s_copy.create());
     // the slot the call below will take (xfr_triplet_contrastive: seq % n_slots when pipelined)
     const int slot = (e->pipeline && !e->profile_on) ? (int)(e->seq % e->n_slots) : 0;
-    if (!e->u8_stage[slot] || e->u8_stage_bytes < need) {
+    if (e->u8_stage[slot].cap < need) {
         for (int i = 0; i < 3; ++i) {
-            if (e->u8_stage[i]) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(e->u8_stage[i]); e->u8_stage[i] = nullptr; e->stage_busy[i] = false; }
+            if (e->u8_stage[i]) { HIP_TRY(hipDeviceSynchronize()); e->u8_stage[i].reset(); e->stage_busy[i] = false; }
         }
+        DevBuf<uint8_t> stage[3];
+        Event copied[3], stage_a[3], stage_b[3];
         for (int i = 0; i < 3; ++i) {
-            HIP_TRY(hipMalloc(&e->u8_stage[i], need));
+            XFR_TRY(stage[i].alloc(need));
             if (!e->ev_copied[i]) {
-                HIP_TRY(hipEventCreateWithFlags(&e->ev_copied[i], hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&e->ev_stage_a[i], hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&e->ev_stage_b[i], hipEventDisableTiming));
+                XFR_TRY(copied[i].create());
+                XFR_TRY(stage_a[i].create());
+                XFR_TRY(stage_b[i].create());
             }
         }
-        e->u8_stage_bytes = need;
+        for (int i = 0; i < 3; ++i) {
+            e->u8_stage[i] = std::move(stage[i]);
+            if (!e->ev_copied[i]) { e->ev_copied[i] = std::move(copied[i]); e->ev_stage_a[i] = std::move(stage_a[i]); e->ev_stage_b[i] = std::move(stage_b[i]); }
+        }
     }
     if (e->stage_busy[slot]) {                 // the forwards that last read this staging buffer
         HIP_TRY(hipStreamWaitEvent(e->s_copy, e->ev_stage_a[slot], 0));
@@ -760,61 +605,6 @@ xfr_status xfr_engine_wait_inputs_copied(xfr_engine* e)
 {
     if (!e) return fail(XFR_INVALID_ARG, "null engine");
     if (e->last_copied) HIP_TRY(hipEventSynchronize(e->last_copied));
-    return XFR_OK;
-}
-
-xfr_status xfr_debug_u8_preprocess(xfr_engine* e, const uint8_t* x_u8_dev, int32_t n, float* out_nchw_dev, void* stream)
-{
-    if (!e || !x_u8_dev || !out_nchw_dev) return fail(XFR_INVALID_ARG, "null argument");
-    xfr_status st = require_u8(e);
-    if (st != XFR_OK) return st;
-    if (n < 1 || n > e->max_batch) return fail(XFR_INVALID_ARG, "batch %d outside [1, %d]", n, e->max_batch);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    const Tensor& in = e->tens[0];
-    launch_u8hwc_to_cnhw(x_u8_dev, e->T(0), n, in.C, in.HW(), e->u8_pre, s);
-    launch_cnhw_to_nchw(e->T(0), out_nchw_dev, n, in.C, in.HW(), s);
-    HIP_TRY(hipGetLastError());
-    e->held_x = nullptr;
-    return fence_slot0(e, s);
-}
-
-// contrastive_tail's launches (without the blur) on the caller's tensor, with the sums and thresholds readable
-xfr_status xfr_debug_contrast_tail(xfr_engine* e, const float* p_dev, int32_t c, int32_t n, int32_t hw, float percentile, double* sums_dev,
-                                   float* thr_dev, float* contrast_dev, void* stream)
-{
-    if (!e || !p_dev || !contrast_dev)
-        return fail(XFR_INVALID_ARG, "debug_contrast_tail: null argument (e %p, p_dev %p, contrast_dev %p)", (void*)e, (const void*)p_dev, (void*)contrast_dev);
-    if (c < 1 || n < 1 || hw < 1 || n > 32767)
-        return fail(XFR_INVALID_ARG, "debug_contrast_tail: c %d, n %d, hw %d: each at least 1, 2 n at most 65535", c, n, hw);
-    if (!(percentile <= 100.f))
-        return fail(XFR_INVALID_ARG, "debug_contrast_tail: percentile %g: at most 100, or below 0 for the plain contrastive form", (double)percentile);
-    if (((uintptr_t)p_dev & 15) != 0)
-        return fail(XFR_INVALID_ARG, "debug_contrast_tail: p_dev %p is not 16-byte aligned", (const void*)p_dev);
-    {
-        const uintptr_t p0 = (uintptr_t)p_dev, p1 = p0 + (size_t)c * 2 * n * hw * sizeof(float);
-        const struct { const char* name; const void* ptr; size_t bytes; } outs[3] = {{"sums_dev", sums_dev, sizeof(double) * 2 * n},
-                                                                                     {"thr_dev", thr_dev, sizeof(float) * n},
-                                                                                     {"contrast_dev", contrast_dev, sizeof(float) * n * hw}};
-        for (const auto& o : outs)
-            if (o.ptr && (uintptr_t)o.ptr < p1 && p0 < (uintptr_t)o.ptr + o.bytes)
-                return fail(XFR_INVALID_ARG, "debug_contrast_tail: %s %p (%zu bytes) overlaps p_dev %p", o.name, o.ptr, o.bytes, (const void*)p_dev);
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    const bool truncated = percentile >= 0.f;
-    const size_t ws_bytes = truncation_scratch_bytes(n), sums_bytes = sizeof(double) * 2 * n;      // both multiples of 8
-    char* scratch = nullptr;
-    HIP_TRY(hipMalloc(&scratch, ws_bytes + sums_bytes + sizeof(float) * n));
-    double* sums = sums_dev ? sums_dev : reinterpret_cast<double*>(scratch + ws_bytes);
-    float* thr = !truncated ? nullptr : thr_dev ? thr_dev : reinterpret_cast<float*>(scratch + ws_bytes + sums_bytes);
-    launch_sample_sums(p_dev, sums, c, 2 * n, hw, s);
-    if (truncated) launch_truncation_threshold(p_dev, sums, percentile, thr, scratch, c, n, hw, s);
-    launch_contrast(p_dev, sums, thr, contrast_dev, c, n, hw, s);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipStreamSynchronize(s);      // the scratch goes away with the call
-    (void)hipFree(scratch);
-    if (err != hipSuccess) return fail(XFR_HIP_ERROR, "debug_contrast_tail: %s", hipGetErrorString(err));
     return XFR_OK;
 }
 
@@ -909,19 +699,27 @@ xfr_status xfr_engine_set_pipeline(xfr_engine* e, int32_t enable)
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     const bool three = enable > 0 && (enable & 4) != 0;
-    auto slot_state = [&](int i) -> xfr_status {
-        if (e->seedbuf[i]) return XFR_OK;
-        HIP_TRY(hipMalloc(&e->seedbuf[i], 2 * (size_t)e->max_batch * e->max_per_n() * sizeof(float)));
-        HIP_TRY(hipEventCreateWithFlags(&e->ev_slot_done[i], hipEventDisableTiming));
-        return XFR_OK;
-    };
-    for (int i = 1; enable && i < (three ? 3 : 2); ++i) {
-        if (e->fwd_ws[i]) continue;
-        HIP_TRY(hipMalloc(&e->fwd_ws[i], e->fwd_region_floats * sizeof(float)));
-        HIP_TRY(hipMalloc(&e->fwd_idx[i], e->idx_bytes));
+    // the slots' forward regions, argmax bytes, seed buffers and events: built together, committed together (slot 0's region and bytes are the
+    // workspace's own); seedbuf[i] stands for slot i
+    const int slots = enable ? (three ? 3 : 2) : 0;
+    DevBuf<float> region[3], seed[3];
+    DevBuf<uint8_t> idx[3];
+    Event done[3];
+    for (int i = 1; i < slots; ++i) {
+        if (e->seedbuf[i]) continue;
+        XFR_TRY(region[i].alloc(e->fwd_region_floats));
+        XFR_TRY(idx[i].alloc(e->idx_bytes));
     }
-    if (enable)
-        for (int i = 0; i < (three ? 3 : 2); ++i) { xfr_status ss = slot_state(i); if (ss != XFR_OK) return ss; }
+    for (int i = 0; i < slots; ++i) {
+        if (e->seedbuf[i]) continue;
+        XFR_TRY(seed[i].alloc(2 * (size_t)e->max_batch * e->max_per_n()));
+        XFR_TRY(done[i].create());
+    }
+    for (int i = 0; i < slots; ++i) {
+        if (e->seedbuf[i]) continue;
+        if (i > 0) { e->fwd_ws[i] = std::move(region[i]); e->fwd_idx[i] = std::move(idx[i]); }
+        e->seedbuf[i] = std::move(seed[i]); e->ev_slot_done[i] = std::move(done[i]);
+    }
     if (enable) { xfr_status es = ensure_streams(e); if (es != XFR_OK) return es; }
     e->pipeline = enable != 0;
     e->pipeline_all = enable > 0 && (enable & 2) != 0;
@@ -1010,148 +808,6 @@ xfr_status xfr_engine_get_trace(xfr_engine* e, double* sums, int32_t* kinds, int
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(sums, e->dbl_ws + 2 * e->max_batch, sizeof(double) * (size_t)nf * SB, hipMemcpyDeviceToHost));
     if (kinds) for (int i = 0; i < nf; ++i) kinds[i] = e->last_trace_kinds[i];
-    return XFR_OK;
-}
-
-xfr_status xfr_debug_conv(const float* in_dev, const float* w_host, const float* bias_host, float* out_dev, int32_t cin, int32_t h,
-                          int32_t w, int32_t nb, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad, int32_t relu_in,
-                          int32_t cfg, int32_t reps, float* ms_out)
-{
-    if (!in_dev || !w_host || !out_dev || cin < 1 || cout < 1 || kh < 1 || kw < 1 || stride < 1 || reps < 1)
-        return fail(XFR_INVALID_ARG, "xfr_debug_conv: bad arguments");
-    const int khw = kh * kw, K = cin * khw;
-    const int ldw = (int)align_up(cout, 128);
-    const bool tap = khw > 1 && (cin % 16 == 0) && khw <= 64;
-    const bool tap4 = khw > 1 && (cin == 3 || cin == 4) && khw <= 60;
-    const int Kf = tap4 ? 4 * khw : K;
-    std::vector<float> host(align_up(Kf, 32) * (size_t)ldw, 0.f);
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int tp = 0; tp < khw; ++tp) {
-                const size_t kk = tap4 ? (size_t)tp * 4 + ci : (tap ? (size_t)tp * cin + ci : (size_t)ci * khw + tp);
-                host[kk * ldw + co] = w_host[((size_t)co * cin + ci) * khw + tp];
-            }
-    float *wd = nullptr, *bd = nullptr;
-    HIP_TRY(hipMalloc(&wd, host.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(wd, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (bias_host) {
-        HIP_TRY(hipMalloc(&bd, cout * sizeof(float)));
-        HIP_TRY(hipMemcpy(bd, bias_host, cout * sizeof(float), hipMemcpyHostToDevice));
-    }
-    ConvParams p;
-    memset(&p, 0, sizeof(p));
-    p.in = in_dev; p.w = wd; p.bias = bd; p.out0 = out_dev;
-    p.Cin = cin; p.H = h; p.W = w; p.NB = nb; p.in_nb = nb; p.out_nb = nb;
-    p.kh = kh; p.kw = kw; p.stride = stride; p.pad = pad;
-    p.OH = (h + 2 * pad - kh) / stride + 1; p.OW = (w + 2 * pad - kw) / stride + 1;
-    p.K = Kf; p.K_logical = K; p.M = nb * p.OH * p.OW; p.CoutTot = cout; p.nhalves = 1; p.ldw = ldw;
-    p.relu_in = relu_in; p.out_H = p.OH; p.out_W = p.OW; p.out_stride = 1;
-    p.in_bytes = (unsigned)((size_t)cin * nb * h * w * sizeof(float));
-    p.tap_major = tap4 ? 2 : (tap ? 1 : 0); p.force_cfg = cfg % 100;
-    // ONE tail workspace for every call of the process (null stream; never freed), its arrival counters zeroed when it is made and never again: like
-    // a stream's workspace in the engine, it sees launches of different kernels and part counts one after the other, and a launch that left a counter
-    // behind would break the next call's (tests/test_gpu_split_kparts.py)
-    static float* tws = nullptr;
-    if (!tws) {
-        HIP_TRY(hipMalloc(&tws, XFR_TAIL_WS_BYTES + XFR_TAIL_MAX_TILES * sizeof(unsigned)));
-        HIP_TRY(hipMemset(reinterpret_cast<char*>(tws) + XFR_TAIL_WS_BYTES, 0, XFR_TAIL_MAX_TILES * sizeof(unsigned)));
-    }
-    p.tail_ws = tws; p.tail_ws_bytes = XFR_TAIL_WS_BYTES;
-    p.tail_cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(tws) + XFR_TAIL_WS_BYTES);
-    p.tail_force = (cfg / 10000) % 100;  // 0 heuristic, 1 off, S >= 2 forced
-    // (cfg / 100) % 10 == 1: the lean probe-forward launch of a convolution behind BatchNorm + ReLU (forward.hip fuse_probe_forward) -- two accumulator
-    // tiles (ConvParams::dualacc), the chain LEAN_Q, AFFINE_C (scale 1, shift 0), RELU, LEAN_STORE.  out_dev then holds TWO tensors: relu(conv(W) + b),
-    // and behind it the stored quotient relu(conv(W) + b) / (relu(conv(relu W) + b) + 1e-16), sign bit set where the first is <= 0
-    const bool lean = (cfg / 100) % 10 == 1;
-    float* affine = nullptr;
-    if (lean) {
-        if (relu_in || (p.M & 3)) return fail(XFR_INVALID_ARG, "xfr_debug_conv: a lean launch reads a clamped input and needs M %% 4 == 0");
-        std::vector<float> ab(2 * (size_t)cout, 0.f);
-        std::fill(ab.begin(), ab.begin() + cout, 1.f);
-        HIP_TRY(hipMalloc(&affine, ab.size() * sizeof(float)));
-        HIP_TRY(hipMemcpy(affine, ab.data(), ab.size() * sizeof(float), hipMemcpyHostToDevice));
-        p.dualacc = 1; p.bias_pos = bd; p.chain_B = nb; p.chain_eps = 1e-16f;
-        EwChain& ch = p.chain;
-        auto push = [&](int type) -> EwStep& { EwStep& q = ch.s[ch.n++]; memset(&q, 0, sizeof(q)); q.type = type; q.prior_sb = -1; return q; };
-        push(EW_LEAN_Q);
-        { EwStep& q = push(EW_AFFINE_C); q.p0 = affine; q.p1 = affine + cout; }
-        push(EW_RELU);
-        { EwStep& q = push(EW_LEAN_STORE); q.action = 0; q.pstore = out_dev + (size_t)cout * p.M; }
-        if (conv_gemm_cannot_launch(p)) { (void)hipFree(affine); return fail(XFR_UNSUPPORTED_LAYER, "xfr_debug_conv: the lean chain has no compiled epilogue"); }
-    }
-    const bool split = (cfg % 100) == CFG_BF16X6;  // the bf16x6 kernel (layers it does not cover run the fp32 kernel the rules give, like in the engine)
-    hipEvent_t a, b;
-    HIP_TRY(hipEventCreate(&a));
-    HIP_TRY(hipEventCreate(&b));
-    const int nstreams = std::max(1, std::min(4, cfg / 1000000));     // > 1: the same launches on several streams at once
-    p.tail_force = (cfg / 10000) % 100;
-    // untimed warm-up: as many launches as are timed (at most 200).  The allocations and copies above left the device idle; one launch
-    // does not bring the clocks back, and the first configuration of a sweep row then reads 5-12 % low (round 4: the same kernel measured
-    // first and third in a row)
-    for (int r = 0; r < std::max(1, std::min(reps, 200)); ++r) launch_conv_gemm(p, 0);
-    float ms = 0.f;
-    if (nstreams == 1) {
-        HIP_TRY(hipEventRecord(a, 0));
-        for (int r = 0; r < reps; ++r) launch_conv_gemm(p, 0);
-        HIP_TRY(hipEventRecord(b, 0));
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipEventElapsedTime(&ms, a, b));
-    } else {
-        // every stream needs its own tail-balancing scratch; the outputs coincide (same values)
-        hipStream_t st[4];
-        float* tw[4];
-        ConvParams q[4];
-        for (int i = 0; i < nstreams; ++i) {
-            HIP_TRY(hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking));
-            HIP_TRY(hipMalloc(&tw[i], XFR_TAIL_WS_BYTES + XFR_TAIL_MAX_TILES * sizeof(unsigned)));
-            q[i] = p;
-            q[i].tail_ws = tw[i];
-            q[i].tail_cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(tw[i]) + XFR_TAIL_WS_BYTES);
-            HIP_TRY(hipMemset(q[i].tail_cnt, 0, XFR_TAIL_MAX_TILES * sizeof(unsigned)));
-        }
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipEventRecord(a, 0));
-        for (int i = 0; i < nstreams; ++i) HIP_TRY(hipStreamWaitEvent(st[i], a, 0));
-        for (int r = 0; r < reps; ++r)
-            for (int i = 0; i < nstreams; ++i) launch_conv_gemm(q[i], st[i]);
-        for (int i = 0; i < nstreams; ++i) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(e, st[i]));
-            HIP_TRY(hipStreamWaitEvent(0, e, 0));
-            (void)hipEventDestroy(e);
-        }
-        HIP_TRY(hipEventRecord(b, 0));
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipEventElapsedTime(&ms, a, b));
-        ms /= nstreams;                       // per launch, all streams' launches counted
-        for (int i = 0; i < nstreams; ++i) { (void)hipStreamDestroy(st[i]); (void)hipFree(tw[i]); }
-    }
-    if (ms_out) *ms_out = ms / reps;
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    if (split) conv_gemm_forget_split(wd, host.size() * sizeof(float));
-    (void)hipFree(wd);
-    if (bd) (void)hipFree(bd);
-    if (affine) (void)hipFree(affine);
-    HIP_TRY(hipGetLastError());
-    return XFR_OK;
-}
-
-xfr_status xfr_debug_conv_stamps(void* stamps_dev, int32_t capacity_workgroups)
-{
-    if (stamps_dev && (capacity_workgroups == 0 || (capacity_workgroups < 0 && -capacity_workgroups < 256)))
-        return fail(XFR_INVALID_ARG, "xfr_debug_conv_stamps: capacity must be positive (or <= -256: sampled mode)");
-    conv_gemm_set_stamps(reinterpret_cast<unsigned long long*>(stamps_dev), capacity_workgroups);
-    return XFR_OK;
-}
-
-xfr_status xfr_debug_conv_log(void* log_dev, int32_t capacity, const char* dump_path)
-{
-    if (dump_path) {
-        const int n = conv_gemm_dump_log(dump_path);
-        if (n < 0) return fail(XFR_HIP_ERROR, "xfr_debug_conv_log: cannot write %s", dump_path);
-    }
-    conv_gemm_set_log(reinterpret_cast<unsigned long long*>(log_dev), capacity);
     return XFR_OK;
 }
 

@@ -1,10 +1,13 @@
 // engine_internal.h -- what the host translation units of the engine share: the planner's records (Hook, Tensor, OpRec, BwdStep, BwdPlan), the engine
-// object, the error helpers and the functions that cross files.  Nothing here is part of the C ABI (include/xfr_amd.h).
+// object, the families' state objects and the functions that cross files.  Nothing here is part of the C ABI (include/xfr_amd.h).
 //   plan.hip           shape inference, hook table, workspace / arena layout, the un-fused backward schedule (device-free)
 //   plan_fuse.hip      the fusion passes over that schedule and the lean rewrite (device-free)
 //   forward.hip        forward fusers and the forward executor
 //   backward.hip       chain resolution and the sweep executor
+//   hip_owner.h        the error helpers and the owners of device buffers, pinned buffers, events and streams (included here)
 //   engine.hip         the C ABI: create / destroy / weights / setters / forward / EBP / contrastive / triplet / uint8 / profiling
+//   weights.hip        the packs of the weight arena, filled on the host; the bf16 planes of the covered packs
+//   debug_abi.hip      the C ABI: the xfr_debug_* entry points
 //   subtree.hip        the C ABI: layerwise and weighted-subtree EBP
 //   probe_sweep.hip    the batched sweep with its side stream that the next two share (ProbeSweep)
 //   strise_abi.hip     the C ABI: STRise blackbox saliency
@@ -17,6 +20,7 @@
 #pragma once
 #include "../../include/xfr_amd.h"
 #include "common.h"
+#include "hip_owner.h"
 
 #include <algorithm>
 #include <cmath>
@@ -26,21 +30,11 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
 namespace xfr {
-
-extern thread_local std::string g_err;      // text of the calling thread's last error (xfr_last_error); defined in engine.hip
-xfr_status fail(xfr_status st, const char* fmt, ...);
-
-#define HIP_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess)                                                                             \
-            return fail(_e == hipErrorOutOfMemory ? XFR_OOM : XFR_HIP_ERROR, "%s failed: %s (%s:%d)", #expr, \
-                        hipGetErrorString(_e), __FILE__, __LINE__);                                       \
-    } while (0)
 
 enum PState { PS_EQ = 0, PS_RELU = 1, PS_OTHER = 2 };
 
@@ -128,13 +122,58 @@ using namespace xfr;
 
 // xfr_strise_* and xfr_inpaint_*: what their sweeps share, one per engine (probe_sweep.hip)
 struct ProbeSweep {
-    hipStream_t s_gen = nullptr;                       // the images of batch i + 1 are built here while batch i encodes
-    hipEvent_t ev_in = nullptr, ev_ready[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
-    hipEvent_t ev_done = nullptr;                      // the end of the previous call of either family, on that call's stream
+    Stream s_gen;                                      // the images of batch i + 1 are built here while batch i encodes
+    Event ev_in, ev_ready[2], ev_free[2];
+    Event ev_done;                                     // the end of the previous call of either family, on that call's stream
     bool done_recorded = false;
-    float* xbuf[2] = {nullptr, nullptr};               // two batches of network input, max_batch x in_c x in_h x in_w
-    float* emb = nullptr;                              // max_batch x D embeddings of the running batch
-    size_t emb_floats = 0;
+    DevBuf<float> xbuf[2];                             // two batches of network input, max_batch x in_c x in_h x in_w
+    DevBuf<float> emb;                                 // max_batch x D embeddings of the running batch
+};
+
+// The families' own buffers, one object per engine, built on first use.  Every member is an owner: the object goes with the engine.
+struct StriseState {                                   // xfr_strise_* (strise_abi.hip)
+    DevBuf<double> orig;                               // n_refs + n_gal similarities of the unmasked probe, then as many 1 / |g|
+    DevBuf<int> tab;                                   // cells, shifts, shift order and group offsets of the current call
+    DevBuf<double> merge_ws;                           // A [scale^2][gh * gw] and wsum [scale^2]
+};
+
+struct InpaintState {                                  // xfr_inpaint_* (inpaint_abi.hip)
+    DevBuf<char> scratch;                              // per map: the sort's keys, indices and running sums
+    DevBuf<uint8_t> first_on;                          // n_maps x H x W
+};
+
+struct MatchState {                                    // xfr_embed_templates / xfr_pair_dists (match_abi.hip)
+    Event ev_done;                                     // the end of the previous call, on that call's stream: its kernels read `tab`
+    bool done_recorded = false;
+    DevBuf<int> tab;                                   // the index table of the running call
+};
+
+struct FinishState {                                   // xfr_finish_saliency (finish_abi.hip)
+    Event ev_done;                                     // the end of the previous call, on that call's stream: its kernels read all of the below
+    bool done_recorded = false;
+    DevBuf<double> planes;                             // the padded coefficient planes of the running call's maps
+    DevBuf<double> stats;                              // FINISH_STATS doubles per map
+    DevBuf<float> totals;                              // the caller's totals
+    DevBuf<double> lut;                                // the colour table, uploaded when it differs from lut_host
+    double lut_host[768];
+    bool lut_set = false;
+};
+
+struct IntakeKernel { double sigma; int radius; double w[INTAKE_WEIGHTS]; };      // w[0 .. radius], w[radius] the centre
+
+struct IntakeState {                                   // xfr_intake_u8[_host] (intake_abi.hip)
+    Event ev_done;                                     // the end of the previous call, on that call's stream: its kernels read all of the below
+    Event ev_copied;                                   // the end of the previous upload on the engine's copy stream
+    bool done_recorded = false, copied_recorded = false;
+    DevBuf<IntakeItem> items;                          // the running call's crops
+    DevBuf<double> wts;                                // [n][2][INTAKE_WEIGHTS]
+    DevBuf<double> lohi;                               // [n][2]
+    DevBuf<double> plane_a, plane_b;                   // the pre-filter's two planes of a chunk
+    DevBuf<uint8_t> q, mid;                            // with tap tables: the zoom's bytes, then the horizontal pass's
+    DevBuf<StriseTap> taps;                            // row table, then column table
+    DevBuf<uint8_t> stage_dev;                         // xfr_intake_u8_host: the sources on the device ...
+    PinnedBuf<uint8_t> stage_host;                     // ... and in pinned host memory on their way there
+    std::vector<IntakeKernel> stated;                  // the caller's own kernels (xfr_intake_set_kernels)
 };
 
 struct xfr_engine {
@@ -144,20 +183,29 @@ struct xfr_engine {
     std::vector<OpRec> ops;
     std::vector<Tensor> tens;
     int n_weights = 0;
+    // Streams and events first: members go in reverse order, so every buffer below is freed before the streams and events it was used on.
+    Stream s_a, s_b;                   // the two internal streams, with ev_fork / ev_a / ev_b one all-or-nothing group (ensure_streams)
+    Event ev_fork, ev_a, ev_b;
+    // xfr_triplet_contrastive_u8_host: the engine's own copy stream and one uint8 staging buffer per forward slot -- fresh inputs keep the cross-call overlap
+    Stream s_copy;
+    Event ev_copied[3], ev_stage_a[3], ev_stage_b[3];
+    Event ev_slot_done[3];             // cross-step pipelining, with seedbuf[] below
+    Event ev_tab;                      // the last host-to-device table copy (subtree scratch)
+    std::vector<std::pair<Event, Event>> ev_pool;      // profiling: one pair per GEMM launch of a run
     // parameters
-    float* arena = nullptr;
+    DevBuf<float> arena;
     size_t arena_floats = 0;
     bool weights_loaded = false;
     // workspace
-    float* fwd_ws[3] = {nullptr, nullptr, nullptr};      // [0]: the whole workspace (forward slot 0, gradients, scratch); [1], [2]: the forward regions of pipeline slots 1 and 2
-    float*& ws = fwd_ws[0];
+    DevBuf<float> fwd_ws[3];           // [0]: the whole workspace (forward slot 0, gradients, scratch); [1], [2]: the forward regions of pipeline slots 1 and 2
+    DevBuf<float>& ws = fwd_ws[0];
     size_t ws_floats = 0;
-    uint8_t* fwd_idx[3] = {nullptr, nullptr, nullptr};   // max-pool argmax bytes, per forward slot
+    DevBuf<uint8_t> fwd_idx[3];        // max-pool argmax bytes, per forward slot
     size_t idx_bytes = 0;
     size_t x_off = 0, seed_off = 0, tap_off = 0, pooled_off = 0, blur_a_off = 0, blur_b_off = 0, misc_off = 0, thr_off = 0;
-    double* dbl_ws = nullptr;      // sums [2*maxB] + trace
+    DevBuf<double> dbl_ws;         // sums [2*maxB] + trace
     size_t trace_cap = 0;          // firings capacity
-    void* trunc_ws = nullptr;
+    DevBuf<char> trunc_ws;
     // mode
     int mode = XFR_MODE_AFFINEONLY_WITH_PRIOR;
     float eps = 1e-16f;
@@ -184,37 +232,39 @@ struct xfr_engine {
     std::vector<char> rc_prior_row, rc_cap_row;       // per firing: does the row hold any entry?
     int rc_dense_slot = -1;                           // firing that carries the dense prior (-1: none)
     const float* rc_prior_dense = nullptr;            // dense prior tensor (single sweep of one image)
-    int *tab_elem_h = nullptr, *tab_elem_d = nullptr; // prior element (or capture element) per (firing, row); -1: none
-    float *tab_val_h = nullptr, *tab_val_d = nullptr; // prior value per (firing, row)
+    // the subtree scratch, one all-or-nothing group with ev_tab (ensure_subtree_scratch); cap_dev stands for it
+    PinnedBuf<int> tab_elem_h;                        // prior element (or capture element) per (firing, row); -1: none
+    DevBuf<int> tab_elem_d;
+    PinnedBuf<float> tab_val_h;                       // prior value per (firing, row)
+    DevBuf<float> tab_val_d;
     size_t tab_cap = 0;                               // entries allocated
-    hipEvent_t ev_tab = nullptr;                      // the last host-to-device table copy
-    float* cap_dev = nullptr;                         // [n_firings][tab_sb] captured values
-    float* stat_v = nullptr;                          // [n_firings][max_batch]
-    int* stat_i = nullptr;
-    void* stat_scratch = nullptr;
-    StatDesc* stat_desc = nullptr;                    // [n_firings] tensor descriptors + firing -> tensor map of the last plan used
-    int* stat_f2u = nullptr;
+    DevBuf<float> cap_dev;                            // [n_firings][tab_sb] captured values
+    DevBuf<float> stat_v;                             // [n_firings][max_batch]
+    DevBuf<int> stat_i;
+    DevBuf<char> stat_scratch;
+    DevBuf<StatDesc> stat_desc;                       // [n_firings] tensor descriptors + firing -> tensor map of the last plan used
+    DevBuf<int> stat_f2u;
     const void* stat_plan = nullptr;
     int stat_nu = 0;
     int store_slot = -1;                              // firing whose full P tensor is kept in store_dev
-    float* store_dev = nullptr;
+    DevBuf<float> store_dev;
     int store_tensor = -1, store_sb = 0;
     // xfr_weighted_subtree_ebp: row-max keys of a round (device + pinned host), the round's gather pairs and the merge table (device + pinned
     // host), and the top-k store used when the caller passes no top_dev (grown on demand)
-    unsigned *wst_key_d = nullptr, *wst_key_h = nullptr;
-    int *wst_pairs_d = nullptr, *wst_pairs_h = nullptr;
-    SubtreeSlot *wst_tab_d = nullptr, *wst_tab_h = nullptr;
-    int *wst_cnt_d = nullptr, *wst_cnt_h = nullptr;
-    size_t wst_tab_cap = 0;
-    float* wst_store = nullptr;
-    size_t wst_store_floats = 0;
+    DevBuf<unsigned> wst_key_d;                       // the round buffers: one all-or-nothing group, wst_key_d stands for it
+    PinnedBuf<unsigned> wst_key_h;
+    DevBuf<int> wst_pairs_d, wst_cnt_d;
+    PinnedBuf<int> wst_pairs_h, wst_cnt_h;
+    DevBuf<SubtreeSlot> wst_tab_d;                    // the merge table: a pair of one capacity
+    PinnedBuf<SubtreeSlot> wst_tab_h;
+    DevBuf<float> wst_store;
     std::vector<char> is_hook_a;       // per tensor: some hook takes its a (and x) from this tensor's forward values
     std::vector<char> fwd_done;        // per forward pass: ops whose work was folded into an earlier GEMM epilogue
     std::vector<char> pos_done;        // ... and whose positive-pass output was produced there too
     int fwd_last_op = 0;
     // tail-balancing scratch (conv_gemm.hip), one per stream that launches GEMMs; kernels on one stream serialise,
     // so consecutive launches share it
-    struct TailWs { hipStream_t s; float* ws; unsigned* cnt; };
+    struct TailWs { hipStream_t s; DevBuf<float> ws; unsigned* cnt; };
     TailWs tail_ws[8];
     int n_tail_ws = 0;
     bool tail_balance = true;          // xfr_engine_set_tail_balance
@@ -255,7 +305,6 @@ struct xfr_engine {
     std::vector<int> last_trace_kinds;
     int profile_on = 0;
     std::string profile_csv;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     std::vector<ConvParams> ev_params;
     std::vector<int> ev_cfg;           // the configuration each profiled launch really ran
     double fam_ms[2] = {0.0, 0.0}, fam_flops[2] = {0.0, 0.0};      // last profiled run, by kernel family: [0] fp32 MFMA, [1] bf16x6
@@ -266,27 +315,21 @@ struct xfr_engine {
     long last_gemm_launches = 0;
     double last_gemm_flops = 0.0;
 
-    ProbeSweep* sweep = nullptr;            // xfr_strise_* and xfr_inpaint_*: side stream, events, input and embedding buffers, built on first use
-    struct StriseState* strise = nullptr;   // xfr_strise_*: the family's own buffers, built on first use (strise_abi.hip)
-    struct InpaintState* inpaint = nullptr; // xfr_inpaint_*: the same for inpainting-game scoring (inpaint_abi.hip)
-    struct MatchState* match = nullptr;     // xfr_embed_templates / xfr_pair_dists: the device copy of the caller's index table (match_abi.hip)
-    struct IntakeState* intake = nullptr;   // xfr_intake_u8[_host]: the items, weights, planes and staging buffers of the running call (intake_abi.hip)
-    struct FinishState* finish = nullptr;   // xfr_finish_saliency: the coefficient planes, the statistics, the colour table (finish_abi.hip)
+    std::unique_ptr<ProbeSweep> sweep;      // xfr_strise_* and xfr_inpaint_*: side stream, events, input and embedding buffers, built on first use
+    std::unique_ptr<StriseState> strise;    // the families' own buffers, each built on its first call
+    std::unique_ptr<InpaintState> inpaint;
+    std::unique_ptr<MatchState> match;
+    std::unique_ptr<IntakeState> intake;
+    std::unique_ptr<FinishState> finish;
 
     float* t_bank = nullptr;       // when set, true activations live in this bank (gallery forward of a triplet step)
-    float* ws_enc = nullptr;       // second bank of true activations (T region only), allocated on first use
+    DevBuf<float> ws_enc;          // second bank of true activations (T region only), allocated on first use
     size_t t_region_floats = 0;
-    hipStream_t s_a = nullptr, s_b = nullptr;
-    // xfr_triplet_contrastive_u8_host: the engine's own copy stream and one uint8 staging buffer per forward slot -- fresh inputs keep the cross-call overlap
-    hipStream_t s_copy = nullptr;
-    uint8_t* u8_stage[3] = {nullptr, nullptr, nullptr};
-    size_t u8_stage_bytes = 0;
-    hipEvent_t ev_copied[3] = {nullptr, nullptr, nullptr}, ev_stage_a[3] = {nullptr, nullptr, nullptr}, ev_stage_b[3] = {nullptr, nullptr, nullptr};
+    DevBuf<uint8_t> u8_stage[3];         // the staging buffers of xfr_triplet_contrastive_u8_host: with their nine events one all-or-nothing group
     bool stage_busy[3] = {false, false, false};
     hipEvent_t inputs_event = nullptr;   // one-shot, set by the _host entry point: the inputs of THIS call are complete when it fires (instead of the caller's stream order)
     int stage_slot = -1;                 // ... and the staging slot its forwards read
     hipEvent_t last_copied = nullptr;    // xfr_engine_wait_inputs_copied
-    hipEvent_t ev_fork = nullptr, ev_a = nullptr, ev_b = nullptr;
     // cross-step pipelining (xfr_engine_set_pipeline): two forward slots (T, Pv, norms, argmax) so that the forward of
     // triplet call i+1 may run while the backward sweep of call i still reads slot i%2
     bool pipeline = false;
@@ -296,8 +339,7 @@ struct xfr_engine {
     long seq = 0;
     int n_slots = 2;               // xfr_engine_set_pipeline bit 2: three forward slots (the forwards may run two calls ahead of the sweep)
     size_t fwd_region_floats = 0;
-    float* seedbuf[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_slot_done[3] = {nullptr, nullptr, nullptr};
+    DevBuf<float> seedbuf[3];
     bool slot_pending[3] = {false, false, false};
     float* fwd_base() { return fwd_ws[cur_slot]; }
     uint8_t* idx_base() { return fwd_idx[cur_slot]; }
@@ -347,6 +389,15 @@ xfr_status run_backward(xfr_engine* e, BwdPlan& plan, int B, int S, hipStream_t 
 xfr_status check_run(xfr_engine* e, const void* x, int n);
 xfr_status fence_slot0(xfr_engine* e, hipStream_t s);
 xfr_status ebp_core(xfr_engine* e, const float* x_dev, int n, int S, int seed_tensor, const float* seed_dev, hipStream_t s);
+xfr_status require_u8(xfr_engine* e);                                       // precondition of every uint8 entry point
+
+// weights.hip
+// row of (input channel ci, tap tp) in a forward pack: (kh,kw,4 channel slots) for image stems, tap-major (kh,kw,ci), or (ci,kh,kw)
+inline size_t forward_pack_row(bool tap4, bool tap, int ci, int tp, int cin, int khw)
+{
+    return tap4 ? (size_t)tp * 4 + ci : (tap ? (size_t)tp * cin + ci : (size_t)ci * khw + tp);
+}
+xfr_status pack_weights(const xfr_engine* e, const xfr_tensor_view* w, std::vector<float>& host);       // every pack of the arena, on the host
 void presplit_weights(xfr_engine* e);
 
 // probe_sweep.hip.  Every xfr_strise_* / xfr_inpaint_* entry point that touches device state runs between sweep_enter, after its argument checks,
@@ -366,33 +417,8 @@ using SweepGenerate = std::function<void(long, float*, hipStream_t)>;
 using SweepConsume = std::function<void(long, const float*, hipStream_t)>;
 xfr_status run_sweep(xfr_engine* e, ProbeSweep* sw, long n_images, int encode_tensor, hipStream_t s, const SweepGenerate& generate,
                      const SweepConsume& consume);
-void sweep_release(xfr_engine* e);
-
-// a device buffer of at least `need` elements; growing frees the old one behind a device synchronisation
-template <class T>
-xfr_status grow(T** p, size_t* cap, size_t need)
-{
-    if (*cap >= need) return XFR_OK;
-    if (*p) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    HIP_TRY(hipMalloc(p, need * sizeof(T)));
-    *cap = need;
-    return XFR_OK;
-}
 
 // strise_abi.hip
-void strise_release(xfr_engine* e);
 xfr_status check_taps(const xfr_strise_tap* tab, int entries, int n, const char* what, const char* who);
-
-// inpaint_abi.hip
-void inpaint_release(xfr_engine* e);
-
-// match_abi.hip
-void match_release(xfr_engine* e);
-
-// finish_abi.hip
-void finish_release(xfr_engine* e);
-
-// intake_abi.hip
-void intake_release(xfr_engine* e);
 
 }  // namespace xfr

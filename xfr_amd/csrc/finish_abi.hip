@@ -5,38 +5,6 @@
 #include <cstring>
 #include "engine_internal.h"
 
-struct FinishState {
-    double* planes = nullptr;                          // the padded coefficient planes of the running call's maps
-    size_t planes_cap = 0;
-    double* stats = nullptr;                           // FINISH_STATS doubles per map
-    size_t stats_cap = 0;
-    float* totals = nullptr;                           // the caller's totals
-    size_t totals_cap = 0;
-    double* lut = nullptr;                             // the colour table, uploaded when it differs from lut_host
-    size_t lut_cap = 0;
-    double lut_host[768];
-    bool lut_set = false;
-    hipEvent_t ev_done = nullptr;                      // the end of the previous call, on that call's stream: its kernels read all of the above
-    bool done_recorded = false;
-};
-
-namespace xfr {
-
-void finish_release(xfr_engine* e)
-{
-    FinishState* st = e->finish;
-    if (!st) return;
-    if (st->planes) (void)hipFree(st->planes);
-    if (st->stats) (void)hipFree(st->stats);
-    if (st->totals) (void)hipFree(st->totals);
-    if (st->lut) (void)hipFree(st->lut);
-    if (st->ev_done) (void)hipEventDestroy(st->ev_done);
-    delete st;
-    e->finish = nullptr;
-}
-
-}  // namespace xfr
-
 namespace {
 
 static_assert(FINISH_MAX_DIM == XFR_FINISH_MAX_DIM && FINISH_MAX_MAPS == XFR_FINISH_MAX_MAPS, "the header states the kernels' limits");
@@ -85,14 +53,14 @@ xfr_status xfr_finish_saliency(xfr_engine* e, const float* maps_dev, int32_t n, 
 
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    if (!e->finish) e->finish = new FinishState();
-    FinishState* st = e->finish;
-    if (!st->ev_done) HIP_TRY(hipEventCreateWithFlags(&st->ev_done, hipEventDisableTiming));
+    if (!e->finish) e->finish.reset(new FinishState());
+    FinishState* st = e->finish.get();
+    if (!st->ev_done) XFR_TRY(st->ev_done.create());
     if (st->done_recorded) HIP_TRY(hipStreamWaitEvent(s, st->ev_done, 0));
-    xfr_status rc = grow(&st->stats, &st->stats_cap, (size_t)n * FINISH_STATS);
-    if (rc == XFR_OK && !identity) rc = grow(&st->planes, &st->planes_cap, (size_t)n * finish_plane_doubles(h, w));
-    if (rc == XFR_OK && totals_host) rc = grow(&st->totals, &st->totals_cap, (size_t)n);
-    if (rc == XFR_OK && probes_u8_dev) rc = grow(&st->lut, &st->lut_cap, 768);
+    xfr_status rc = st->stats.grow((size_t)n * FINISH_STATS);
+    if (rc == XFR_OK && !identity) rc = st->planes.grow((size_t)n * finish_plane_doubles(h, w));
+    if (rc == XFR_OK && totals_host) rc = st->totals.grow((size_t)n);
+    if (rc == XFR_OK && probes_u8_dev) rc = st->lut.grow(768);
     if (rc != XFR_OK) return rc;
     bool uploaded = false;
     if (totals_host) {

@@ -43,12 +43,12 @@ xfr_status run_conv(xfr_engine* e, const ConvParams& p_in, hipStream_t s)
         int k = 0;
         while (k < e->n_tail_ws && e->tail_ws[k].s != s) ++k;
         if (k == e->n_tail_ws && k < 8) {
-            float* ws = nullptr;
-            HIP_TRY(hipMalloc(&ws, XFR_TAIL_WS_BYTES + XFR_TAIL_MAX_TILES * sizeof(unsigned)));
-            unsigned* cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + XFR_TAIL_WS_BYTES);
+            DevBuf<float> ws;      // the workspace, then the tiles' arrival counters
+            XFR_TRY(ws.alloc((XFR_TAIL_WS_BYTES + XFR_TAIL_MAX_TILES * sizeof(unsigned)) / sizeof(float)));
+            unsigned* cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws.p) + XFR_TAIL_WS_BYTES);
             HIP_TRY(hipMemset(cnt, 0, XFR_TAIL_MAX_TILES * sizeof(unsigned)));
             HIP_TRY(hipDeviceSynchronize());
-            e->tail_ws[k] = {s, ws, cnt};
+            e->tail_ws[k].s = s; e->tail_ws[k].ws = std::move(ws); e->tail_ws[k].cnt = cnt;
             e->n_tail_ws = k + 1;
         }
         if (k < e->n_tail_ws) {
@@ -59,10 +59,10 @@ xfr_status run_conv(xfr_engine* e, const ConvParams& p_in, hipStream_t s)
     }
     if (e->profile_on) {
         if (e->ev_used == e->ev_pool.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            e->ev_pool.emplace_back(a, b);
+            Event a, b;
+            XFR_TRY(a.create(true));
+            XFR_TRY(b.create(true));
+            e->ev_pool.emplace_back(std::move(a), std::move(b));
         }
         if (e->ev_params.size() < e->ev_pool.size()) { e->ev_params.resize(e->ev_pool.size()); e->ev_cfg.resize(e->ev_pool.size()); }
         const int why = conv_gemm_cannot_launch(p);

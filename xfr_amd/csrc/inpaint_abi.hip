@@ -5,27 +5,6 @@
 #include <vector>
 #include "engine_internal.h"
 
-struct InpaintState {
-    char* scratch = nullptr;                           // per map: the sort's keys, indices and running sums
-    size_t scratch_cap = 0;
-    uint8_t* first_on = nullptr;                       // n_maps x H x W
-    size_t first_on_cap = 0;
-};
-
-namespace xfr {
-
-void inpaint_release(xfr_engine* e)
-{
-    InpaintState* st = e->inpaint;
-    if (!st) return;
-    if (st->scratch) (void)hipFree(st->scratch);
-    if (st->first_on) (void)hipFree(st->first_on);
-    delete st;
-    e->inpaint = nullptr;
-}
-
-}  // namespace xfr
-
 namespace {
 
 struct MaskArgs {
@@ -172,12 +151,12 @@ struct Call : SweepCall {
         xfr_status rc = enter(e, (hipStream_t)stream);
         if (rc != XFR_OK) return rc;
         const long n = HW;
-        if (!e->inpaint) e->inpaint = new InpaintState();
-        InpaintState* st = e->inpaint;
-        rc = grow(&st->scratch, &st->scratch_cap, a.method == XFR_INPAINT_PERCENT_DENSITY ? (size_t)a.n_maps * inpaint_scratch_bytes(n) : (size_t)256);
+        if (!e->inpaint) e->inpaint.reset(new InpaintState());
+        InpaintState* st = e->inpaint.get();
+        rc = st->scratch.grow(a.method == XFR_INPAINT_PERCENT_DENSITY ? (size_t)a.n_maps * inpaint_scratch_bytes(n) : (size_t)256);
         if (rc != XFR_OK) return rc;
         if (!first_on) {
-            rc = grow(&st->first_on, &st->first_on_cap, (size_t)a.n_maps * n);
+            rc = st->first_on.grow((size_t)a.n_maps * n);
             if (rc != XFR_OK) return rc;
             first_on = st->first_on;
         }

@@ -5,57 +5,6 @@
 #include <cstring>
 #include "engine_internal.h"
 
-struct IntakeKernel { double sigma; int radius; double w[INTAKE_WEIGHTS]; };      // w[0 .. radius], w[radius] the centre
-
-struct IntakeState {
-    IntakeItem* items = nullptr;                       // the running call's crops
-    size_t items_cap = 0;
-    double* wts = nullptr;                             // [n][2][INTAKE_WEIGHTS]
-    size_t wts_cap = 0;
-    double* lohi = nullptr;                            // [n][2]
-    size_t lohi_cap = 0;
-    double* plane_a = nullptr;                         // the pre-filter's two planes of a chunk
-    double* plane_b = nullptr;
-    size_t plane_a_cap = 0, plane_b_cap = 0;
-    uint8_t* q = nullptr;                              // with tap tables: the zoom's bytes, then the horizontal pass's
-    uint8_t* mid = nullptr;
-    size_t q_cap = 0, mid_cap = 0;
-    StriseTap* taps = nullptr;                         // row table, then column table
-    size_t taps_cap = 0;
-    uint8_t* stage_dev = nullptr;                      // xfr_intake_u8_host: the sources on the device ...
-    size_t stage_dev_cap = 0;
-    uint8_t* stage_host = nullptr;                     // ... and in pinned host memory on their way there
-    size_t stage_host_cap = 0;
-    hipEvent_t ev_done = nullptr;                      // the end of the previous call, on that call's stream: its kernels read all of the above
-    hipEvent_t ev_copied = nullptr;                    // the end of the previous upload on the engine's copy stream
-    bool done_recorded = false, copied_recorded = false;
-    std::vector<IntakeKernel> stated;                  // the caller's own kernels (xfr_intake_set_kernels)
-};
-
-namespace xfr {
-
-void intake_release(xfr_engine* e)
-{
-    IntakeState* st = e->intake;
-    if (!st) return;
-    if (st->items) (void)hipFree(st->items);
-    if (st->wts) (void)hipFree(st->wts);
-    if (st->lohi) (void)hipFree(st->lohi);
-    if (st->plane_a) (void)hipFree(st->plane_a);
-    if (st->plane_b) (void)hipFree(st->plane_b);
-    if (st->q) (void)hipFree(st->q);
-    if (st->mid) (void)hipFree(st->mid);
-    if (st->taps) (void)hipFree(st->taps);
-    if (st->stage_dev) (void)hipFree(st->stage_dev);
-    if (st->stage_host) (void)hipHostFree(st->stage_host);
-    if (st->ev_done) (void)hipEventDestroy(st->ev_done);
-    if (st->ev_copied) (void)hipEventDestroy(st->ev_copied);
-    delete st;
-    e->intake = nullptr;
-}
-
-}  // namespace xfr
-
 namespace {
 
 static_assert(INTAKE_MAX_DIM == XFR_INTAKE_MAX_DIM && INTAKE_MAX_ITEMS == XFR_INTAKE_MAX_ITEMS && INTAKE_MAX_RADIUS == XFR_INTAKE_MAX_RADIUS,
@@ -176,8 +125,8 @@ xfr_status check_call(xfr_engine* e, const void* src, size_t src_bytes, const xf
 
 IntakeState* state_of(xfr_engine* e)
 {
-    if (!e->intake) e->intake = new IntakeState();
-    return e->intake;
+    if (!e->intake) e->intake.reset(new IntakeState());
+    return e->intake.get();
 }
 
 // the checked call on sources that are on the device
@@ -185,7 +134,7 @@ xfr_status run(xfr_engine* e, const uint8_t* src_dev, const xfr_intake_item* ite
                const xfr_strise_tap* col_tab, int fh, int fw, uint8_t* out_dev, hipStream_t s)
 {
     IntakeState* st = state_of(e);
-    if (!st->ev_done) HIP_TRY(hipEventCreateWithFlags(&st->ev_done, hipEventDisableTiming));
+    if (!st->ev_done) XFR_TRY(st->ev_done.create());
     if (st->done_recorded) HIP_TRY(hipStreamWaitEvent(s, st->ev_done, 0));
 
     // the crops as the kernels see them, their weights, and the chunks: consecutive crops whose planes fit PLANE_DOUBLES
@@ -221,14 +170,14 @@ xfr_status run(xfr_engine* e, const uint8_t* src_dev, const xfr_intake_item* ite
     }
     chunk_first.push_back(n);
 
-    xfr_status rc = grow(&st->items, &st->items_cap, (size_t)n);
-    if (rc == XFR_OK) rc = grow(&st->lohi, &st->lohi_cap, (size_t)n * 2);
-    if (rc == XFR_OK && any_filter) rc = grow(&st->wts, &st->wts_cap, wts.size());
-    if (rc == XFR_OK && need_a) rc = grow(&st->plane_a, &st->plane_a_cap, need_a);
-    if (rc == XFR_OK && need_b) rc = grow(&st->plane_b, &st->plane_b_cap, need_b);
-    if (rc == XFR_OK && row_tab) rc = grow(&st->q, &st->q_cap, (size_t)n * H * W * 3);
-    if (rc == XFR_OK && row_tab) rc = grow(&st->mid, &st->mid_cap, (size_t)n * H * fw * 3);
-    if (rc == XFR_OK && row_tab) rc = grow(&st->taps, &st->taps_cap, (size_t)fh + fw);
+    xfr_status rc = st->items.grow((size_t)n);
+    if (rc == XFR_OK) rc = st->lohi.grow((size_t)n * 2);
+    if (rc == XFR_OK && any_filter) rc = st->wts.grow(wts.size());
+    if (rc == XFR_OK && need_a) rc = st->plane_a.grow(need_a);
+    if (rc == XFR_OK && need_b) rc = st->plane_b.grow(need_b);
+    if (rc == XFR_OK && row_tab) rc = st->q.grow((size_t)n * H * W * 3);
+    if (rc == XFR_OK && row_tab) rc = st->mid.grow((size_t)n * H * fw * 3);
+    if (rc == XFR_OK && row_tab) rc = st->taps.grow((size_t)fh + fw);
     if (rc != XFR_OK) return rc;
     HIP_TRY(hipMemcpyAsync(st->items, dev.data(), sizeof(IntakeItem) * n, hipMemcpyHostToDevice, s));
     if (any_filter) HIP_TRY(hipMemcpyAsync(st->wts, wts.data(), sizeof(double) * wts.size(), hipMemcpyHostToDevice, s));
@@ -304,15 +253,11 @@ xfr_status xfr_intake_u8_host(xfr_engine* e, const uint8_t* src_host, size_t src
     HIP_TRY(hipSetDevice(e->device));
     IntakeState* st = state_of(e);
     hipStream_t s = (hipStream_t)stream;
-    if (!e->s_copy) HIP_TRY(hipStreamCreateWithFlags(&e->s_copy, hipStreamNonBlocking));
-    if (!st->ev_copied) HIP_TRY(hipEventCreateWithFlags(&st->ev_copied, hipEventDisableTiming));
+    if (!e->s_copy) XFR_TRY(e->s_copy.create());
+    if (!st->ev_copied) XFR_TRY(st->ev_copied.create());
     if (st->copied_recorded) HIP_TRY(hipEventSynchronize(st->ev_copied));      // the pinned buffer is free again
-    if (st->stage_host_cap < src_bytes) {
-        if (st->stage_host) { (void)hipHostFree(st->stage_host); st->stage_host = nullptr; st->stage_host_cap = 0; }
-        HIP_TRY(hipHostMalloc((void**)&st->stage_host, src_bytes, hipHostMallocDefault));
-        st->stage_host_cap = src_bytes;
-    }
-    rc = grow(&st->stage_dev, &st->stage_dev_cap, src_bytes);
+    if (st->stage_host.cap < src_bytes) XFR_TRY(st->stage_host.alloc(src_bytes));
+    rc = st->stage_dev.grow(src_bytes);
     if (rc != XFR_OK) return rc;
     std::memcpy(st->stage_host, src_host, src_bytes);
     if (st->done_recorded) HIP_TRY(hipStreamWaitEvent(e->s_copy, st->ev_done, 0));      // the previous call's kernels read the device copy

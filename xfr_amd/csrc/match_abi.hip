@@ -4,27 +4,6 @@
 #include <vector>
 #include "engine_internal.h"
 
-struct MatchState {
-    int* tab = nullptr;                                // the index table of the running call
-    size_t tab_cap = 0;
-    hipEvent_t ev_done = nullptr;                      // the end of the previous call, on that call's stream: its kernels read `tab`
-    bool done_recorded = false;
-};
-
-namespace xfr {
-
-void match_release(xfr_engine* e)
-{
-    MatchState* st = e->match;
-    if (!st) return;
-    if (st->tab) (void)hipFree(st->tab);
-    if (st->ev_done) (void)hipEventDestroy(st->ev_done);
-    delete st;
-    e->match = nullptr;
-}
-
-}  // namespace xfr
-
 namespace {
 
 static_assert(MATCH_MAX_K == XFR_MATCH_MAX_K && MATCH_MAX_D == XFR_MATCH_MAX_D, "the header states the kernels' limits");
@@ -46,11 +25,11 @@ xfr_status check_dim(const char* what, int D)
 xfr_status upload(xfr_engine* e, const std::vector<int>& tab, hipStream_t s, int** dev)
 {
     HIP_TRY(hipSetDevice(e->device));
-    if (!e->match) e->match = new MatchState();
-    MatchState* st = e->match;
-    if (!st->ev_done) HIP_TRY(hipEventCreateWithFlags(&st->ev_done, hipEventDisableTiming));
+    if (!e->match) e->match.reset(new MatchState());
+    MatchState* st = e->match.get();
+    if (!st->ev_done) XFR_TRY(st->ev_done.create());
     if (st->done_recorded) HIP_TRY(hipStreamWaitEvent(s, st->ev_done, 0));
-    const xfr_status rc = grow(&st->tab, &st->tab_cap, tab.size());
+    const xfr_status rc = st->tab.grow(tab.size());
     if (rc != XFR_OK) return rc;
     HIP_TRY(hipMemcpyAsync(st->tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));                  // the host vector goes away with the call

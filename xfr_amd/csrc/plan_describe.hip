@@ -15,7 +15,7 @@ xfr_status xfr_plan_describe(const xfr_op_desc* ops, int32_t n_ops, int32_t n_we
     if (ops[0].kind != XFR_OP_CONV || ops[0].in0 != 0)
         return fail(XFR_UNSUPPORTED_LAYER, "the first layer must be a convolution on the input image");
     xfr_engine* e = new xfr_engine();
-    struct Del { xfr_engine* e; ~Del() { delete e; } } del{e};
+    struct Del { xfr_engine* e; ~Del() { e->ws.p = nullptr; e->arena.p = nullptr; delete e; } } del{e};      // (the stand-in addresses below are nobody's to free)
     e->max_batch = batch; e->in_c = in_c; e->in_h = in_h; e->in_w = in_w; e->n_weights = n_weights;
     e->mode = subtree_mode;
     e->planning_only = true;
@@ -26,8 +26,8 @@ xfr_status xfr_plan_describe(const xfr_op_desc* ops, int32_t n_ops, int32_t n_we
     if (st == XFR_OK) st = layout_workspace(e);
     if (st != XFR_OK) return st;
     if (seed_tensor < 2 || seed_tensor >= (int)e->tens.size()) return fail(XFR_INVALID_ARG, "bad seed tensor %d", seed_tensor);
-    e->ws = reinterpret_cast<float*>((uintptr_t)1 << 40);
-    e->arena = reinterpret_cast<float*>((uintptr_t)2 << 40);
+    e->ws.p = reinterpret_cast<float*>((uintptr_t)1 << 40);
+    e->arena.p = reinterpret_cast<float*>((uintptr_t)2 << 40);
     compute_need(e);
     BwdPlan* plan = nullptr;
     st = get_plan(e, seed_tensor, &plan);

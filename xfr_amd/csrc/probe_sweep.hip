@@ -5,36 +5,23 @@
 
 namespace xfr {
 
-void sweep_release(xfr_engine* e)
-{
-    ProbeSweep* sw = e->sweep;
-    if (!sw) return;
-    for (int k = 0; k < 2; ++k) {
-        if (sw->xbuf[k]) (void)hipFree(sw->xbuf[k]);
-        if (sw->ev_ready[k]) (void)hipEventDestroy(sw->ev_ready[k]);
-        if (sw->ev_free[k]) (void)hipEventDestroy(sw->ev_free[k]);
-    }
-    if (sw->ev_in) (void)hipEventDestroy(sw->ev_in);
-    if (sw->ev_done) (void)hipEventDestroy(sw->ev_done);
-    if (sw->s_gen) (void)hipStreamDestroy(sw->s_gen);
-    if (sw->emb) (void)hipFree(sw->emb);
-    delete sw;
-    e->sweep = nullptr;
-}
-
 xfr_status sweep_enter(xfr_engine* e, hipStream_t s, ProbeSweep** out)
 {
     HIP_TRY(hipSetDevice(e->device));
-    if (!e->sweep) e->sweep = new ProbeSweep();
-    ProbeSweep* sw = e->sweep;
+    if (!e->sweep) e->sweep.reset(new ProbeSweep());
+    ProbeSweep* sw = e->sweep.get();
     if (!sw->s_gen) {
-        HIP_TRY(hipEventCreateWithFlags(&sw->ev_in, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&sw->ev_done, hipEventDisableTiming));
+        Event in, done, ready[2], free_[2];
+        Stream gen;
+        XFR_TRY(in.create());
+        XFR_TRY(done.create());
         for (int k = 0; k < 2; ++k) {
-            HIP_TRY(hipEventCreateWithFlags(&sw->ev_ready[k], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&sw->ev_free[k], hipEventDisableTiming));
+            XFR_TRY(ready[k].create());
+            XFR_TRY(free_[k].create());
         }
-        HIP_TRY(hipStreamCreateWithFlags(&sw->s_gen, hipStreamNonBlocking));      // last: its presence says that the events exist
+        XFR_TRY(gen.create());
+        sw->ev_in = std::move(in); sw->ev_done = std::move(done); sw->s_gen = std::move(gen);
+        for (int k = 0; k < 2; ++k) { sw->ev_ready[k] = std::move(ready[k]); sw->ev_free[k] = std::move(free_[k]); }
     }
     // the engine's buffers may still be read by the side stream, or by the previous call on another stream: this call starts behind both
     HIP_TRY(hipEventRecord(sw->ev_in, sw->s_gen));
@@ -61,8 +48,8 @@ xfr_status run_sweep(xfr_engine* e, ProbeSweep* sw, long n_images, int encode_te
 {
     const int B = e->max_batch;
     for (int k = 0; k < 2; ++k)
-        if (!sw->xbuf[k]) HIP_TRY(hipMalloc(&sw->xbuf[k], (size_t)B * e->in_c * e->in_h * e->in_w * sizeof(float)));
-    xfr_status rc = grow(&sw->emb, &sw->emb_floats, (size_t)B * e->tens[encode_tensor].per_n());
+        if (!sw->xbuf[k]) XFR_TRY(sw->xbuf[k].alloc((size_t)B * e->in_c * e->in_h * e->in_w));
+    xfr_status rc = sw->emb.grow((size_t)B * e->tens[encode_tensor].per_n());
     if (rc != XFR_OK) return rc;
     const long n_batches = (n_images + B - 1) / B;      // the last one is padded: generate fills it, consume drops what lies beyond n_images
     bool used[2] = {false, false};

@@ -2,28 +2,7 @@
 // the two ends of the batched sweep (probe_sweep.hip), the grouping of the masks by shift for the merge.  The kernels are strise.hip.
 #include "engine_internal.h"
 
-struct StriseState {
-    double* orig = nullptr;                            // n_refs + n_gal similarities of the unmasked probe, then as many 1 / |g|
-    size_t orig_cap = 0;
-    int* tab = nullptr;                                // cells, shifts, shift order and group offsets of the current call
-    size_t tab_cap = 0;
-    double* merge_ws = nullptr;                        // A [scale^2][gh * gw] and wsum [scale^2]
-    size_t merge_cap = 0;
-};
-
 namespace xfr {
-
-void strise_release(xfr_engine* e)
-{
-    StriseState* st = e->strise;
-    if (!st) return;
-    if (st->orig) (void)hipFree(st->orig);
-    if (st->tab) (void)hipFree(st->tab);
-    if (st->merge_ws) (void)hipFree(st->merge_ws);
-    delete st;
-    e->strise = nullptr;
-}
-
 
 // one tap table of Pillow's 8-bit resampling against the axis of n pixels it reads; `who` names the calling family in the text
 xfr_status check_taps(const xfr_strise_tap* tab, int entries, int n, const char* what, const char* who)
@@ -51,8 +30,8 @@ namespace {
 
 StriseState* strise_state(xfr_engine* e)
 {
-    if (!e->strise) e->strise = new StriseState();
-    return e->strise;
+    if (!e->strise) e->strise.reset(new StriseState());
+    return e->strise.get();
 }
 
 // the options of the _ex calls as the entry points use them; opt == NULL: the engine's input size, no quantisation
@@ -148,7 +127,7 @@ xfr_status check_u8(xfr_engine* e, StriseOpt* o)
 // a host table into the state's `tab` on `s`; the host waits for the copy there: the table is pageable and local to the call
 xfr_status upload_table(StriseState* st, const std::vector<int>& tab, hipStream_t s)
 {
-    xfr_status rc = grow(&st->tab, &st->tab_cap, tab.size());
+    xfr_status rc = st->tab.grow(tab.size());
     if (rc != XFR_OK) return rc;
     HIP_TRY(hipMemcpyAsync(st->tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -266,7 +245,7 @@ xfr_status xfr_strise_score_ex(xfr_engine* e, const uint8_t* probe_u8_dev, const
     const StriseOpt& o = c.o;
     const int B = e->max_batch, D = (int)e->tens[encode_tensor].per_n();
     const int nrg = n_refs + n_gal;
-    rc = grow(&st->orig, &st->orig_cap, (size_t)2 * nrg);
+    rc = st->orig.grow((size_t)2 * nrg);
     if (rc != XFR_OK) return rc;
     const long total = (long)n_masks + 1;
     const long rows = (total + B - 1) / B * B;
@@ -334,7 +313,7 @@ xfr_status xfr_strise_combine_ex(xfr_engine* e, const double* weights_dev, int32
     rc = c.begin(e, stream);      // the table may still be read by the side stream of an earlier xfr_strise_score: this call starts behind it
     if (rc != XFR_OK) return rc;
     StriseState* st = c.st;
-    rc = grow(&st->merge_ws, &st->merge_cap, (size_t)ng * nc + ng);
+    rc = st->merge_ws.grow((size_t)ng * nc + ng);
     if (rc == XFR_OK) rc = upload_table(st, tab, c.s);
     if (rc != XFR_OK) return rc;
     const int* order_d = st->tab + (size_t)n_masks * g.n_elem;

@@ -7,20 +7,31 @@ extern "C" {
 static xfr_status ensure_subtree_scratch(xfr_engine* e)
 {
     if (e->cap_dev) return XFR_OK;
-    const size_t nf = e->trace_cap + 1;
-    e->tab_cap = nf * 2 * (size_t)e->max_batch;
-    HIP_TRY(hipMalloc(&e->cap_dev, e->tab_cap * sizeof(float)));
-    HIP_TRY(hipMalloc(&e->tab_elem_d, e->tab_cap * sizeof(int)));
-    HIP_TRY(hipMalloc(&e->tab_val_d, e->tab_cap * sizeof(float)));
-    HIP_TRY(hipHostMalloc(&e->tab_elem_h, e->tab_cap * sizeof(int)));
-    HIP_TRY(hipHostMalloc(&e->tab_val_h, e->tab_cap * sizeof(float)));
-    HIP_TRY(hipEventCreateWithFlags(&e->ev_tab, hipEventDisableTiming));
-    HIP_TRY(hipMalloc(&e->stat_v, nf * e->max_batch * sizeof(float)));
-    HIP_TRY(hipMalloc(&e->stat_i, nf * e->max_batch * sizeof(int)));
-    HIP_TRY(hipMalloc(&e->stat_scratch, subtree_stats_scratch_bytes(e->max_batch, (int)nf)));
-    HIP_TRY(hipMalloc(&e->stat_desc, nf * sizeof(StatDesc)));
-    HIP_TRY(hipMalloc(&e->stat_f2u, nf * sizeof(int)));
-    HIP_TRY(hipMalloc(&e->store_dev, 2 * (size_t)e->max_batch * e->max_per_n() * sizeof(float)));
+    const size_t nf = e->trace_cap + 1, cap = nf * 2 * (size_t)e->max_batch;
+    DevBuf<float> cap_dev, tab_val_d, stat_v, store_dev;
+    DevBuf<int> tab_elem_d, stat_i, stat_f2u;
+    PinnedBuf<int> tab_elem_h;
+    PinnedBuf<float> tab_val_h;
+    Event ev_tab;
+    DevBuf<char> stat_scratch;
+    DevBuf<StatDesc> stat_desc;
+    XFR_TRY(cap_dev.alloc(cap));
+    XFR_TRY(tab_elem_d.alloc(cap));
+    XFR_TRY(tab_val_d.alloc(cap));
+    XFR_TRY(tab_elem_h.alloc(cap));
+    XFR_TRY(tab_val_h.alloc(cap));
+    XFR_TRY(ev_tab.create());
+    XFR_TRY(stat_v.alloc(nf * e->max_batch));
+    XFR_TRY(stat_i.alloc(nf * e->max_batch));
+    XFR_TRY(stat_scratch.alloc(subtree_stats_scratch_bytes(e->max_batch, (int)nf)));
+    XFR_TRY(stat_desc.alloc(nf));
+    XFR_TRY(stat_f2u.alloc(nf));
+    XFR_TRY(store_dev.alloc(2 * (size_t)e->max_batch * e->max_per_n()));
+    e->tab_cap = cap;
+    e->cap_dev = std::move(cap_dev); e->tab_elem_d = std::move(tab_elem_d); e->tab_val_d = std::move(tab_val_d);
+    e->tab_elem_h = std::move(tab_elem_h); e->tab_val_h = std::move(tab_val_h); e->ev_tab = std::move(ev_tab);
+    e->stat_v = std::move(stat_v); e->stat_i = std::move(stat_i); e->stat_scratch = std::move(stat_scratch);
+    e->stat_desc = std::move(stat_desc); e->stat_f2u = std::move(stat_f2u); e->store_dev = std::move(store_dev);
     return XFR_OK;
 }
 
@@ -233,29 +244,31 @@ static xfr_status ensure_weighted_scratch(xfr_engine* e, int n, int topk, bool n
 {
     const size_t rows = 2 * (size_t)e->max_batch;
     if (!e->wst_key_d) {
-        HIP_TRY(hipMalloc(&e->wst_key_d, rows * sizeof(unsigned)));
-        HIP_TRY(hipHostMalloc(&e->wst_key_h, rows * sizeof(unsigned)));
-        HIP_TRY(hipMalloc(&e->wst_pairs_d, 2 * rows * sizeof(int)));
-        HIP_TRY(hipHostMalloc(&e->wst_pairs_h, 2 * rows * sizeof(int)));
-        HIP_TRY(hipMalloc(&e->wst_cnt_d, (size_t)e->max_batch * sizeof(int)));
-        HIP_TRY(hipHostMalloc(&e->wst_cnt_h, (size_t)e->max_batch * sizeof(int)));
+        DevBuf<unsigned> key_d;
+        PinnedBuf<unsigned> key_h;
+        DevBuf<int> pairs_d, cnt_d;
+        PinnedBuf<int> pairs_h, cnt_h;
+        XFR_TRY(key_d.alloc(rows));
+        XFR_TRY(key_h.alloc(rows));
+        XFR_TRY(pairs_d.alloc(2 * rows));
+        XFR_TRY(pairs_h.alloc(2 * rows));
+        XFR_TRY(cnt_d.alloc((size_t)e->max_batch));
+        XFR_TRY(cnt_h.alloc((size_t)e->max_batch));
+        e->wst_key_d = std::move(key_d); e->wst_key_h = std::move(key_h); e->wst_pairs_d = std::move(pairs_d);
+        e->wst_pairs_h = std::move(pairs_h); e->wst_cnt_d = std::move(cnt_d); e->wst_cnt_h = std::move(cnt_h);
     }
     const size_t slots = (size_t)n * topk;
-    if (slots > e->wst_tab_cap) {
-        if (e->wst_tab_d) { (void)hipFree(e->wst_tab_d); e->wst_tab_d = nullptr; }
-        if (e->wst_tab_h) { (void)hipHostFree(e->wst_tab_h); e->wst_tab_h = nullptr; }
-        e->wst_tab_cap = 0;
-        HIP_TRY(hipMalloc(&e->wst_tab_d, slots * sizeof(SubtreeSlot)));
-        HIP_TRY(hipHostMalloc(&e->wst_tab_h, slots * sizeof(SubtreeSlot)));
-        e->wst_tab_cap = slots;
+    if (slots > e->wst_tab_d.cap) {
+        e->wst_tab_d.reset();
+        e->wst_tab_h.reset();
+        DevBuf<SubtreeSlot> tab_d;
+        PinnedBuf<SubtreeSlot> tab_h;
+        XFR_TRY(tab_d.alloc(slots));
+        XFR_TRY(tab_h.alloc(slots));
+        e->wst_tab_d = std::move(tab_d); e->wst_tab_h = std::move(tab_h);
     }
     const size_t floats = slots * (size_t)e->tens[1].HW();
-    if (need_store && floats > e->wst_store_floats) {
-        if (e->wst_store) { (void)hipFree(e->wst_store); e->wst_store = nullptr; }
-        e->wst_store_floats = 0;
-        HIP_TRY(hipMalloc(&e->wst_store, floats * sizeof(float)));
-        e->wst_store_floats = floats;
-    }
+    if (need_store && floats > e->wst_store.cap) XFR_TRY(e->wst_store.alloc(floats));
     return XFR_OK;
 }
 
