@@ -268,7 +268,8 @@ xfr_status xfr_engine_set_inputs_ready(xfr_engine* e, int32_t ready);
  * Forward: the reference evaluates a down-sampling block's shortcut behind the main path (resnet.py:144-146); the engine computes it in front of
  * the main path's last convolution, so that the residual add [+ ReLU] joins that convolution's epilogue like in every other block, and keeps the
  * pooled shortcut inside its zero-padded form (a channel prefix is a storage prefix in CNHW: the padding is one fill, no copy).  The order of two
- * independent branches changes no value; bit 8 (tests, A/B) keeps program order and the separate add. */
+ * independent branches changes no value; bit 8 (tests, A/B) keeps program order and the separate add.
+ * Bit 9 (tests, A/B): the phase launches of a strided KxK layer's backward-data pass run one after another instead of side by side (same bits). */
 xfr_status xfr_engine_set_epilogue_fusion(xfr_engine* e, int32_t enable);
 
 /* Share one forward pass between consecutive calls on the same input (off by default).  While hold = 1, a run call

@@ -72,16 +72,18 @@ void resolve_chain(xfr_engine* e, const std::vector<BwdStep::Sym>& syms, EwChain
     }
 }
 
-// launch parameters of a backward-data GEMM step (with its fused chain resolved against the workspace)
-static void bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& st, int B, int SB, int SBa, ConvParams& p)
+// launch parameters of a backward-data GEMM step (with its fused chain resolved against the workspace); ph: the phase of a strided KxK layer.
+// false: a layer that runs by phases was asked for without one, or a phase came with another layer -- p is not a launch
+bool bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& st, int B, int SB, int SBa, ConvParams& p, const PhaseRec* ph)
 {
     const OpRec& o = e->ops[st.op];
     const xfr_op_desc& d = o.d;
     const Tensor& a = e->tens[d.in0];
     const Tensor& t = e->tens[d.out];
     memset(&p, 0, sizeof(p));
+    if ((ph != nullptr) != !o.phases.empty() || (st.compact && ph)) return false;
     p.in = e->G(st.src_t);
-    p.w = e->arena + (plan.plain ? o.w_bwd_true : o.w_bwd);
+    if (!ph) p.w = e->arena + (plan.plain ? o.w_bwd_true : o.w_bwd);
     p.out0 = e->G(st.dst_t);
     p.Cin = t.C; p.H = t.H; p.W = t.W; p.NB = SBa; p.in_nb = SB; p.out_nb = SB;
     p.tap_major = (d.stride == 1 && o.tap_bwd) ? 1 : 0;
@@ -101,6 +103,17 @@ static void bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& s
         p.kh = d.kh; p.kw = d.kw; p.stride = 1; p.pad = d.kh - 1 - d.pad; p.pad_dw = d.kw - d.kh;
         p.OH = a.H; p.OW = a.W;
         p.out_H = a.H; p.out_W = a.W; p.out_stride = 1;
+    } else if (ph) {
+        // one phase of a strided KxK layer: a stride-1 convolution of dY with the phase's flipped sub-kernel, its nq x nu results scattered
+        // with the layer's stride from the phase's first pixel on
+        p.w = e->arena + (plan.plain ? ph->w_bwd_true : ph->w_bwd);
+        p.K = ph->K;
+        p.tap_major = ph->tap ? 1 : 0;
+        p.kh = ph->ka; p.kw = ph->kb; p.stride = 1; p.pad = ph->ka - 1 - ph->q0; p.pad_dw = (ph->kb - 1 - ph->u0) - p.pad;
+        p.OH = ph->nq; p.OW = ph->nu;
+        p.out0 = e->G(st.dst_t) + (size_t)ph->ih0 * a.W + ph->iw0;
+        p.out_H = a.H; p.out_W = a.W; p.out_stride = d.stride;
+        p.accumulate = 1;   // the target was zero-filled or already holds other contributions
     } else {
         // 1x1 stride-s: the gradient lands on the sampled grid only
         p.kh = 1; p.kw = 1; p.stride = 1; p.pad = 0;
@@ -118,6 +131,7 @@ static void bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& s
     }
     p.chain_interpret = e->interpret_chains ? 1 : 0;
     p.bwd = 1;
+    return true;
 }
 
 // The fan-out schedule (plan.fused_gemm: MaxFeatureMap VJPs inside GEMM epilogues) only runs where every such epilogue is COMPILED --
@@ -134,7 +148,7 @@ static bool fanout_compiled(xfr_engine* e, BwdPlan& plan, int B, int SB)
         for (const auto& sy : st.chain) if (sy.type == EW_MAXHALF_OUT) fan = true;
         if (!fan) continue;
         ConvParams p;
-        bwd_conv_params(e, plan, st, B, SB, SB, p);
+        if (!bwd_conv_params(e, plan, st, B, SB, SB, p)) { plan.fan_ok = 0; break; }      // (a layer that runs by phases carries no chain)
         p.chain_interpret = 0;
         if (conv_gemm_cannot_launch(p)) { plan.fan_ok = 0; break; }
     }
@@ -219,8 +233,35 @@ xfr_status run_backward(xfr_engine* e, BwdPlan& plan, int B, int S, hipStream_t 
                 break;
             case ST_CONV_BWD: {
                 ConvParams p;
-                bwd_conv_params(e, plan, st, B, SB, SBa, p);
-                xfr_status rs = run_conv(e, p, s);
+                const std::vector<PhaseRec>& phases = e->ops[st.op].phases;
+                if (!phases.empty() && !st.chain.empty()) return fail(XFR_STATE_ERROR, "a scattering backward-data GEMM cannot carry a fused chain");
+                // A strided KxK layer: one launch per phase, each onto its own pixels of the (zero-filled) target.  The phases write disjoint pixels and
+                // read the same gradient, so they run side by side: phase q on the sweep's stream (q % 4 == 0) or on a side stream, forked behind what
+                // the sweep has enqueued and joined before its next step.  Same launches, same bits.  A profiled run times launches one by one: in a row.
+                PhaseStreams* side = nullptr;
+                if (phases.size() > 1 && e->overlap_phases && !e->profile_on) {
+                    if (!e->ph_streams) {
+                        std::unique_ptr<PhaseStreams> g(new PhaseStreams());
+                        XFR_TRY(g->fork.create());
+                        for (int i = 0; i < 3; ++i) { XFR_TRY(g->s[i].create()); XFR_TRY(g->done[i].create()); }
+                        e->ph_streams = std::move(g);
+                    }
+                    side = e->ph_streams.get();
+                    HIP_TRY(hipEventRecord(side->fork, s));
+                    for (int i = 0; i < 3 && i + 1 < (int)phases.size(); ++i) HIP_TRY(hipStreamWaitEvent(side->s[i], side->fork, 0));
+                }
+                xfr_status rs = XFR_OK;
+                for (size_t q = 0; q < std::max<size_t>(phases.size(), 1) && rs == XFR_OK; ++q) {
+                    if (!bwd_conv_params(e, plan, st, B, SB, SBa, p, phases.empty() ? nullptr : &phases[q]))
+                        rs = fail(XFR_STATE_ERROR, "backward-data GEMM of op %d: phase and layer do not match", st.op);
+                    else
+                        rs = run_conv(e, p, (side && (q & 3)) ? (hipStream_t)side->s[(q & 3) - 1] : s);
+                }
+                if (side)      // the join, on every way out: the sweep goes on behind whatever the side streams hold
+                    for (int i = 0; i < 3 && i + 1 < (int)phases.size(); ++i) {
+                        HIP_TRY(hipEventRecord(side->done[i], side->s[i]));
+                        HIP_TRY(hipStreamWaitEvent(s, side->done[i], 0));
+                    }
                 if (rs != XFR_OK) return rs;
                 break;
             }

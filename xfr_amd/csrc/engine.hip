@@ -633,6 +633,7 @@ xfr_status xfr_engine_set_epilogue_fusion(xfr_engine* e, int32_t enable)
     e->pair_tiles = (enable & 32) == 0;           // bit 5 (A/B measurements): tile order of the two-stream backward GEMMs as before round 4
     e->hoist_shortcut = (enable & 256) == 0;      // bit 8 (tests, A/B): the down-sampling blocks' shortcut in program order, their residual add as its own launch
     e->direct_stem = (enable & 16) == 0;          // bit 4 (tests): the first layer of Light-CNN through the GEMM like every other convolution
+    e->overlap_phases = (enable & 512) == 0;      // bit 9 (tests, A/B): the phase launches of a strided KxK layer's backward-data pass one after another on the sweep's stream
     e->held_x = nullptr;
     for (auto& p : e->plans) p.lean_state = -1;   // the lean tables follow the probe forward's fusion decisions
     return XFR_OK;

@@ -59,8 +59,23 @@ struct Tensor {
     int HW() const { return H * W; }
 };
 
+// One phase of the backward-data pass of a strided KxK convolution (stride s, padding p): the input pixels with ((ih + p) % s, (iw + p) % s) == (r, c)
+// see only the taps a = r, r + s, ... < kh and b = c, c + s, ... < kw, and their gradient is an ordinary stride-1 convolution of dY with the flipped
+// ka x kb sub-kernel (top / left padding ka - 1 - q0 / kb - 1 - u0), whose nq x nu results land at dX[ih0 + s i][iw0 + s j].
+struct PhaseRec {
+    int r = 0, c = 0;
+    int ka = 0, kb = 0;        // taps of the phase per axis: ceil((kh - r) / s), ceil((kw - c) / s)
+    int q0 = 0, u0 = 0;        // first output row / column of the forward whose window holds a pixel of the phase: max(0, ceil((p - r) / s))
+    int ih0 = 0, iw0 = 0;      // the phase's first input pixel: s q0 + r - p
+    int nq = 0, nu = 0;        // the phase's pixels per axis: (H - 1 - ih0) / s + 1
+    int K = 0;                 // cout * ka * kb
+    bool tap = false;          // K packed tap-major (tap, co)
+    long w_bwd = -1, w_bwd_true = -1;      // the phase's relu(W) and true packs in the arena
+};
+
 struct OpRec {
     xfr_op_desc d;
+    std::vector<PhaseRec> phases;            // a strided KxK convolution behind the first layer: the launches of its backward-data pass (layout_arena)
     // packed parameter offsets (floats) into the arena; -1 if absent
     long w_true = -1, w_pos = -1, w_bwd = -1, w_bwd_true = -1;   // w_bwd_true: true-weight backward pack (plain gradients)
     long b_true = -1, b_pos = -1;            // conv/linear bias and relu(bias)
@@ -176,6 +191,12 @@ struct IntakeState {                                   // xfr_intake_u8[_host] (
     std::vector<IntakeKernel> stated;                  // the caller's own kernels (xfr_intake_set_kernels)
 };
 
+// the side streams on which the phases of one strided KxK layer's backward-data pass run next to the sweep's own stream: one all-or-nothing group
+struct PhaseStreams {
+    Stream s[3];
+    Event fork, done[3];
+};
+
 struct xfr_engine {
     int device = 0;
     int max_batch = 0;
@@ -191,6 +212,8 @@ struct xfr_engine {
     Event ev_copied[3], ev_stage_a[3], ev_stage_b[3];
     Event ev_slot_done[3];             // cross-step pipelining, with seedbuf[] below
     Event ev_tab;                      // the last host-to-device table copy (subtree scratch)
+    std::unique_ptr<PhaseStreams> ph_streams;      // built at the first sweep through a strided KxK layer (backward.hip)
+    bool overlap_phases = true;        // the phases of one layer run side by side (they write disjoint pixels); profiled runs keep them in a row
     std::vector<std::pair<Event, Event>> ev_pool;      // profiling: one pair per GEMM launch of a run
     // parameters
     DevBuf<float> arena;
@@ -384,6 +407,7 @@ bool lean_applies(xfr_engine* e, BwdPlan& plan, int B);
 // backward.hip
 void resolve_chain(xfr_engine* e, const std::vector<BwdStep::Sym>& syms, EwChain& ch, double* trace, int SB, bool plain = false);
 xfr_status run_backward(xfr_engine* e, BwdPlan& plan, int B, int S, hipStream_t s);
+bool bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& st, int B, int SB, int SBa, ConvParams& p, const PhaseRec* ph = nullptr);
 
 // engine.hip
 xfr_status check_run(xfr_engine* e, const void* x, int n);

@@ -73,9 +73,26 @@ xfr_status build(xfr_engine* e, const xfr_op_desc* ops, int n_ops)
                 t.H = (a.H + 2 * d.pad - d.kh) / d.stride + 1;
                 t.W = (a.W + 2 * d.pad - d.kw) / d.stride + 1;
                 if (t.H <= 0 || t.W <= 0) return fail(XFR_INVALID_ARG, "op %d: empty conv output", k);
-                if (d.stride > 1 && !(d.kh == 1 && d.kw == 1) && k != 0)
-                    return fail(XFR_UNSUPPORTED_LAYER, "op %d: strided %dx%d convolution is only supported as the first layer "
-                                "(its backward-data pass is not needed for P[-2])", k, d.kh, d.kw);
+                if (d.stride > 1 && !(d.kh == 1 && d.kw == 1) && k != 0) {
+                    // backward-data by phases (PhaseRec): padding <= kernel - stride keeps every phase's leading padding non-negative
+                    if (d.pad > d.kh - d.stride || d.pad > d.kw - d.stride)
+                        return fail(XFR_UNSUPPORTED_LAYER, "op %d: a strided %dx%d convolution behind the first layer needs pad <= kernel - stride on "
+                                    "each axis (stride %d, pad %d): its backward-data pass runs by phases", k, d.kh, d.kw, d.stride, d.pad);
+                    const int s = d.stride, p = d.pad;
+                    for (int r = 0; r < s && r < d.kh; ++r)
+                        for (int c = 0; c < s && c < d.kw; ++c) {
+                            PhaseRec ph;
+                            ph.r = r; ph.c = c;
+                            ph.ka = (d.kh - r + s - 1) / s; ph.kb = (d.kw - c + s - 1) / s;
+                            ph.q0 = p > r ? (p - r + s - 1) / s : 0; ph.u0 = p > c ? (p - c + s - 1) / s : 0;
+                            ph.ih0 = s * ph.q0 + r - p; ph.iw0 = s * ph.u0 + c - p;
+                            if (ph.ih0 >= a.H || ph.iw0 >= a.W) continue;      // the phase's origin lies outside the map
+                            ph.nq = (a.H - 1 - ph.ih0) / s + 1; ph.nu = (a.W - 1 - ph.iw0) / s + 1;
+                            ph.K = d.cout * ph.ka * ph.kb;
+                            ph.tap = (d.cout % 16 == 0) && (ph.ka * ph.kb <= 64);
+                            o.phases.push_back(ph);
+                        }
+                }
                 o.Cin = a.C; o.K = a.C * d.kh * d.kw; o.Kb = d.cout * d.kh * d.kw;
                 t.nonneg = false; t.pstate = PS_OTHER;
                 break;
@@ -292,8 +309,14 @@ xfr_status layout_arena(xfr_engine* e)
             o.w_pos = take(align_up(o.Kf, 32) * o.ldw);
             if (k != 0) {
                 o.ldb = (int)align_up(o.Cin, 128);
-                o.w_bwd = take(align_up(o.Kb, 32) * o.ldb);
-                o.w_bwd_true = take(align_up(o.Kb, 32) * o.ldb);
+                if (o.phases.empty()) {
+                    o.w_bwd = take(align_up(o.Kb, 32) * o.ldb);
+                    o.w_bwd_true = take(align_up(o.Kb, 32) * o.ldb);
+                }
+                for (PhaseRec& ph : o.phases) {      // a strided KxK layer: one flipped sub-kernel pack per phase instead of the whole kernel's
+                    ph.w_bwd = take(align_up(ph.K, 32) * o.ldb);
+                    ph.w_bwd_true = take(align_up(ph.K, 32) * o.ldb);
+                }
             }
             if (d.w_bias >= 0) { o.b_true = take(d.cout); o.b_pos = take(d.cout); }
         } else if (d.kind == XFR_OP_BATCHNORM) {

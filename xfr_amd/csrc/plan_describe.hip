@@ -119,6 +119,15 @@ xfr_status xfr_plan_describe(const xfr_op_desc* ops, int32_t n_ops, int32_t n_we
                 }
             }
             out += "\n";
+            // a strided KxK layer: the launches of its phases (two gradient streams of `batch` images), each with the kernel the rules give it
+            if (style == SCHED_FULL && b.kind == ST_CONV_BWD)
+                for (const PhaseRec& ph : e->ops[b.op].phases) {
+                    ConvParams p;
+                    if (!bwd_conv_params(e, *plan, b, batch, 2 * batch, 2 * batch, p, &ph)) continue;
+                    snprintf(line, sizeof(line), "%s PHASE op %d (%d,%d) kernel %dx%d cfg %d K %d M %d origin (%d,%d) grid %d x %d\n", prefix, b.op, ph.r, ph.c,
+                             ph.ka, ph.kb, conv_gemm_pick_cfg(p), p.K, p.M, ph.ih0, ph.iw0, ph.nq, ph.nu);
+                    out += line;
+                }
         }
     };
     // forward-only runs (encode / the gallery of a triplet step): Conv -> BatchNorm [-> Add] [-> ReLU] epilogues

@@ -49,6 +49,22 @@ xfr_status pack_weights(const xfr_engine* e, const xfr_tensor_view* w, std::vect
                                 wbt[kk * o.ldb + ci] = v;
                             }
             }
+            // backward-data packs of a strided KxK layer, one per phase: the taps (r + s i, c + s j) of the kernel as a ka x kb kernel, flipped
+            for (const PhaseRec& ph : o.phases) {
+                float* wb = host.data() + ph.w_bwd;
+                float* wbt = host.data() + ph.w_bwd_true;
+                for (int co = 0; co < d.cout; ++co)
+                    for (int ci = 0; ci < o.Cin; ++ci)
+                        for (int i = 0; i < ph.ka; ++i)
+                            for (int j = 0; j < ph.kb; ++j) {
+                                const int a = ph.r + d.stride * i, b = ph.c + d.stride * j;
+                                const float v = wv.data[(((size_t)co * o.Cin + ci) * d.kh + a) * d.kw + b];
+                                const int i2 = ph.ka - 1 - i, j2 = ph.kb - 1 - j;
+                                const size_t kk = ph.tap ? (size_t)(i2 * ph.kb + j2) * d.cout + co : (size_t)(co * ph.ka + i2) * ph.kb + j2;
+                                wb[kk * o.ldb + ci] = v > 0.f ? v : 0.f;
+                                wbt[kk * o.ldb + ci] = v;
+                            }
+            }
             if (d.w_bias >= 0) {
                 const xfr_tensor_view& bv = w[d.w_bias];
                 if (!bv.data || bv.numel != d.cout) return fail(XFR_INVALID_ARG, "op %zu: bad bias size", k);

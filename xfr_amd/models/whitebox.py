@@ -24,6 +24,9 @@ from .lightcnn import lightcnn_preprocess
 from .resnet import MEAN_RGB, convert_resnet101v4_image
 
 
+_TRACE_ALIAS = {'AdaptiveAvgPool2d': 'AvgPool2d'}      # str(module) class name -> the op kind's name (program.LAYER_NAMES), where they differ
+
+
 def _is_dataframe(obj):
     """pandas.DataFrame without importing pandas unless the caller already did (whitebox.py:752)."""
     import sys
@@ -232,6 +235,26 @@ class Whitebox_resnet50_128(WhiteboxNetwork):
         return ('sub_mean', 3, (131.0912, 103.8827, 91.4953), None)                    # whitebox.py:238,256
 
 
+class WhiteboxTVResnet(WhiteboxNetwork):
+    """A torchvision ResNet (models/tv_resnet.py) the way the reference's README has users bring their own network: the hooked classifier is the
+    net's `fc`, set_triplet_classifier installs the un-hooked 2-row classifier on the pooled features, encode returns those features."""
+
+    def set_triplet_classifier(self, x_mate, x_nonmate):
+        w = _triplet_rows(x_mate, x_nonmate)
+        self._classifier = _TripletClassifier(w)
+        self.net.fc2 = self._classifier
+
+    def num_classes(self):
+        return self._classifier.out_features if self._classifier is not None else self.net.num_classes
+
+    def preprocess(self, im):
+        """torchvision's ImageNet recipe at the net's input size: RGB in [0, 1], minus the mean, over the standard deviation."""
+        c, h, w = self.net.in_shape
+        x = np.asarray(im.convert('RGB').resize((w, h), resample=PIL.Image.BILINEAR), dtype=np.float32) / 255.0
+        x = (x - np.asarray(self.net.meta['mean'], dtype=np.float32)) / np.asarray(self.net.meta['std'], dtype=np.float32)
+        return torch.from_numpy(np.ascontiguousarray(x.transpose(2, 0, 1))).unsqueeze(0)
+
+
 class _PList(object):
     """`Whitebox.P` (whitebox.py:294,394): the MWP tensors of the last sweep in firing order.  The reference clones every one
     of them on every sweep; the engine hands back the channel-pooled P[-2] its callers read (whitebox.py:499,524) and recomputes
@@ -362,7 +385,8 @@ class Whitebox(object):
         self.P_layername = self._layernames(seed_tensor)
         if self.debug_trace:
             sums, names, nf = eng.get_trace()
-            assert names == [s.split('(')[0] for s in self.P_layername[:nf]]
+            # the engine names a firing by its op kind; AdaptiveAvgPool2d (models/tv_resnet.py) is an average-pool op under torch's own name
+            assert names == [_TRACE_ALIAS.get(c, c) for c in (s.split('(')[0] for s in self.P_layername[:nf])]
             self.P_trace = sums[:nf * n].reshape(nf, n).copy()
             eng.set_trace(False)
         self.P = _PList(self, x, seed_tensor, seed.unsqueeze(0), len(self.P_layername) - 1)
