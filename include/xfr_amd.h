@@ -76,7 +76,8 @@ typedef struct {
     int32_t kh, kw;      /* CONV/MAXPOOL/AVGPOOL kernel; LINEAR: must equal the input H, W */
     int32_t stride;
     int32_t pad;
-    int32_t ceil_mode;   /* MAXPOOL */
+    int32_t ceil_mode;   /* MAXPOOL: ceil_mode.  CONV: `groups` of a grouped convolution (nn.Conv2d(groups = g), weight [cout][Cin / g][kh][kw]); 0 and 1 mean an
+                          * ordinary convolution.  Cin and cout must be multiples of g; not on the first layer, a LINEAR or a MaxFeatureMap pair convolution */
     int32_t inplace;     /* RELU: 1 = nn.ReLU(inplace=True) (hook lands on the output tensor) */
     float   fparam;      /* MULTIPLY: n;  BATCHNORM: eps */
     int32_t w_weight;    /* index into the weight table, or -1 */
@@ -843,7 +844,8 @@ xfr_status xfr_debug_conv_stamps(void* stamps_dev, int32_t capacity_workgroups);
  * device memory, 64 bytes per launch, `capacity` launches), every GEMM launch of this process records when its first workgroup
  * started and its last one ended (s_memrealtime, 10 ns ticks) and the library notes its shape, stream and tile configuration.  A
  * call with dump_path != NULL first writes what has been recorded so far as CSV (synchronise the device before); log_dev = NULL
- * stops recording.  tools/gemm_timeline.py reads the file.
+ * stops recording.  tools/gemm_timeline.py reads the file.  (The launches of grouped convolutions -- configuration 13, their own kernel -- are not in
+ * this log; the profile records of xfr_engine_profile_csv list them.)
  * xfr_debug_conv_stamps and xfr_debug_conv_log are PROCESS-GLOBAL (every engine of the process records into them) and mutex-guarded: engines
  * may launch from other host threads while they are set, dumped or cleared; launches only touch the lock while a hook is on.  A dump after
  * log_dev = NULL writes nothing and returns XFR_OK. */
@@ -861,7 +863,8 @@ xfr_status xfr_engine_get_profile(xfr_engine* e, double* gemm_ms, int64_t* gemm_
  * kernel -- each family has its own ceiling (157.3 / 419.4 fp32-equivalent TFLOP/s), and bench.py reports a roofline fraction per family.  Arrays of 2. */
 xfr_status xfr_engine_get_profile_by_kernel(xfr_engine* e, double* gemm_ms, int64_t* gemm_launches, double* gemm_flops);
 /* While profiling is on, also append one CSV record per GEMM launch to `path` (NULL: stop):
- * Cout,nhalves,K,M,kh,stride,out_stride,relu_in,accumulate,ms,TFLOP/s,cfg  (profiles/layer_table.py reads it; cfg = the configuration that ran, 9 = bf16x6). */
+ * Cout,nhalves,K,M,kh,stride,out_stride,relu_in,accumulate,ms,TFLOP/s,cfg  (profiles/layer_table.py reads it; cfg = the configuration that ran, 9 = bf16x6,
+ * 13 = the grouped-convolution kernel, whose K is that of one group: Cin / groups * kh * kw). */
 xfr_status xfr_engine_profile_csv(xfr_engine* e, const char* path);
 
 /* Process-wide counts of GEMM launches that carried a fused elementwise chain: those whose epilogue was one of the

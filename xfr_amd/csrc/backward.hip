@@ -86,11 +86,16 @@ bool bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& st, int 
     if (!ph) p.w = e->arena + (plan.plain ? o.w_bwd_true : o.w_bwd);
     p.out0 = e->G(st.dst_t);
     p.Cin = t.C; p.H = t.H; p.W = t.W; p.NB = SBa; p.in_nb = SB; p.out_nb = SB;
-    p.tap_major = (d.stride == 1 && o.tap_bwd) ? 1 : 0;
+    p.tap_major = (d.stride == 1 && o.tap_bwd && o.groups <= 1) ? 1 : 0;
     p.in_bytes = (unsigned)((size_t)SB * t.per_n() * sizeof(float));
     p.CoutTot = a.C; p.nhalves = 1; p.ldw = o.ldb;
     p.K = o.Kb;
     p.accumulate = st.accumulate;
+    if (o.groups > 1) {
+        // a grouped layer: the same GEMM per group with the roles of Ci and Co swapped (conv_group.hip) -- no chain, no compact form
+        if (st.compact || !st.chain.empty()) return false;
+        p.groups = o.groups; p.ldw = GROUP_ROWS;
+    }
     if (st.compact) {
         // 1x1 stride-s, result left on the sampled grid (dense rows of t.H x t.W per sample): EW_AVGUP_IN places it
         p.kh = 1; p.kw = 1; p.stride = 1; p.pad = 0;
@@ -108,7 +113,7 @@ bool bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& st, int 
         // with the layer's stride from the phase's first pixel on
         p.w = e->arena + (plan.plain ? ph->w_bwd_true : ph->w_bwd);
         p.K = ph->K;
-        p.tap_major = ph->tap ? 1 : 0;
+        p.tap_major = (ph->tap && o.groups <= 1) ? 1 : 0;
         p.kh = ph->ka; p.kw = ph->kb; p.stride = 1; p.pad = ph->ka - 1 - ph->q0; p.pad_dw = (ph->kb - 1 - ph->u0) - p.pad;
         p.OH = ph->nq; p.OW = ph->nu;
         p.out0 = e->G(st.dst_t) + (size_t)ph->ih0 * a.W + ph->iw0;

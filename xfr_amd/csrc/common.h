@@ -291,6 +291,10 @@ struct ConvParams {
     int chain_interpret; // 1: run the chain through the interpreted epilogue even if a compiled one exists (tests)
     int co_pair;         // Co > 0: MaxFeatureMap convolution whose 2*Co output channels are PACKED interleaved (GEMM row 2c = channel c, row
                          // 2c+1 = channel c + Co): rows are stored at their channel's place, a chain may end in EW_MAXPAIR
+    int groups;          // > 1: a grouped convolution (conv_group.hip): group g reads input channels [g Cin / groups, (g + 1) Cin / groups) and writes output
+                         // channels [g CoutTot / groups, (g + 1) CoutTot / groups); K = (Cin / groups) * kh * kw is the K of ONE group and w / w_pos are
+                         // per-group packs (group_pack_floats below).  0 / 1: an ordinary convolution.  (The field fills the four bytes of padding in front
+                         // of `stamps`: no other member moves, and the kernels that take a ConvParams by value are the same instruction for instruction.)
     unsigned long long* stamps;   // tuning hook (xfr_debug_conv_stamps): per wave 8 words -- s_memrealtime at kernel entry, first operands landed,
                                   // K loop done, epilogue entered, exit; HW_ID; XCC_ID; life in shader cycles.  nullptr: off
     int stamps_cap;               // workgroups the stamp buffer holds (later ones do not record)
@@ -321,6 +325,7 @@ enum ConvCfg {
     CFG_KS_4_4 = 7,    // ... (4, 4)
     CFG_BF16X6 = 9,    // the bf16x6 split GEMM (conv_gemm_split.hip)
     CFG_ROW32 = 12,    // 32 x 128 block tile (four waves side by side along m)
+    CFG_GROUP = 13,    // the grouped-convolution kernel (conv_group.hip; ConvParams::groups > 1): fp32 MFMA 16x16x4, row blocks of 16 channels of one group
 };
 int conv_gemm_pick_cfg(const ConvParams& p);
 int conv_gemm_last_cfg();       // the configuration the calling thread's last launch_conv_gemm really ran (CFG_BF16X6: the bf16x6 kernel)
@@ -331,6 +336,23 @@ void conv_gemm_forget_split(const void* lo, size_t bytes);
 bool conv_gemm_presplit(const ConvParams& layer, const float* w, hipStream_t s);     // the planes of pack w of that layer (geometry, K, CoutTot, ldw); false: no memory (the pack stays on the fp32 kernels)
 int conv_gemm_split_covers(const ConvParams& p);       // a layer xfr_engine_set_split_gemm covers (whatever the launch's grid)
 long conv_gemm_split_launches();
+// Grouped convolutions (conv_group.hip, configuration 13; ConvParams::groups > 1): one launch over all groups, forward (one or two halves) and
+// backward-data alike.  The per-group pack of a layer: for every group, for every row block of 16 output channels of that group, [align_up(K, 4)][16]
+// floats -- row k = (ci, kh, kw) ci-major within the group, column = channel within the row block; rows beyond K and columns beyond the group's
+// channels are zero.  false: the parameters are not a grouped launch this kernel takes (a chain, dualacc, co_pair), nothing was launched
+constexpr int GROUP_ROWS = 16;
+inline int group_row_blocks(int co_per_group) { return (co_per_group + GROUP_ROWS - 1) / GROUP_ROWS; }
+inline int group_pack_rows(int k_per_group) { return (k_per_group + 3) / 4 * 4; }
+inline size_t group_pack_floats(int groups, int co_per_group, int k_per_group)
+{
+    return (size_t)groups * group_row_blocks(co_per_group) * group_pack_rows(k_per_group) * GROUP_ROWS;
+}
+inline size_t group_pack_index(int g, int co_local, int k, int co_per_group, int k_per_group)
+{
+    return (((size_t)g * group_row_blocks(co_per_group) + co_local / GROUP_ROWS) * group_pack_rows(k_per_group) + k) * GROUP_ROWS + co_local % GROUP_ROWS;
+}
+bool launch_conv_group(const ConvParams& p, hipStream_t s);
+long conv_group_launches();
 
 // g = src[idx]; run chain; dst[idx] = (accumulate ? dst[idx] : 0) + g.   Tensors are [C][SB][HW] for the gradient
 // and [C][B][HW] for the forward-side sources (sample b = sb % B).

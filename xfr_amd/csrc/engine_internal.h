@@ -68,7 +68,7 @@ struct PhaseRec {
     int q0 = 0, u0 = 0;        // first output row / column of the forward whose window holds a pixel of the phase: max(0, ceil((p - r) / s))
     int ih0 = 0, iw0 = 0;      // the phase's first input pixel: s q0 + r - p
     int nq = 0, nu = 0;        // the phase's pixels per axis: (H - 1 - ih0) / s + 1
-    int K = 0;                 // cout * ka * kb
+    int K = 0;                 // cout * ka * kb (of one group: cout / groups * ka * kb)
     bool tap = false;          // K packed tap-major (tap, co)
     long w_bwd = -1, w_bwd_true = -1;      // the phase's relu(W) and true packs in the arena
 };
@@ -85,6 +85,9 @@ struct OpRec {
     bool tap4_fwd = false;                   // image stems (Cin 3 or 4): K packed (kh,kw,4 channel slots); Kf = rows of the forward pack
     int Kf = 0;
     int Cin = 0, K = 0, Kb = 0;
+    int groups = 1;                          // > 1: a grouped convolution (xfr_op_desc::ceil_mode of a CONV).  K, Kb and PhaseRec::K are then those of ONE group
+                                             // (Cin / groups * kh * kw, cout / groups * kh * kw), the packs per group (conv_group.hip), and the layer carries
+                                             // no fused chain, no lean rewrite, no bf16x6, no tail balancing, no pair_m and no as_strided form
     size_t idx_off = 0;                      // maxpool argmax (bytes into idx workspace)
     size_t norm_off = 0;                     // normalize: norms (floats into misc workspace)
     int pair = 0;                            // MaxFeatureMap convolution (Conv -> Split -> max of halves, lightcnn.py:48-62): Co = cout / 2; its forward

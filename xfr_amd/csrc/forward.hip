@@ -34,6 +34,27 @@ static xfr_status pos_op(xfr_engine* e, int k, int B, hipStream_t s);
 // ---------------------------------------------------------------------------------------------------------------
 xfr_status run_conv(xfr_engine* e, const ConvParams& p_in, hipStream_t s)
 {
+    if (p_in.groups > 1) {
+        // a grouped layer (conv_group.hip, configuration 13): no chain, no bf16x6, no tail balancing
+        if (e->profile_on) {
+            if (e->ev_used == e->ev_pool.size()) {
+                Event a, b;
+                XFR_TRY(a.create(true));
+                XFR_TRY(b.create(true));
+                e->ev_pool.emplace_back(std::move(a), std::move(b));
+            }
+            if (e->ev_params.size() < e->ev_pool.size()) { e->ev_params.resize(e->ev_pool.size()); e->ev_cfg.resize(e->ev_pool.size()); }
+            HIP_TRY(hipEventRecord(e->ev_pool[e->ev_used].first, s));
+        }
+        if (!launch_conv_group(p_in, s)) return fail(XFR_STATE_ERROR, "a grouped convolution launch (groups %d) the grouped kernel does not take", p_in.groups);
+        if (e->profile_on) {
+            e->ev_params[e->ev_used] = p_in;
+            e->ev_cfg[e->ev_used] = CFG_GROUP;
+            HIP_TRY(hipEventRecord(e->ev_pool[e->ev_used++].second, s));
+            e->prof_flops += 2.0 * (double)p_in.K * (double)p_in.M * (double)p_in.CoutTot * (double)p_in.nhalves;      // K of one group
+        }
+        return XFR_OK;
+    }
     ConvParams p = p_in;
     p.chain_interpret = e->interpret_chains ? 1 : 0;
     p.split_ok = (e->split_mask & (p.bwd ? 2 : 1)) ? (e->split_any_grid ? 2 : 1) : 0;
@@ -100,6 +121,7 @@ void conv_geometry(xfr_engine* e, int k, int NB, ConvParams& p)
     p.in_bytes = (unsigned)((size_t)NB * a.per_n() * sizeof(float));
     p.tap_major = o.tap4_fwd ? 2 : (o.tap_fwd ? 1 : 0);
     p.co_pair = o.pair;
+    if (o.groups > 1) { p.groups = o.groups; p.tap_major = 0; p.ldw = GROUP_ROWS; }
 }
 
 // The reference evaluates a down-sampling block's shortcut BEHIND the main path (resnet.py:144-146: `residual = self.downsample(x)` after
@@ -446,7 +468,8 @@ static xfr_status fwd_op(xfr_engine* e, int k, int B, bool want_pos, hipStream_t
                 e->fwd_done[o.pair_max] = 1;
                 return XFR_OK;
             }
-            if (o.pair && e->fuse_fwd_only && !dual && !p.relu_in && fuse_mfm_forward(e, k, B, want_pos || keep_raw, p, want_pos)) { }
+            if (o.groups > 1) { }       // a grouped layer carries no epilogue: the ops behind it keep their kernels
+            else if (o.pair && e->fuse_fwd_only && !dual && !p.relu_in && fuse_mfm_forward(e, k, B, want_pos || keep_raw, p, want_pos)) { }
             else if (!want_pos && e->fuse_fwd_only && !p.relu_in) fuse_forward_only(e, k, B, p, s);
             else if (want_pos && e->fuse_probe_fwd && !p.relu_in) fuse_probe_forward(e, k, B, p, s, dual);
             if (p.chain.n > 0 && p.chain.s[0].type == EW_LEAN_Q) {

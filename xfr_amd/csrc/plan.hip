@@ -69,6 +69,17 @@ xfr_status build(xfr_engine* e, const xfr_op_desc* ops, int n_ops)
                     return fail(XFR_INVALID_ARG, "op %d: bad conv/linear geometry", k);
                 if (d.kind == XFR_OP_LINEAR && (d.kh != a.H || d.kw != a.W || d.pad != 0))
                     return fail(XFR_INVALID_ARG, "op %d: linear kernel must equal the input extent %dx%d", k, a.H, a.W);
+                // grouped convolution: `groups` travels in the ceil_mode slot (0 and 1: an ordinary convolution)
+                if (d.ceil_mode < 0) return fail(XFR_INVALID_ARG, "op %d: groups must be >= 1 (got %d)", k, d.ceil_mode);
+                const int G = d.ceil_mode > 1 ? d.ceil_mode : 1;
+                if (G > 1) {
+                    if (d.kind == XFR_OP_LINEAR) return fail(XFR_UNSUPPORTED_LAYER, "op %d: groups %d on a Linear layer is not supported", k, G);
+                    if (k == 0)
+                        return fail(XFR_UNSUPPORTED_LAYER, "op %d: groups %d on the first layer is not supported (the image stem has its own paths)", k, G);
+                    if (a.C % G) return fail(XFR_INVALID_ARG, "op %d: %d input channels are not divisible by groups %d", k, a.C, G);
+                    if (d.cout % G) return fail(XFR_INVALID_ARG, "op %d: %d output channels are not divisible by groups %d", k, d.cout, G);
+                }
+                o.groups = G;
                 t.C = d.cout;
                 t.H = (a.H + 2 * d.pad - d.kh) / d.stride + 1;
                 t.W = (a.W + 2 * d.pad - d.kw) / d.stride + 1;
@@ -88,12 +99,12 @@ xfr_status build(xfr_engine* e, const xfr_op_desc* ops, int n_ops)
                             ph.ih0 = s * ph.q0 + r - p; ph.iw0 = s * ph.u0 + c - p;
                             if (ph.ih0 >= a.H || ph.iw0 >= a.W) continue;      // the phase's origin lies outside the map
                             ph.nq = (a.H - 1 - ph.ih0) / s + 1; ph.nu = (a.W - 1 - ph.iw0) / s + 1;
-                            ph.K = d.cout * ph.ka * ph.kb;
-                            ph.tap = (d.cout % 16 == 0) && (ph.ka * ph.kb <= 64);
+                            ph.K = d.cout / G * ph.ka * ph.kb;
+                            ph.tap = G == 1 && (d.cout % 16 == 0) && (ph.ka * ph.kb <= 64);
                             o.phases.push_back(ph);
                         }
                 }
-                o.Cin = a.C; o.K = a.C * d.kh * d.kw; o.Kb = d.cout * d.kh * d.kw;
+                o.Cin = a.C; o.K = a.C / G * d.kh * d.kw; o.Kb = d.cout / G * d.kh * d.kw;      // of ONE group where the layer has groups
                 t.nonneg = false; t.pstate = PS_OTHER;
                 break;
             }
@@ -198,6 +209,9 @@ xfr_status build(xfr_engine* e, const xfr_op_desc* ops, int n_ops)
         if (e->ops[k1].d.kind != XFR_OP_SPLIT || e->tens[e->ops[k1].d.out].consumers.size() != 1) continue;
         const int k2 = e->tens[e->ops[k1].d.out].consumers[0];
         if (e->ops[k2].d.kind != XFR_OP_G_MAXHALVES) continue;
+        if (e->ops[k].groups > 1)
+            return fail(XFR_UNSUPPORTED_LAYER, "op %d: groups %d on a MaxFeatureMap pair convolution (Conv -> Split -> max of halves) is not supported", k,
+                        e->ops[k].groups);
         e->ops[k].pair = d.cout / 2;
         e->ops[k].pair_split = k1;
         e->ops[k].pair_max = k2;
@@ -299,7 +313,22 @@ xfr_status layout_arena(xfr_engine* e)
     for (size_t k = 0; k < e->ops.size(); ++k) {
         OpRec& o = e->ops[k];
         const xfr_op_desc& d = o.d;
-        if (d.kind == XFR_OP_CONV || d.kind == XFR_OP_LINEAR) {
+        if ((d.kind == XFR_OP_CONV || d.kind == XFR_OP_LINEAR) && o.groups > 1) {
+            // a grouped layer: the same set of packs in the per-group layout of conv_group.hip (common.h: group_pack_floats), no tap-major order
+            const int Ci = o.Cin / o.groups, Co = d.cout / o.groups;
+            o.Kf = o.K;
+            o.w_true = take(group_pack_floats(o.groups, Co, o.K));
+            o.w_pos = take(group_pack_floats(o.groups, Co, o.K));
+            if (o.phases.empty()) {
+                o.w_bwd = take(group_pack_floats(o.groups, Ci, o.Kb));
+                o.w_bwd_true = take(group_pack_floats(o.groups, Ci, o.Kb));
+            }
+            for (PhaseRec& ph : o.phases) {
+                ph.w_bwd = take(group_pack_floats(o.groups, Ci, ph.K));
+                ph.w_bwd_true = take(group_pack_floats(o.groups, Ci, ph.K));
+            }
+            if (d.w_bias >= 0) { o.b_true = take(d.cout); o.b_pos = take(d.cout); }
+        } else if (d.kind == XFR_OP_CONV || d.kind == XFR_OP_LINEAR) {
             o.ldw = (int)align_up(d.cout, 128);
             o.tap_fwd = (d.kh * d.kw > 1) && (o.Cin % 16 == 0) && (d.kh * d.kw <= 64);
             o.tap_bwd = (d.kh * d.kw > 1) && (d.cout % 16 == 0) && (d.kh * d.kw <= 64);

@@ -57,6 +57,15 @@ xfr_status xfr_plan_describe(const xfr_op_desc* ops, int32_t n_ops, int32_t n_we
         ConvParams p;
         conv_geometry(e, k, batch, p);
         p.out0 = e->T(d.out);
+        if (e->ops[k].groups > 1) {
+            // a grouped layer: no epilogue, one launch of the grouped kernel over all groups (per-group Ci, Co and K)
+            if (kind == FWD_LEAN) return 0;
+            const int G = e->ops[k].groups;
+            snprintf(line, sizeof(line), "%s GROUPED op %d [%d x %d x %d] groups %d Ci %d Co %d K %d M %d cfg %d\n", fwd_names[kind], k, e->tens[d.out].C,
+                     e->tens[d.out].H, e->tens[d.out].W, G, e->ops[k].Cin / G, d.cout / G, p.K, p.M, CFG_GROUP);
+            out += line;
+            return 0;
+        }
         if (kind == FWD_LEAN) {
             const bool dual = e->tens[d.out].need_pv && e->tens[d.in0].nonneg;
             if (e->ops[k].pair || !dual) return 0;
@@ -105,6 +114,14 @@ xfr_status xfr_plan_describe(const xfr_op_desc* ops, int32_t n_ops, int32_t n_we
                 const int tt = b.kind == ST_EW ? b.ew_t : b.dst_t;
                 if (tt >= 0) { snprintf(line, sizeof(line), " [%d x %d x %d]", e->tens[tt].C, e->tens[tt].H, e->tens[tt].W); out += line; }
                 if (b.kind == ST_CONV_BWD) { snprintf(line, sizeof(line), " K %d", e->ops[b.op].Kb); out += line; }
+                if (b.kind == ST_CONV_BWD && e->ops[b.op].groups > 1) {      // the backward-data GEMM of a grouped layer: Ci and Co of the GEMM (the layer's swapped)
+                    // (M 0: the layer runs by phases, whose PHASE lines below carry their own M)
+                    const OpRec& go = e->ops[b.op];
+                    ConvParams gp;
+                    const bool one = go.phases.empty() && bwd_conv_params(e, *plan, b, batch, 2 * batch, 2 * batch, gp);
+                    snprintf(line, sizeof(line), " groups %d Ci %d Co %d M %d cfg %d", go.groups, go.d.cout / go.groups, go.Cin / go.groups, one ? gp.M : 0, CFG_GROUP);
+                    out += line;
+                }
             }
             if (!b.chain.empty()) {
                 EwChain ch;
@@ -124,9 +141,12 @@ xfr_status xfr_plan_describe(const xfr_op_desc* ops, int32_t n_ops, int32_t n_we
                 for (const PhaseRec& ph : e->ops[b.op].phases) {
                     ConvParams p;
                     if (!bwd_conv_params(e, *plan, b, batch, 2 * batch, 2 * batch, p, &ph)) continue;
-                    snprintf(line, sizeof(line), "%s PHASE op %d (%d,%d) kernel %dx%d cfg %d K %d M %d origin (%d,%d) grid %d x %d\n", prefix, b.op, ph.r, ph.c,
-                             ph.ka, ph.kb, conv_gemm_pick_cfg(p), p.K, p.M, ph.ih0, ph.iw0, ph.nq, ph.nu);
+                    const int G = e->ops[b.op].groups;
+                    snprintf(line, sizeof(line), "%s PHASE op %d (%d,%d) kernel %dx%d cfg %d K %d M %d origin (%d,%d) grid %d x %d", prefix, b.op, ph.r, ph.c,
+                             ph.ka, ph.kb, G > 1 ? (int)CFG_GROUP : conv_gemm_pick_cfg(p), p.K, p.M, ph.ih0, ph.iw0, ph.nq, ph.nu);
                     out += line;
+                    if (G > 1) { snprintf(line, sizeof(line), " groups %d Ci %d Co %d", G, e->ops[b.op].d.cout / G, e->ops[b.op].Cin / G); out += line; }
+                    out += "\n";
                 }
         }
     };

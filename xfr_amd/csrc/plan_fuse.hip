@@ -79,7 +79,8 @@ bool writes(const BwdStep& b, int t)
     for (const Sym& y : b.chain) if (y.type == EW_STORE && y.t0 == t) return true;
     return false;
 }
-bool scatter_conv(const xfr_engine* e, const BwdStep& b) { return b.kind == ST_CONV_BWD && e->ops[b.op].d.stride != 1; }
+// a backward-data GEMM that takes no chain: it scatters (a strided layer), or it is a grouped layer's (conv_group.hip has no epilogue)
+bool scatter_conv(const xfr_engine* e, const BwdStep& b) { return b.kind == ST_CONV_BWD && (e->ops[b.op].d.stride != 1 || e->ops[b.op].groups > 1); }
 // first step at or after `from` that reads or writes t (st.size(): none)
 size_t next_touch(const std::vector<BwdStep>& st, size_t from, int t)
 {
@@ -246,6 +247,7 @@ void fuse_downsample_avgpool(xfr_engine* e, std::vector<BwdStep>& st)
         if (cv.kind != ST_CONV_BWD || cv.dst_t != D || !cv.accumulate || !cv.chain.empty()) continue;
         const xfr_op_desc& dc = e->ops[cv.op].d;
         if (dc.kh != 1 || dc.kw != 1 || dc.stride != 2 || dc.pad != 0 || dc.in0 != D || e->tens[dc.out].H != tp.H || e->tens[dc.out].W != tp.W) continue;
+        if (e->ops[cv.op].groups > 1) continue;            // a grouped layer has no compact form
         const size_t i4 = next_touch(st, i3 + 1, D);
         if (i4 >= st.size()) continue;
         const BwdStep& ew = st[i4];
@@ -291,7 +293,7 @@ void fuse_downsample_projection(xfr_engine* e, std::vector<BwdStep>& st)
             const BwdStep& cv = st[k];
             const xfr_op_desc& dc = e->ops[cv.op].d;
             const Tensor& tg = e->tens[dc.out];
-            if (cv.dst_t != D || !cv.accumulate || !cv.chain.empty() || dc.kh != 1 || dc.kw != 1 || dc.stride != 2 || dc.pad != 0 || dc.in0 != D ||
+            if (cv.dst_t != D || !cv.accumulate || !cv.chain.empty() || e->ops[cv.op].groups > 1 || dc.kh != 1 || dc.kw != 1 || dc.stride != 2 || dc.pad != 0 || dc.in0 != D ||
                 td.H != 2 * tg.H || td.W != 2 * tg.W || (gh >= 0 && (gh != tg.H || gw != tg.W))) { ok = false; break; }
             gh = tg.H; gw = tg.W;
             gemms.push_back(k);

@@ -14,9 +14,54 @@ xfr_status pack_weights(const xfr_engine* e, const xfr_tensor_view* w, std::vect
         if (d.kind == XFR_OP_CONV || d.kind == XFR_OP_LINEAR) {
             const xfr_tensor_view& wv = w[d.w_weight];
             const int khw = d.kh * d.kw;
-            if (!wv.data || wv.numel != (int64_t)d.cout * o.Cin * khw)
+            if (!wv.data || wv.numel != (int64_t)d.cout * (o.Cin / o.groups) * khw)
                 return fail(XFR_INVALID_ARG, "op %zu: weight has %lld elements, expected %lld", k, (long long)wv.numel,
-                            (long long)d.cout * o.Cin * khw);
+                            (long long)d.cout * (o.Cin / o.groups) * khw);
+            if (o.groups > 1) {
+                // A grouped layer, weight [cout][Ci][kh][kw] with Ci = Cin / groups: every pack of a dense layer per group, group after group, in the
+                // layout of conv_group.hip (common.h: group_pack_index) -- K ordered ci-major, (ci, kh, kw) within the group, which is the weight's own
+                // order; rows up to the next multiple of 4 and the columns of a ragged row block stay zero.  Output channel co = g Co + col belongs to
+                // group g; in the backward-data packs the roles swap: row (col, flipped tap) of group g, column ci.
+                const int G = o.groups, Ci = o.Cin / G, Co = d.cout / G;
+                float* wt = host.data() + o.w_true;
+                float* wp = host.data() + o.w_pos;
+                for (int co = 0; co < d.cout; ++co) {
+                    const int g = co / Co, col = co % Co;
+                    const float* src = wv.data + (size_t)co * o.K;
+                    for (int kk = 0; kk < o.K; ++kk) {
+                        const size_t at = group_pack_index(g, col, kk, Co, o.K);
+                        wt[at] = src[kk];
+                        wp[at] = src[kk] > 0.f ? src[kk] : 0.f;
+                    }
+                    for (int ci = 0; ci < Ci; ++ci)
+                        for (int a = 0; a < d.kh; ++a)
+                            for (int b = 0; b < d.kw; ++b) {
+                                const float v = src[(ci * d.kh + a) * d.kw + b];
+                                if (o.w_bwd >= 0) {
+                                    const size_t at = group_pack_index(g, ci, (col * d.kh + (d.kh - 1 - a)) * d.kw + (d.kw - 1 - b), Ci, o.Kb);
+                                    host[o.w_bwd + at] = v > 0.f ? v : 0.f;
+                                    host[o.w_bwd_true + at] = v;
+                                }
+                                for (const PhaseRec& ph : o.phases) {
+                                    const int s = d.stride;
+                                    if (a % s != ph.r || b % s != ph.c) continue;
+                                    const int i2 = ph.ka - 1 - a / s, j2 = ph.kb - 1 - b / s;
+                                    const size_t at = group_pack_index(g, ci, (col * ph.ka + i2) * ph.kb + j2, Ci, ph.K);
+                                    host[ph.w_bwd + at] = v > 0.f ? v : 0.f;
+                                    host[ph.w_bwd_true + at] = v;
+                                }
+                            }
+                }
+                if (d.w_bias >= 0) {
+                    const xfr_tensor_view& bv = w[d.w_bias];
+                    if (!bv.data || bv.numel != d.cout) return fail(XFR_INVALID_ARG, "op %zu: bad bias size", k);
+                    for (int co = 0; co < d.cout; ++co) {
+                        host[o.b_true + co] = bv.data[co];
+                        host[o.b_pos + co] = bv.data[co] > 0.f ? bv.data[co] : 0.f;
+                    }
+                }
+                continue;
+            }
             float* wt = host.data() + o.w_true;
             float* wp = host.data() + o.w_pos;
             // forward pack: [k][co], k = (ci,kh,kw) or tap-major (kh,kw,ci)
@@ -103,7 +148,7 @@ void presplit_weights(xfr_engine* e)
     for (size_t k = 0; k < e->ops.size(); ++k) {
         const OpRec& o = e->ops[k];
         const xfr_op_desc& d = o.d;
-        if (d.kind != XFR_OP_CONV && d.kind != XFR_OP_LINEAR) continue;
+        if ((d.kind != XFR_OP_CONV && d.kind != XFR_OP_LINEAR) || o.groups > 1) continue;        // (a grouped layer never runs the bf16x6 kernel)
         ConvParams p;
         conv_geometry(e, (int)k, 1, p);
         p.CoutTot = d.cout; p.nhalves = 1;

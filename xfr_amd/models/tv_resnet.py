@@ -1,7 +1,9 @@
 """The torchvision ResNet family (torchvision/models/resnet.py) for the EBP hot path, with torchvision's state-dict names: BasicBlock nets
 (resnet18 [2,2,2,2], resnet34 [3,4,6,3]) and Bottleneck v1.5 nets (resnet50 [3,4,6,3]: the stride on the 3x3), functional `out += identity`,
 in-place ReLU, a 1x1 / stride 2 projection + BatchNorm shortcut where a stage opens.  The strided 3x3 layers behind the stem run their
-backward-data pass by phases (xfr_amd/csrc/plan.hip).
+backward-data pass by phases (xfr_amd/csrc/plan.hip).  `groups` and `width_per_group` are torchvision's: the Bottleneck's inner width is
+int(planes * width_per_group / 64) * groups and its 3x3 (conv2) is a grouped convolution (xfr_amd/csrc/conv_group.hip) -- ResNeXt-50 32x4d,
+ResNeXt-101 32x8d and 64x4d; width_per_group = 128 alone gives wide_resnet50_2.
 
 `width` is the channel count of the first stage (64 in torchvision), `in_shape` any C x H x W whose last stage map is square: the
 AdaptiveAvgPool2d((1, 1)) in front of `fc` is an average pool over that map."""
@@ -14,10 +16,14 @@ from ._backbone import Backbone
 class TVResnet(Backbone):
     arch = 'tv_resnet'
 
-    def __init__(self, block='basic', layers=(2, 2, 2, 2), num_classes=1000, width=64, in_shape=(3, 224, 224)):
+    def __init__(self, block='basic', layers=(2, 2, 2, 2), num_classes=1000, width=64, in_shape=(3, 224, 224), groups=1, width_per_group=64):
         super(TVResnet, self).__init__()
         if block not in ('basic', 'bottleneck'):
             raise ValueError("block must be 'basic' or 'bottleneck'")
+        if block == 'basic' and (groups != 1 or width_per_group != 64):
+            raise ValueError('BasicBlock only supports groups=1 and base_width=64')
+        self.groups = int(groups)
+        self.width_per_group = int(width_per_group)
         self.block = block
         self.layers = tuple(int(v) for v in layers)
         self.num_classes = int(num_classes)
@@ -37,6 +43,10 @@ class TVResnet(Backbone):
                 yield 'layer%d.%d' % (s + 1, b), cin, planes, stride, (stride != 1 or cin != planes * self.expansion)
                 cin = planes * self.expansion
 
+    def inner_width(self, planes):
+        """torchvision's Bottleneck: width = int(planes * (base_width / 64.0)) * groups."""
+        return int(planes * (self.width_per_group / 64.0)) * self.groups
+
     @property
     def feature_dim(self):
         return (self.width << (len(self.layers) - 1)) * self.expansion
@@ -44,8 +54,8 @@ class TVResnet(Backbone):
     def param_specs(self):
         specs = []
 
-        def conv(p, cin, cout, k):
-            specs.append((p + '.weight', (cout, cin, k, k), 'conv_w'))
+        def conv(p, cin, cout, k, groups=1):
+            specs.append((p + '.weight', (cout, cin // groups, k, k), 'conv_w'))
 
         def bn(p, c):
             specs.extend([(p + '.weight', (c,), 'bn_w'), (p + '.bias', (c,), 'bn_b'),
@@ -60,11 +70,12 @@ class TVResnet(Backbone):
                 conv(pre + '.conv2', planes, planes, 3)
                 bn(pre + '.bn2', planes)
             else:
-                conv(pre + '.conv1', cin, planes, 1)
-                bn(pre + '.bn1', planes)
-                conv(pre + '.conv2', planes, planes, 3)
-                bn(pre + '.bn2', planes)
-                conv(pre + '.conv3', planes, planes * 4, 1)
+                wd = self.inner_width(planes)
+                conv(pre + '.conv1', cin, wd, 1)
+                bn(pre + '.bn1', wd)
+                conv(pre + '.conv2', wd, wd, 3, self.groups)
+                bn(pre + '.bn2', wd)
+                conv(pre + '.conv3', wd, planes * 4, 1)
                 bn(pre + '.bn3', planes * 4)
             if proj:
                 conv(pre + '.downsample.0', cin, planes * self.expansion, 1)
@@ -96,9 +107,11 @@ class TVResnet(Backbone):
                 o = p.conv(o, pre + '.conv2', planes, 3, stride=1, pad=1, bias=False)
                 o = p.batchnorm(o, pre + '.bn2')
             else:
-                o = p.conv(t, pre + '.conv1', planes, 1, bias=False)
+                wd = self.inner_width(planes)
+                grouped = dict(groups=self.groups) if self.groups > 1 else {}                   # (builders without grouped layers keep the old signature)
+                o = p.conv(t, pre + '.conv1', wd, 1, bias=False)
                 o = p.relu_(p.batchnorm(o, pre + '.bn1'))
-                o = p.conv(o, pre + '.conv2', planes, 3, stride=stride, pad=1, bias=False)      # v1.5: the stride sits on the 3x3
+                o = p.conv(o, pre + '.conv2', wd, 3, stride=stride, pad=1, bias=False, **grouped)      # v1.5: the stride sits on the 3x3
                 o = p.relu_(p.batchnorm(o, pre + '.bn2'))
                 o = p.conv(o, pre + '.conv3', planes * 4, 1, bias=False)
                 o = p.batchnorm(o, pre + '.bn3')
@@ -137,3 +150,20 @@ def resnet34(weights_path=None, **kwargs):
 def resnet50(weights_path=None, **kwargs):
     """Bottleneck v1.5 [3, 4, 6, 3]."""
     return _make('bottleneck', (3, 4, 6, 3), weights_path, kwargs)
+
+
+def resnext50_32x4d(weights_path=None, **kwargs):
+    return _make('bottleneck', (3, 4, 6, 3), weights_path, dict(kwargs, groups=32, width_per_group=4))
+
+
+def resnext101_32x8d(weights_path=None, **kwargs):
+    return _make('bottleneck', (3, 4, 23, 3), weights_path, dict(kwargs, groups=32, width_per_group=8))
+
+
+def resnext101_64x4d(weights_path=None, **kwargs):
+    return _make('bottleneck', (3, 4, 23, 3), weights_path, dict(kwargs, groups=64, width_per_group=4))
+
+
+def wide_resnet50_2(weights_path=None, **kwargs):
+    """Bottleneck [3, 4, 6, 3] with inner widths twice ResNet-50's (width_per_group = 128); no grouped layer."""
+    return _make('bottleneck', (3, 4, 6, 3), weights_path, dict(kwargs, width_per_group=128))

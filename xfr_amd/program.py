@@ -34,7 +34,8 @@ LAYER_NAMES = {
 
 
 class OpDesc(ctypes.Structure):
-    """Mirror of `xfr_op_desc` in include/xfr_amd.h."""
+    """Mirror of `xfr_op_desc` in include/xfr_amd.h.  `ceil_mode` is MAXPOOL's flag and, on a CONV, carries `groups` of a grouped convolution
+    (0 and 1: an ordinary convolution)."""
     _fields_ = [
         ('kind', ctypes.c_int32), ('in0', ctypes.c_int32), ('in1', ctypes.c_int32), ('out', ctypes.c_int32),
         ('cout', ctypes.c_int32), ('kh', ctypes.c_int32), ('kw', ctypes.c_int32), ('stride', ctypes.c_int32),
@@ -75,8 +76,9 @@ class Program(object):
         return out
 
     # hooked leaf modules -----------------------------------------------------------------------------
-    def conv(self, x, prefix, cout, k, stride=1, pad=0, bias=True):
-        return self._op(OpKind.CONV, x, cout=cout, kh=k, kw=k, stride=stride, pad=pad,
+    def conv(self, x, prefix, cout, k, stride=1, pad=0, bias=True, groups=1):
+        """nn.Conv2d; groups > 1: a grouped convolution, weight (cout, Cin / groups, k, k) -- `groups` travels in the op's ceil_mode slot."""
+        return self._op(OpKind.CONV, x, cout=cout, kh=k, kw=k, stride=stride, pad=pad, ceil_mode=int(groups) if int(groups) != 1 else 0,
                         w_weight=prefix + '.weight', w_bias=(prefix + '.bias') if bias else None)
 
     def batchnorm(self, x, prefix, eps=1e-5):
@@ -179,7 +181,7 @@ class Program(object):
         ch = ch or self.tensor_channels()
         with torch.device('meta'):
             if kind == OpKind.CONV:
-                return str(torch.nn.Conv2d(ch[o.in0], o.cout, o.kh, stride=o.stride, padding=o.pad, bias=o.w_bias >= 0))
+                return str(torch.nn.Conv2d(ch[o.in0], o.cout, o.kh, stride=o.stride, padding=o.pad, groups=max(o.ceil_mode, 1), bias=o.w_bias >= 0))
             if kind == OpKind.BATCHNORM:
                 return str(torch.nn.BatchNorm2d(ch[o.in0], eps=float('%.6g' % o.fparam)))
             if kind == OpKind.RELU:
