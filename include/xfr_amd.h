@@ -270,7 +270,9 @@ xfr_status xfr_engine_set_inputs_ready(xfr_engine* e, int32_t ready);
  * the main path's last convolution, so that the residual add [+ ReLU] joins that convolution's epilogue like in every other block, and keeps the
  * pooled shortcut inside its zero-padded form (a channel prefix is a storage prefix in CNHW: the padding is one fill, no copy).  The order of two
  * independent branches changes no value; bit 8 (tests, A/B) keeps program order and the separate add.
- * Bit 9 (tests, A/B): the phase launches of a strided KxK layer's backward-data pass run one after another instead of side by side (same bits). */
+ * Bit 9 (tests, A/B): the phase launches of a strided KxK layer's backward-data pass run one after another instead of side by side (same bits).
+ * Bit 10 (tests, A/B): depthwise launches (a grouped launch with one input or one output channel per group) stay on configuration 13, the grouped
+ * MFMA kernel, instead of the vector-ALU kernel of configuration 14 (same values to rounding: the order of the sums differs). */
 xfr_status xfr_engine_set_epilogue_fusion(xfr_engine* e, int32_t enable);
 
 /* Share one forward pass between consecutive calls on the same input (off by default).  While hold = 1, a run call

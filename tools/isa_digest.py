@@ -20,7 +20,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'xfr_amd', 'csrc')
-DEFAULT_FILES = ('conv_gemm.hip', 'conv_gemm_split.hip', 'elementwise.hip', 'strise.hip', 'inpaint.hip', 'saliency.hip', 'match.hip', 'finish.hip', 'intake.hip', 'u8_tail.hip')
+DEFAULT_FILES = ('conv_gemm.hip', 'conv_gemm_split.hip', 'elementwise.hip', 'strise.hip', 'inpaint.hip', 'saliency.hip', 'match.hip', 'finish.hip', 'intake.hip', 'u8_tail.hip', 'conv_depthwise.hip')
 FIGURES = (('vgpr', 'NumVgprs'), ('agpr', 'NumAgprs'), ('sgpr', '(?:Total)?NumSgprs'), ('scratch', 'ScratchSize'), ('lds', 'LDSByteSize'), ('occupancy', 'Occupancy'))
 
 

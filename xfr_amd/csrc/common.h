@@ -326,6 +326,7 @@ enum ConvCfg {
     CFG_BF16X6 = 9,    // the bf16x6 split GEMM (conv_gemm_split.hip)
     CFG_ROW32 = 12,    // 32 x 128 block tile (four waves side by side along m)
     CFG_GROUP = 13,    // the grouped-convolution kernel (conv_group.hip; ConvParams::groups > 1): fp32 MFMA 16x16x4, row blocks of 16 channels of one group
+    CFG_DEPTHWISE = 14, // the depthwise kernel (conv_depthwise.hip; a grouped launch with one input or one output channel per group): fp32 on the vector ALU
 };
 int conv_gemm_pick_cfg(const ConvParams& p);
 int conv_gemm_last_cfg();       // the configuration the calling thread's last launch_conv_gemm really ran (CFG_BF16X6: the bf16x6 kernel)
@@ -353,6 +354,12 @@ inline size_t group_pack_index(int g, int co_local, int k, int co_per_group, int
 }
 bool launch_conv_group(const ConvParams& p, hipStream_t s);
 long conv_group_launches();
+// Depthwise launches (conv_depthwise.hip, configuration 14): the grouped launches with min(Cin, CoutTot) / groups == 1 -- a depthwise layer's forward
+// (any channel multiplier), its backward-data pass, the phases of a strided one -- in fp32 on the vector ALU from one LDS staging of the input.  The
+// contract and the packs are launch_conv_group's.  false: not a launch this kernel takes (see the caps in its head comment), nothing was launched:
+// the caller goes on to launch_conv_group
+bool launch_conv_depthwise(const ConvParams& p, hipStream_t s);
+long conv_depthwise_launches();
 
 // g = src[idx]; run chain; dst[idx] = (accumulate ? dst[idx] : 0) + g.   Tensors are [C][SB][HW] for the gradient
 // and [C][B][HW] for the forward-side sources (sample b = sb % B).

@@ -634,6 +634,7 @@ xfr_status xfr_engine_set_epilogue_fusion(xfr_engine* e, int32_t enable)
     e->hoist_shortcut = (enable & 256) == 0;      // bit 8 (tests, A/B): the down-sampling blocks' shortcut in program order, their residual add as its own launch
     e->direct_stem = (enable & 16) == 0;          // bit 4 (tests): the first layer of Light-CNN through the GEMM like every other convolution
     e->overlap_phases = (enable & 512) == 0;      // bit 9 (tests, A/B): the phase launches of a strided KxK layer's backward-data pass one after another on the sweep's stream
+    e->depthwise_valu = (enable & 1024) == 0;     // bit 10 (tests, A/B): depthwise launches stay on configuration 13 (conv_group.hip) instead of 14 (conv_depthwise.hip)
     e->held_x = nullptr;
     for (auto& p : e->plans) p.lean_state = -1;   // the lean tables follow the probe forward's fusion decisions
     return XFR_OK;

@@ -217,6 +217,7 @@ struct xfr_engine {
     Event ev_tab;                      // the last host-to-device table copy (subtree scratch)
     std::unique_ptr<PhaseStreams> ph_streams;      // built at the first sweep through a strided KxK layer (backward.hip)
     bool overlap_phases = true;        // the phases of one layer run side by side (they write disjoint pixels); profiled runs keep them in a row
+    bool depthwise_valu = true;        // depthwise launches on the vector-ALU kernel (conv_depthwise.hip, configuration 14); fusion-mask bit 10 keeps them on 13
     std::vector<std::pair<Event, Event>> ev_pool;      // profiling: one pair per GEMM launch of a run
     // parameters
     DevBuf<float> arena;

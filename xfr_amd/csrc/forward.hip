@@ -35,7 +35,7 @@ static xfr_status pos_op(xfr_engine* e, int k, int B, hipStream_t s);
 xfr_status run_conv(xfr_engine* e, const ConvParams& p_in, hipStream_t s)
 {
     if (p_in.groups > 1) {
-        // a grouped layer (conv_group.hip, configuration 13): no chain, no bf16x6, no tail balancing
+        // a grouped layer (conv_group.hip, configuration 13; a depthwise launch: conv_depthwise.hip, configuration 14): no chain, no bf16x6, no tail balancing
         if (e->profile_on) {
             if (e->ev_used == e->ev_pool.size()) {
                 Event a, b;
@@ -46,10 +46,11 @@ xfr_status run_conv(xfr_engine* e, const ConvParams& p_in, hipStream_t s)
             if (e->ev_params.size() < e->ev_pool.size()) { e->ev_params.resize(e->ev_pool.size()); e->ev_cfg.resize(e->ev_pool.size()); }
             HIP_TRY(hipEventRecord(e->ev_pool[e->ev_used].first, s));
         }
-        if (!launch_conv_group(p_in, s)) return fail(XFR_STATE_ERROR, "a grouped convolution launch (groups %d) the grouped kernel does not take", p_in.groups);
+        const bool dw = e->depthwise_valu && launch_conv_depthwise(p_in, s);
+        if (!dw && !launch_conv_group(p_in, s)) return fail(XFR_STATE_ERROR, "a grouped convolution launch (groups %d) the grouped kernel does not take", p_in.groups);
         if (e->profile_on) {
             e->ev_params[e->ev_used] = p_in;
-            e->ev_cfg[e->ev_used] = CFG_GROUP;
+            e->ev_cfg[e->ev_used] = dw ? CFG_DEPTHWISE : CFG_GROUP;
             HIP_TRY(hipEventRecord(e->ev_pool[e->ev_used++].second, s));
             e->prof_flops += 2.0 * (double)p_in.K * (double)p_in.M * (double)p_in.CoutTot * (double)p_in.nhalves;      // K of one group
         }

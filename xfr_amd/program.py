@@ -77,8 +77,10 @@ class Program(object):
 
     # hooked leaf modules -----------------------------------------------------------------------------
     def conv(self, x, prefix, cout, k, stride=1, pad=0, bias=True, groups=1):
-        """nn.Conv2d; groups > 1: a grouped convolution, weight (cout, Cin / groups, k, k) -- `groups` travels in the op's ceil_mode slot."""
-        return self._op(OpKind.CONV, x, cout=cout, kh=k, kw=k, stride=stride, pad=pad, ceil_mode=int(groups) if int(groups) != 1 else 0,
+        """nn.Conv2d; groups > 1: a grouped convolution, weight (cout, Cin / groups, k, k) -- `groups` travels in the op's ceil_mode slot.
+        k: an int, or (kh, kw) for a kernel that is not square (the global depthwise head on a map that is not)."""
+        kh, kw = (k, k) if isinstance(k, int) else k
+        return self._op(OpKind.CONV, x, cout=cout, kh=kh, kw=kw, stride=stride, pad=pad, ceil_mode=int(groups) if int(groups) != 1 else 0,
                         w_weight=prefix + '.weight', w_bias=(prefix + '.bias') if bias else None)
 
     def batchnorm(self, x, prefix, eps=1e-5):
@@ -181,7 +183,7 @@ class Program(object):
         ch = ch or self.tensor_channels()
         with torch.device('meta'):
             if kind == OpKind.CONV:
-                return str(torch.nn.Conv2d(ch[o.in0], o.cout, o.kh, stride=o.stride, padding=o.pad, groups=max(o.ceil_mode, 1), bias=o.w_bias >= 0))
+                return str(torch.nn.Conv2d(ch[o.in0], o.cout, o.kh if o.kh == o.kw else (o.kh, o.kw), stride=o.stride, padding=o.pad, groups=max(o.ceil_mode, 1), bias=o.w_bias >= 0))
             if kind == OpKind.BATCHNORM:
                 return str(torch.nn.BatchNorm2d(ch[o.in0], eps=float('%.6g' % o.fparam)))
             if kind == OpKind.RELU:
