@@ -111,12 +111,12 @@ class Tape(object):
         return F.relu(b) if (positive and self.with_bias) else b  # whitebox.py:321-324
 
     # -- hooked leaf modules ----------------------------------------------------------------
-    def conv(self, x, prefix, stride=1, pad=0):
+    def conv(self, x, prefix, stride=1, pad=0, groups=1):
         bname = prefix + '.bias'
 
         def fn(ins, positive):
             return F.conv2d(ins[0], self._w(prefix + '.weight', positive), self._b(bname, positive),
-                            stride=stride, padding=pad)
+                            stride=stride, padding=pad, groups=groups)
         return self._record('Conv2d', [x], True, fn)
 
     def linear(self, x, prefix):

@@ -5,7 +5,7 @@ tests/strided_golden_inputs.py, seeded triplet rows."""
 import numpy as np
 import torch
 
-import grouped_nets as GN
+import layer_nets as L
 from oracle import ebp_oracle as O
 from strided_golden_inputs import IN_SHAPE, MODES, NUM_CLASSES, class_seed, image  # noqa: F401
 from xfr_amd import synth
@@ -41,7 +41,7 @@ class OracleTVResnext(object):
     def ebp(self, x, Pn):
         """-> (P list, pooled P[-2])"""
         tape = O.Tape({k: v for k, v in self.sd.items() if v.dtype.is_floating_point}, dtype=self.dtype)
-        b = GN.GroupedTapeBuilder(tape, x)
+        b = L._TapeBuilder(tape, x)
         tape.input(x)
         out = self.bb.forward_on(b, classifier=self.triplet is None)
         if self.triplet is not None:

@@ -3,27 +3,14 @@ grouped kernel and of its per-group packs: row blocks padded from 4, 2 or 1 chan
 GEMM swaps them), K that is no multiple of 4, a strided grouped 1x1 (scatter store), a bias, the phases of a strided grouped 3x3 next to a dense
 scatter, and a batch prefix.
 
-Every net opens with a dense 3x3 + BatchNorm + ReLU and ends in a Linear head; NetCase and the tape builder are tests/layer_nets.py's, the builder
-with a grouped `conv` on top.  oracle/ebp_oracle.py's Tape.conv has no `groups`: the grouped convolution is recorded here through Tape._record with
-F.conv2d(groups = g), as _TapeBuilder.linear records its own op.  `grouped` names the layer the net exists for.
+Every net opens with a dense 3x3 + BatchNorm + ReLU and ends in a Linear head; NetCase and the tape builder are tests/layer_nets.py's, whose `conv`
+takes `groups` (oracle/ebp_oracle.py Tape.conv passes it to F.conv2d).  `grouped` names the layer the net exists for.
 """
-import numpy as np
 import torch
 import torch.nn.functional as F
 
-from layer_nets import NetCase, _TapeBuilder
-from oracle import ebp_oracle as O
-
-
-class GroupedTapeBuilder(_TapeBuilder):
-    def conv(self, x, prefix, cout, k, stride=1, pad=0, bias=True, groups=1):
-        if groups == 1:
-            return _TapeBuilder.conv(self, x, prefix, cout, k, stride=stride, pad=pad, bias=bias)
-        t = self.t
-
-        def fn(ins, positive):
-            return F.conv2d(ins[0], t._w(prefix + '.weight', positive), t._b(prefix + '.bias', positive), stride=stride, padding=pad, groups=groups)
-        return t._record('Conv2d', [x], True, fn)
+import layer_nets as L
+from layer_nets import NetCase
 
 
 def _single(cin0, cout, groups, k, stride, pad, head_hw, bias=False):
@@ -61,48 +48,6 @@ class GroupedCase(NetCase):
         self.grouped = grouped          # (weight prefix, H, W of its input, Cin, cout, groups, kernel, stride, pad)
         self.batch = batch              # the batch the net is in the catalogue for (None: any)
 
-    def params(self):
-        """NetCase.params with (cout, Ci, kh, kw) weights of fan-in Ci kh kw for the grouped layers, calibrated on the grouped tape."""
-        if self._params is not None:
-            return self._params
-        prog = self.program()
-        g = torch.Generator().manual_seed(7919 * self.seed + 3)
-        ch = prog.tensor_channels()
-        names = prog.weight_names
-        sd = {}
-        for o in prog.ops:
-            if o.w_weight < 0:
-                continue
-            wname = names[o.w_weight]
-            if o.kind in (1, 9):                              # CONV, LINEAR
-                ci = ch[o.in0] // max(o.ceil_mode, 1) if o.kind == 1 else ch[o.in0]
-                fan = ci * o.kh * o.kw
-                shape = (o.cout, ci, o.kh, o.kw) if o.kind == 1 else (o.cout, fan)
-                sd[wname] = torch.randn(shape, generator=g) * (1.5 / np.sqrt(fan))
-                if o.w_bias >= 0:
-                    sd[names[o.w_bias]] = 0.1 * torch.randn((o.cout,), generator=g)
-            elif o.kind == 2:                                 # BATCHNORM
-                c = ch[o.in0]
-                sd[wname] = 0.5 + torch.rand((c,), generator=g)
-                sd[names[o.w_bias]] = 0.2 * torch.randn((c,), generator=g)
-                sd[names[o.w_mean]] = torch.zeros((c,))
-                sd[names[o.w_var]] = torch.ones((c,))
-        calib = {}
-        tape = O.Tape(sd, dtype=torch.float64)
-        b = GroupedTapeBuilder(tape, None, calibrate=calib)
-        tape.input(self.inputs(4, seed=99))
-        self.forward(b)
-        sd.update(calib)
-        self._params = sd
-        return sd
-
-    def tape(self, x, dtype=torch.float32, params=None):
-        """The forward on the oracle tape -> (tape, output tensor id); `params` replaces the case's own (a test that edits one)."""
-        tape = O.Tape(self.params() if params is None else params, dtype=dtype)
-        b = GroupedTapeBuilder(tape, x)
-        tape.input(x)
-        return tape, self.forward(b)
-
     def grouped_op(self, prog=None):
         """Index of the grouped layer in the program."""
         prog = prog or self.program()
@@ -133,18 +78,9 @@ BY_NAME = {c.name: c for c in CASES}
 
 
 def phases(case):
-    """The phase launches of a strided grouped KxK layer by the formulas of the phase form (tests/strided_nets.py), with K of ONE group."""
+    """The phase launches of the net's strided grouped KxK layer (layer_nets.phases), with the K of ONE group."""
     _, H, W, cin, cout, G, k, s, p = case.grouped
-    out = []
-    for r in range(min(s, k)):
-        for c in range(min(s, k)):
-            ka, kb = -(-(k - r) // s), -(-(k - c) // s)
-            q0, u0 = max(0, -(-(p - r) // s)), max(0, -(-(p - c) // s))
-            ih0, iw0 = s * q0 + r - p, s * u0 + c - p
-            if ih0 >= H or iw0 >= W:
-                continue
-            out.append(dict(r=r, c=c, ka=ka, kb=kb, K=cout // G * ka * kb, ih0=ih0, iw0=iw0, nq=(H - 1 - ih0) // s + 1, nu=(W - 1 - iw0) // s + 1))
-    return out
+    return L.phases(H, W, cout // G, k, s, p)
 
 
 def grouped_conv_by_slabs(x, w, bias, groups, stride, pad):

@@ -25,8 +25,8 @@ class _TapeBuilder(object):
         self.marks = {}
         tape.pool_args = {}                 # max-pool output tensor -> (kernel, stride, pad, ceil_mode), for pool_windows_clear
 
-    def conv(self, x, prefix, cout, k, stride=1, pad=0, bias=True):
-        return self.t.conv(x, prefix, stride=stride, pad=pad)
+    def conv(self, x, prefix, cout, k, stride=1, pad=0, bias=True, groups=1):
+        return self.t.conv(x, prefix, stride=stride, pad=pad, groups=groups)
 
     def batchnorm(self, x, prefix, eps=1e-5):
         if self.calibrate is not None:
@@ -267,7 +267,8 @@ class NetCase(object):
         return torch.randn((n,) + self.in_shape, generator=g)
 
     def params(self):
-        """Seeded weights (fan-in scaled), BatchNorm affine parameters around one, running statistics from a calibration batch."""
+        """Seeded weights (fan-in scaled; a grouped convolution's are (cout, Cin / groups, kh, kw) -- Program keeps `groups` in the op's ceil_mode
+        slot), BatchNorm affine parameters around one, running statistics from a calibration batch."""
         if self._params is not None:
             return self._params
         prog = self.program()
@@ -280,7 +281,7 @@ class NetCase(object):
                 continue
             wname = names[o.w_weight]
             if o.kind in (1, 9):                              # CONV, LINEAR
-                cin = ch[o.in0]
+                cin = ch[o.in0] // max(o.ceil_mode, 1) if o.kind == 1 else ch[o.in0]
                 fan = cin * o.kh * o.kw
                 shape = (o.cout, cin, o.kh, o.kw) if o.kind == 1 else (o.cout, fan)
                 sd[wname] = torch.randn(shape, generator=g) * (1.5 / np.sqrt(fan))
@@ -301,9 +302,9 @@ class NetCase(object):
         self._params = sd
         return sd
 
-    def tape(self, x, dtype=torch.float32):
-        """The forward on the oracle tape -> (tape, output tensor id)."""
-        tape = O.Tape(self.params(), dtype=dtype)
+    def tape(self, x, dtype=torch.float32, params=None):
+        """The forward on the oracle tape -> (tape, output tensor id); `params` replaces the case's own (a test that edits one)."""
+        tape = O.Tape(self.params() if params is None else params, dtype=dtype)
         b = _TapeBuilder(tape, x)
         tape.input(x)
         return tape, self.forward(b)
@@ -406,3 +407,19 @@ def pool_windows_clear(tape64, rel_gap=1e-6):
         if bool(near.any()):
             bad.append((c.name, int(near.sum())))
     return bad
+
+
+def phases(H, W, k_channels, k, s, p):
+    """The phase launches of a k x k / stride s / pad p convolution's backward-data pass onto an H x W map by the formulas of the phase form
+    (xfr_amd/csrc/plan.hip PhaseRec), k_channels GEMM rows per tap (cout; of ONE group for a grouped layer)
+    -> list of dicts (r, c, ka, kb, K, ih0, iw0, nq, nu)."""
+    out = []
+    for r in range(min(s, k)):
+        for c in range(min(s, k)):
+            ka, kb = -(-(k - r) // s), -(-(k - c) // s)
+            q0, u0 = max(0, -(-(p - r) // s)), max(0, -(-(p - c) // s))
+            ih0, iw0 = s * q0 + r - p, s * u0 + c - p
+            if ih0 >= H or iw0 >= W:
+                continue
+            out.append(dict(r=r, c=c, ka=ka, kb=kb, K=k_channels * ka * kb, ih0=ih0, iw0=iw0, nq=(H - 1 - ih0) // s + 1, nu=(W - 1 - iw0) // s + 1))
+    return out

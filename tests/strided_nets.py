@@ -3,8 +3,10 @@ pass by phases (xfr_amd/csrc/plan.hip PhaseRec): odd and even maps, rows the for
 without a second tap, a stride that leaves phases of one, two and four taps, and the ci-major K order.
 
 Every net opens with a stride-1 3x3 + BatchNorm + ReLU and ends in a Linear head; the builders and NetCase are tests/layer_nets.py's.
-`strided` names the convolution the net exists for, `phases(case)` lists what the formulas of the phase form give for it.
+`strided` names the convolution the net exists for, `phases(case)` lists what the formulas of the phase form
+(layer_nets.phases) give for it.
 """
+import layer_nets as L
 from layer_nets import NetCase
 
 
@@ -78,15 +80,6 @@ BY_NAME = {c.name: c for c in CASES}
 
 
 def phases(case):
-    """The phase launches of the net's strided layer by the formulas of the phase form -> list of dicts (r, c, ka, kb, K, ih0, iw0, nq, nu)."""
+    """The phase launches of the net's strided layer (layer_nets.phases)."""
     _, H, W, cout, k, s, p = case.strided
-    out = []
-    for r in range(min(s, k)):
-        for c in range(min(s, k)):
-            ka, kb = -(-(k - r) // s), -(-(k - c) // s)
-            q0, u0 = max(0, -(-(p - r) // s)), max(0, -(-(p - c) // s))
-            ih0, iw0 = s * q0 + r - p, s * u0 + c - p
-            if ih0 >= H or iw0 >= W:
-                continue
-            out.append(dict(r=r, c=c, ka=ka, kb=kb, K=cout * ka * kb, ih0=ih0, iw0=iw0, nq=(H - 1 - ih0) // s + 1, nu=(W - 1 - iw0) // s + 1))
-    return out
+    return L.phases(H, W, cout, k, s, p)

@@ -3,7 +3,7 @@ kernel (xfr_amd/csrc/conv_depthwise.hip, configuration 14): forward (one launch,
 kernel, Ci and Co swapped), the phases of a strided layer; which launches take that kernel (the profile records), that it agrees with the grouped
 MFMA kernel (fusion-mask bit 10 keeps configuration 13), that images and channels stay apart, and that it repeats its bits.
 
-The rule and its constants are those of test_gpu_grouped_parity.py, unchanged: for every tensor e_eng = max|engine - fp64| / max|fp64|,
+The rule, its constants and the engine / oracle / report plumbing are tests/parity_harness.py's: for every tensor e_eng = max|engine - fp64| / max|fp64|,
 e32 = max|fp32 oracle - fp64| / max|fp64|, and  e_eng <= max(4 * e32, 2e-6); the layerwise rows add the conditioning allowance of a one-element
 prior (layerwise_inputs.one_element_cond).  XFR_LAYER_PARITY_REPORT=<path> writes every measured (e_eng, e32) pair there as JSON.
 Measured on the MI355X over the 1038 comparisons of this file (990 per-firing and pooled, 48 layerwise and weight rows): e32 at most 9.0e-7, e_eng at
@@ -12,8 +12,6 @@ under the floor (the true-weight row of dw3_s2_odd, gate lt0, sample 2: e_eng 7.
 (mult3, all, three images, P[1]: e_eng 7.09e-7 under the 2e-6 floor, 4 x e32 = 1.22e-6).  On dw_tiles, mult3_s2 and mbv1_mini configurations 13 and 14
 both pass with the same margins to the printed digits.  Inputs and seeds are fixed and the kernels deterministic, so the margins repeat run to run.
 """
-import csv
-import json
 import os
 
 import numpy as np
@@ -23,117 +21,32 @@ import torch
 import depthwise_nets as DN
 import grouped_nets as GN
 import layerwise_inputs as W
+import parity_harness as H
+from parity_harness import CFG_DEPTHWISE, CFG_GROUP, KEEP_ON_13, by_cfg as _by_cfg, profiled_sweep as _profiled_sweep
 from xfr_amd.engine import Engine
 
 pytestmark = pytest.mark.gpu
 
-K_RATIO = 4.0
-FLOOR = 2e-6
-CFG_GROUP = 13
-CFG_DEPTHWISE = 14
-KEEP_ON_13 = 1 << 10
-MODES = ('affineonly', 'affineonly_with_prior', 'all', 'norelu')
 # one subtree mode per net for the un-observed schedules (all four across the catalogue)
 SCHEDULE_MODE = {'dw_tiles': 'affineonly_with_prior', 'dw_7x7map': 'norelu', 'dw5_p2': 'all', 'dw7_p3': 'affineonly', 'gdc7': 'norelu', 'dw3_s2_odd': 'all',
                  'dw3_s2_p0': 'affineonly_with_prior', 'dw1_s2': 'affineonly', 'mult3': 'norelu', 'mult3_s2': 'all', 'dw_bias': 'affineonly_with_prior',
                  'dw_prefix': 'norelu', 'pair_g': 'affineonly', 'mbv1_mini': 'affineonly_with_prior'}
-FUSION_SEPARATE = 3 | (1 << 3) | (1 << 4) | (1 << 6) | (1 << 7) | (1 << 8)
-SCHEDULES = [('default', 3, {}), ('default_b4', 4, {}), ('fusion0', 3, {'fusion': 0}), ('fusion_separate', 3, {'fusion': FUSION_SEPARATE}), ('literal_b4', 4, {'lean': 0})]
 NAMES = [c.name for c in DN.CASES]
-REPORT = {}
-_ENGINES = {}
-_ORACLE = {}
+h = H.Harness(print_check=True, print_rule=True)
+_engine, _oracle, _apply, _check, _rule = h.engine, h.oracle, h.apply, h.check, h.rule
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _engines_and_report():
     yield
-    for e in _ENGINES.values():
-        e.close()
-    _ENGINES.clear()
-    path = os.environ.get('XFR_LAYER_PARITY_REPORT')
-    if path:
-        merged = {}
-        if os.path.exists(path):          # the other parity files write the same file earlier in a session: add to it
-            with open(path) as f:
-                merged = json.load(f)
-        merged.update(REPORT)
-        with open(path, 'w') as f:
-            json.dump(merged, f, indent=0, sort_keys=True)
-
-
-def _engine(case, device, max_batch=8):
-    if case.name not in _ENGINES:
-        e = Engine(case.program(), max_batch, device)
-        e.load_weights(case.params())
-        _ENGINES[case.name] = e
-    return _ENGINES[case.name]
-
-
-def _seed(case, n, d, salt=0):
-    g = torch.Generator().manual_seed(31 * case.seed + 7 * n + 1 + salt)
-    return torch.rand((1, n, d), generator=g)
-
-
-def _rel(a, ref):
-    return float((a.double() - ref).abs().max()) / max(float(ref.abs().max()), 1e-300)
-
-
-def _check(bad, key, got, p32, p64):
-    got = got.detach().cpu()
-    if tuple(got.shape) != tuple(p64.shape):
-        bad.append('%s: shape %s vs %s' % (key, tuple(got.shape), tuple(p64.shape)))
-        return
-    if not bool(torch.isfinite(got).all()):
-        bad.append('%s: non-finite values' % key)
-        return
-    e_eng, e32 = _rel(got, p64), _rel(p32, p64)
-    REPORT[key] = (e_eng, e32)
-    print('%s e_eng %.3e e32 %.3e' % (key, e_eng, e32))
-    if e_eng > max(K_RATIO * e32, FLOOR):
-        i = int((got.double() - p64).abs().argmax())
-        idx = np.unravel_index(i, tuple(p64.shape))
-        bad.append('%s: e_eng %.3e > max(%g x e32 %.3e, %g); worst element %s: engine %.9g, fp64 %.9g' % (
-            key, e_eng, K_RATIO, e32, FLOOR, tuple(int(v) for v in idx), float(got.reshape(-1)[i]), float(p64.reshape(-1)[i])))
-
-
-def _oracle(case, n, mode, salt):
-    """(x, seed, P fp32 list, P fp64 list) of one sweep, computed once per session."""
-    key = (case.name, n, mode, salt)
-    if key not in _ORACLE:
-        x = case.inputs(n, seed=salt)
-        tape, out = case.tape(x, torch.float64)
-        d = int(tape.T[out].shape[1])
-        seed = _seed(case, n, d, salt)
-        P64 = tape.backward(out, seed[0], mode, 1e-16)[0]
-        P32 = case.oracle_P(x, seed[0], mode)[0]
-        _ORACLE[key] = (x, seed, P32, P64)
-    return _ORACLE[key]
-
-
-def _apply(eng, sw):
-    eng.set_lean(sw.get('lean', 1))
-    eng.set_epilogue_fusion(sw.get('fusion', 3))
+    h.finish('XFR_LAYER_PARITY_REPORT', merge=True)          # the other parity files write the same file earlier in a session: add to it
 
 
 @pytest.mark.parametrize('name', NAMES)
 def test_every_firing_matches_float64(gpu_device, name):
     """Engine.ebp_firing(k) for every firing k including k == firing_count (the P[-1] gather), four subtree modes, one and three images (three of an
     engine of max_batch 8)."""
-    case = DN.BY_NAME[name]
-    eng = _engine(case, gpu_device)
-    st = case.program().marks['classify']
-    bad = []
-    for n in (1, 3):
-        for mode in MODES:
-            eng.set_mode(mode)
-            x, seed, P32, P64 = _oracle(case, n, mode, 0)
-            nf = eng.firing_count(st)
-            assert nf + 1 == len(P64), (name, nf, len(P64))
-            xd, sd = x.to(gpu_device), seed.to(gpu_device)
-            for k in range(nf + 1):
-                _check(bad, '%s/%s/n%d/P[%d]' % (name, mode, n, k), eng.ebp_firing(xd, st, sd, k), P32[k], P64[k])
-    assert not bad, '\n'.join(bad)
+    H.run_every_firing(h, DN.BY_NAME[name], gpu_device)
 
 
 @pytest.mark.parametrize('name', NAMES)
@@ -141,22 +54,8 @@ def test_schedule_pooled_matches_float64(gpu_device, name):
     """Engine.ebp(want_pooled=True), the un-observed sweep, against the float64 pooled P[-2]: the default schedule at three and four images, fusion
     off, fusion with its optional bits off, the literal schedule at four images, and for the strided nets the phases in a row (bit 9)."""
     case = DN.BY_NAME[name]
-    mode = SCHEDULE_MODE[name]
-    eng = _engine(case, gpu_device)
-    eng.set_mode(mode)
-    st = case.program().marks['classify']
-    bad = []
-    schedules = SCHEDULES + ([('phases_in_a_row', 3, {'fusion': 3 | 512})] if case.grouped[7] == 2 and case.grouped[6] > 1 else [])
-    try:
-        for tag, n, sw in schedules:
-            x, seed, P32, P64 = _oracle(case, n, mode, 1)
-            _apply(eng, sw)
-            _, pooled = eng.ebp(x.to(gpu_device), st, seed.to(gpu_device), want_mwp=False, want_pooled=True)
-            torch.cuda.synchronize()
-            _check(bad, '%s/%s/%s' % (name, mode, tag), pooled[0], P32[-2].sum(dim=1), P64[-2].sum(dim=1))
-    finally:
-        _apply(eng, {})
-    assert not bad, '\n'.join(bad)
+    schedules = H.SCHEDULES + ([('phases_in_a_row', 3, {'fusion': 3 | 512})] if case.grouped[7] == 2 and case.grouped[6] > 1 else [])
+    H.run_schedule_pooled(h, case, gpu_device, SCHEDULE_MODE[name], schedules)
 
 
 @pytest.mark.parametrize('name', ['dw_tiles', 'mult3_s2', 'mbv1_mini'])
@@ -179,24 +78,6 @@ def test_both_kernels_pass_the_float64_rule(gpu_device, name):
     finally:
         _apply(eng, {})
     assert not bad, '\n'.join(bad)
-
-
-def _rule(bad, key, got, ref32, ref64, cond):
-    got, ref64 = got.detach().cpu().double(), torch.as_tensor(np.asarray(ref64)).double()
-    if not bool(torch.isfinite(got).all()):
-        bad.append('%s: non-finite values' % key)
-        return
-    scale = float(ref64.abs().max())
-    if scale == 0:
-        if float(got.abs().max()) != 0:
-            bad.append('%s: the truth is identically zero, the engine has max|.| %.3e' % (key, float(got.abs().max())))
-        return
-    e_eng = float((got - ref64).abs().max()) / scale
-    e32 = float((torch.as_tensor(np.asarray(ref32)).double() - ref64).abs().max()) / scale
-    REPORT[key] = (e_eng, e32, float(cond))
-    print('%s e_eng %.3e e32 %.3e cond %.3e' % (key, e_eng, e32, cond))
-    if e_eng > max(K_RATIO * e32 + cond, FLOOR):
-        bad.append('%s: e_eng %.3e > max(%g x e32 %.3e + cond %.3e, %g)' % (key, e_eng, K_RATIO, e32, cond, FLOOR))
 
 
 @pytest.mark.parametrize('name', ['dw3_s2_odd', 'dw_prefix'])
@@ -255,29 +136,6 @@ def test_true_weight_pass_through_the_depthwise_layer(gpu_device, name):
 
 
 # -- launch records -----------------------------------------------------------------------------------------------------------------------------
-def _profiled_sweep(eng, case, device, path, n, streams):
-    """One un-observed sweep of `streams` seeds with the per-launch profile records appended to `path` -> the records as lists of strings:
-    (Cout, nhalves, K, M, kh, stride, out_stride, relu_in, accumulate, ms, TFLOP/s, cfg)."""
-    st = case.program().marks['classify']
-    x = case.inputs(n, seed=1).to(device)
-    d = int(np.prod(eng.tensor_shape(st)))
-    seed = torch.rand((streams, n, d), generator=torch.Generator().manual_seed(5)).to(device)
-    eng.set_profile(True)
-    eng.profile_csv(path)
-    try:
-        eng.ebp(x, st, seed, want_mwp=False, want_pooled=True)
-        torch.cuda.synchronize()
-    finally:
-        eng.profile_csv(None)
-        eng.set_profile(False)
-    with open(path) as f:
-        return [r for r in csv.reader(f) if r]
-
-
-def _by_cfg(rows, cfg):
-    return [[int(v) for v in r[:9]] for r in rows if int(r[11]) == cfg]
-
-
 def test_depthwise_launch_records(gpu_device, tmp_path):
     """A sweep of dw_bias over two seeds of three images: exactly one forward launch of configuration 14 (W and relu(W) in one launch, K 9,
     M = 3 x 9 x 12), one backward-data launch over both gradient streams (M twice that), and no launch of configuration 13."""

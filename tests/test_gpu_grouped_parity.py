@@ -2,17 +2,15 @@
 W and relu(W) from the same staged input), backward-data (the same kernel, Ci and Co swapped) and, for a strided grouped 3x3, the phases
 (xfr_amd/csrc/conv_group.hip, plan.hip, backward.hip).
 
-The rule and its constants are those of test_gpu_layer_parity.py and test_gpu_strided_parity.py, restated: for every tensor
-e_eng = max|engine - fp64| / max|fp64|, e32 = max|fp32 oracle - fp64| / max|fp64|, and  e_eng <= max(4 * e32, 2e-6).  The layerwise rows use the
-rule of test_gpu_layerwise_parity.py (the same, plus the conditioning allowance of a one-element prior, layerwise_inputs.one_element_cond).
+The rule, its constants and the engine / oracle / report plumbing are tests/parity_harness.py's: for every tensor
+e_eng = max|engine - fp64| / max|fp64|, e32 = max|fp32 oracle - fp64| / max|fp64|, and  e_eng <= max(4 * e32, 2e-6).  The layerwise rows add the
+conditioning allowance of a one-element prior (layerwise_inputs.one_element_cond).
 XFR_LAYER_PARITY_REPORT=<path> writes every measured (e_eng, e32) pair there as JSON.
 Measured on the MI355X over the 677 comparisons of this file (614 per-firing and pooled, 63 layerwise and weight rows): e32 at most 7.4e-7, e_eng at
 most 1.4e-6, e_eng / e32 at most 3.6 (g2_ragged, norelu, three images, P[5]: e_eng 1.33e-6 against 4 x 3.71e-7); the tightest comparison uses 69 % of its
 bound (g2_ragged, norelu, three images, P[4]: e_eng 1.38e-6 under the 2e-6 floor, 4 x e32 = 1.75e-6).  Inputs and seeds are fixed and the kernels
 deterministic, so the margins repeat run to run.
 """
-import csv
-import json
 import os
 
 import numpy as np
@@ -22,114 +20,30 @@ import torch
 import grouped_nets as GN
 import layer_nets as L
 import layerwise_inputs as W
+import parity_harness as H
 from xfr_amd.engine import Engine
 
 pytestmark = pytest.mark.gpu
 
-K_RATIO = 4.0
-FLOOR = 2e-6
-CFG_GROUP = 13
-MODES = ('affineonly', 'affineonly_with_prior', 'all', 'norelu')
 # one subtree mode per net for the un-observed schedules (all four across the catalogue)
 SCHEDULE_MODE = {'g8_c4': 'affineonly_with_prior', 'depthwise': 'norelu', 'dw_mult2': 'all', 'g2_ragged': 'affineonly', 'g3_odd': 'norelu',
                  'g4_1x1_s2': 'all', 'g4_5x5_bias': 'affineonly_with_prior', 'resnext_block': 'affineonly_with_prior', 'g2_prefix': 'norelu'}
-FUSION_SEPARATE = 3 | (1 << 3) | (1 << 4) | (1 << 6) | (1 << 7) | (1 << 8)
-SCHEDULES = [('default', 3, {}), ('default_b4', 4, {}), ('fusion0', 3, {'fusion': 0}), ('fusion_separate', 3, {'fusion': FUSION_SEPARATE}), ('literal_b4', 4, {'lean': 0})]
 NAMES = [c.name for c in GN.CASES]
-REPORT = {}
-_ENGINES = {}
-_ORACLE = {}
+h = H.Harness(print_check=True, print_rule=True)
+_engine, _oracle, _rule = h.engine, h.oracle, h.rule
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _engines_and_report():
     yield
-    for e in _ENGINES.values():
-        e.close()
-    _ENGINES.clear()
-    path = os.environ.get('XFR_LAYER_PARITY_REPORT')
-    if path:
-        merged = {}
-        if os.path.exists(path):          # the other parity files write the same file earlier in a session: add to it
-            with open(path) as f:
-                merged = json.load(f)
-        merged.update(REPORT)
-        with open(path, 'w') as f:
-            json.dump(merged, f, indent=0, sort_keys=True)
-
-
-def _engine(case, device, max_batch=8):
-    if case.name not in _ENGINES:
-        e = Engine(case.program(), max_batch, device)
-        e.load_weights(case.params())
-        _ENGINES[case.name] = e
-    return _ENGINES[case.name]
-
-
-def _seed(case, n, d, salt=0):
-    g = torch.Generator().manual_seed(31 * case.seed + 7 * n + 1 + salt)
-    return torch.rand((1, n, d), generator=g)
-
-
-def _rel(a, ref):
-    return float((a.double() - ref).abs().max()) / max(float(ref.abs().max()), 1e-300)
-
-
-def _check(bad, key, got, p32, p64):
-    got = got.detach().cpu()
-    if tuple(got.shape) != tuple(p64.shape):
-        bad.append('%s: shape %s vs %s' % (key, tuple(got.shape), tuple(p64.shape)))
-        return
-    if not bool(torch.isfinite(got).all()):
-        bad.append('%s: non-finite values' % key)
-        return
-    e_eng, e32 = _rel(got, p64), _rel(p32, p64)
-    REPORT[key] = (e_eng, e32)
-    print('%s e_eng %.3e e32 %.3e' % (key, e_eng, e32))
-    if e_eng > max(K_RATIO * e32, FLOOR):
-        i = int((got.double() - p64).abs().argmax())
-        idx = np.unravel_index(i, tuple(p64.shape))
-        bad.append('%s: e_eng %.3e > max(%g x e32 %.3e, %g); worst element %s: engine %.9g, fp64 %.9g' % (
-            key, e_eng, K_RATIO, e32, FLOOR, tuple(int(v) for v in idx), float(got.reshape(-1)[i]), float(p64.reshape(-1)[i])))
-
-
-def _oracle(case, n, mode, salt):
-    """(x, seed, P fp32 list, P fp64 list) of one sweep, computed once per session."""
-    key = (case.name, n, mode, salt)
-    if key not in _ORACLE:
-        x = case.inputs(n, seed=salt)
-        tape, out = case.tape(x, torch.float64)
-        d = int(tape.T[out].shape[1])
-        seed = _seed(case, n, d, salt)
-        P64 = tape.backward(out, seed[0], mode, 1e-16)[0]
-        P32 = case.oracle_P(x, seed[0], mode)[0]
-        _ORACLE[key] = (x, seed, P32, P64)
-    return _ORACLE[key]
+    h.finish('XFR_LAYER_PARITY_REPORT', merge=True)          # the other parity files write the same file earlier in a session: add to it
 
 
 @pytest.mark.parametrize('name', NAMES)
 def test_every_firing_matches_float64(gpu_device, name):
     """Engine.ebp_firing(k) for every firing k including k == firing_count (the P[-1] gather), four subtree modes, one and three images (three of an
     engine of max_batch 8)."""
-    case = GN.BY_NAME[name]
-    eng = _engine(case, gpu_device)
-    st = case.program().marks['classify']
-    bad = []
-    for n in (1, 3):
-        for mode in MODES:
-            eng.set_mode(mode)
-            x, seed, P32, P64 = _oracle(case, n, mode, 0)
-            nf = eng.firing_count(st)
-            assert nf + 1 == len(P64), (name, nf, len(P64))
-            xd, sd = x.to(gpu_device), seed.to(gpu_device)
-            for k in range(nf + 1):
-                _check(bad, '%s/%s/n%d/P[%d]' % (name, mode, n, k), eng.ebp_firing(xd, st, sd, k), P32[k], P64[k])
-    assert not bad, '\n'.join(bad)
-
-
-def _apply(eng, sw):
-    eng.set_lean(sw.get('lean', 1))
-    eng.set_epilogue_fusion(sw.get('fusion', 3))
+    H.run_every_firing(h, GN.BY_NAME[name], gpu_device)
 
 
 @pytest.mark.parametrize('name', NAMES)
@@ -137,23 +51,8 @@ def test_schedule_pooled_matches_float64(gpu_device, name):
     """Engine.ebp(want_pooled=True), the un-observed sweep, against the float64 pooled P[-2]: the default schedule at three and four images (lean on the
     dense neighbours where it applies, the grouped layer literal), fusion off, fusion with its optional bits off, the literal schedule at four images,
     and for resnext_block the phases in a row (bit 9)."""
-    case = GN.BY_NAME[name]
-    mode = SCHEDULE_MODE[name]
-    eng = _engine(case, gpu_device)
-    eng.set_mode(mode)
-    st = case.program().marks['classify']
-    bad = []
-    schedules = SCHEDULES + ([('phases_in_a_row', 3, {'fusion': 3 | 512})] if name == 'resnext_block' else [])
-    try:
-        for tag, n, sw in schedules:
-            x, seed, P32, P64 = _oracle(case, n, mode, 1)
-            _apply(eng, sw)
-            _, pooled = eng.ebp(x.to(gpu_device), st, seed.to(gpu_device), want_mwp=False, want_pooled=True)
-            torch.cuda.synchronize()
-            _check(bad, '%s/%s/%s' % (name, mode, tag), pooled[0], P32[-2].sum(dim=1), P64[-2].sum(dim=1))
-    finally:
-        _apply(eng, {})
-    assert not bad, '\n'.join(bad)
+    schedules = H.SCHEDULES + ([('phases_in_a_row', 3, {'fusion': 3 | 512})] if name == 'resnext_block' else [])
+    H.run_schedule_pooled(h, GN.BY_NAME[name], gpu_device, SCHEDULE_MODE[name], schedules)
 
 
 def test_groups_do_not_mix(gpu_device):
@@ -220,24 +119,6 @@ def test_two_sweeps_are_bit_identical(gpu_device):
     assert bool(torch.isfinite(runs[0][0]).all()) and float(runs[0][0].abs().max()) > 0
     assert torch.equal(runs[0][0], runs[1][0])
     assert all(torch.equal(u, v) for u, v in zip(runs[0][1], runs[1][1]))
-
-
-def _rule(bad, key, got, ref32, ref64, cond):
-    got, ref64 = got.detach().cpu().double(), torch.as_tensor(np.asarray(ref64)).double()
-    if not bool(torch.isfinite(got).all()):
-        bad.append('%s: non-finite values' % key)
-        return
-    scale = float(ref64.abs().max())
-    if scale == 0:
-        if float(got.abs().max()) != 0:
-            bad.append('%s: the truth is identically zero, the engine has max|.| %.3e' % (key, float(got.abs().max())))
-        return
-    e_eng = float((got - ref64).abs().max()) / scale
-    e32 = float((torch.as_tensor(np.asarray(ref32)).double() - ref64).abs().max()) / scale
-    REPORT[key] = (e_eng, e32, float(cond))
-    print('%s e_eng %.3e e32 %.3e cond %.3e' % (key, e_eng, e32, cond))
-    if e_eng > max(K_RATIO * e32 + cond, FLOOR):
-        bad.append('%s: e_eng %.3e > max(%g x e32 %.3e + cond %.3e, %g)' % (key, e_eng, K_RATIO, e32, cond, FLOOR))
 
 
 @pytest.mark.parametrize('name', ['resnext_block', 'g2_prefix'])
@@ -327,24 +208,6 @@ def test_mini_resnext_matches_live_reference_golden(gpu_device, mode):
         wbn.engine().close()
 
 
-def _profiled_sweep(eng, case, device, path, n, streams):
-    """One un-observed sweep of `streams` seeds with the per-launch profile records appended to `path` -> the records as lists of strings."""
-    st = case.program().marks['classify']
-    x = case.inputs(n, seed=1).to(device)
-    d = int(np.prod(eng.tensor_shape(st)))
-    seed = torch.rand((streams, n, d), generator=torch.Generator().manual_seed(5)).to(device)
-    eng.set_profile(True)
-    eng.profile_csv(path)
-    try:
-        eng.ebp(x, st, seed, want_mwp=False, want_pooled=True)
-        torch.cuda.synchronize()
-    finally:
-        eng.profile_csv(None)
-        eng.set_profile(False)
-    with open(path) as f:
-        return [r for r in csv.reader(f) if r]
-
-
 def test_grouped_launch_counters(gpu_device, tmp_path):
     """The profile records (Cout, nhalves, K, M, kh, stride, out_stride, relu_in, accumulate, ms, TFLOP/s, cfg) of a sweep of g8_c4 over two seeds of
     three images show exactly one launch of configuration 13 for the grouped forward -- W and relu(W) in one launch, M = 3 x 15 x 13 -- and one for its
@@ -352,8 +215,8 @@ def test_grouped_launch_counters(gpu_device, tmp_path):
     case = GN.BY_NAME['g8_c4']
     eng = _engine(case, gpu_device)
     eng.set_mode('norelu')
-    rows = _profiled_sweep(eng, case, gpu_device, str(tmp_path / 'g8_c4.csv'), 3, 2)
-    grouped = [r for r in rows if int(r[11]) == CFG_GROUP]
+    rows = H.profiled_sweep(eng, case, gpu_device, str(tmp_path / 'g8_c4.csv'), 3, 2)
+    grouped = [r for r in rows if int(r[11]) == H.CFG_GROUP]
     assert len(rows) > len(grouped) == 2, rows
     fwd, bwd = grouped
     assert [int(v) for v in fwd[:9]] == [32, 2, 36, 3 * 15 * 13, 3, 1, 1, 0, 0], fwd
@@ -363,7 +226,7 @@ def test_grouped_launch_counters(gpu_device, tmp_path):
         try:
             e.load_weights(other.params())
             e.set_mode('affineonly_with_prior')
-            rows = _profiled_sweep(e, other, gpu_device, str(tmp_path / (other.name + '.csv')), 1, 1)
+            rows = H.profiled_sweep(e, other, gpu_device, str(tmp_path / (other.name + '.csv')), 1, 1)
         finally:
             e.close()
-        assert rows and not [r for r in rows if int(r[11]) == CFG_GROUP], (other.name, rows)
+        assert rows and not [r for r in rows if int(r[11]) == H.CFG_GROUP], (other.name, rows)

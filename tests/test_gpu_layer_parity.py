@@ -5,10 +5,11 @@ shapes that reach them, every float4 / row-pair / fused / global form of the poo
 element by element with the float64 oracle tape.
 
 The rule, for every tensor:  e_eng = max|engine - fp64| / max|fp64|,  e32 = max|fp32 oracle - fp64| / max|fp64| (the reference's own
-precision on the same tensor), and  e_eng <= max(K_RATIO * e32, FLOOR).  Measured on the MI355X over the 1832 comparisons of this file
+precision on the same tensor), and  e_eng <= max(K_RATIO * e32, FLOOR); it is stated in tests/parity_harness.py, with its constants and the engine
+cache and report of this and the other parity files.  Measured on the MI355X over the 1832 comparisons of this file
 (e32 between 5e-8 and 4e-6, e_eng at most 5.5e-6): e_eng / e32 per firing at most 1.0 (pool_odd17) .. 5.6 (halo65), on the pooled P[-2] of the
 schedule matrix at most 1.3 (pool_odd17) .. 5.9 (classifier, lean and two-stream legs); the 24 comparisons above 4 all have e_eng <= 7.7e-7, under
-the floor.  K_RATIO = 4 and FLOOR = 2e-6 (the float32 rounding of O(1) sums of a few thousand terms) were chosen before measuring and kept; the
+the floor.  K_RATIO 4 and FLOOR 2e-6 (the float32 rounding of O(1) sums of a few thousand terms) were chosen before measuring and kept; the
 tightest comparison uses 93 % of its bound (avg_shortcut), the tightest of the pooling nets added later 60 % (avg_shortcut_v4).  All inputs and
 seeds are fixed and the kernels deterministic, so the margins repeat run to run.
 Value-only mutations of the engine (the interpreted chain launch's store, the max-pool VJP, one BatchNorm channel of the positive pass, each
@@ -31,8 +32,6 @@ net, the variants its runs must launch, and the library's launch counters (xfr_e
 or a changed shape rule, fails with the name of the variant that no longer ran instead of quietly testing the scalar kernel.
 """
 import ctypes
-import json
-import os
 
 import numpy as np
 import pytest
@@ -41,65 +40,21 @@ import torch.nn.functional as F
 
 import layer_nets as L
 from oracle import ebp_oracle as O
+from parity_harness import FUSION_SEPARATE, MODES, Harness
 from parity_utils import assert_map_close
 from xfr_amd import _lib
 from xfr_amd.engine import Engine
 
 pytestmark = pytest.mark.gpu
 
-K_RATIO = 4.0
-FLOOR = 2e-6
-MODES = ('affineonly', 'affineonly_with_prior', 'all', 'norelu')
-REPORT = {}
-_ENGINES = {}
+h = Harness(switches=('lean', 'split', 'fusion', 'tail'))
+_engine, _seed, _check, _apply = h.engine, h.seed, h.check, h.apply
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _engines_and_report():
     yield
-    for e in _ENGINES.values():
-        e.close()
-    _ENGINES.clear()
-    path = os.environ.get('XFR_LAYER_PARITY_REPORT')
-    if path:
-        with open(path, 'w') as f:
-            json.dump(REPORT, f, indent=0, sort_keys=True)
-
-
-def _engine(case, device, max_batch=8):
-    key = (case.name, max_batch)
-    if key not in _ENGINES:
-        e = Engine(case.program(), max_batch, device)
-        e.load_weights(case.params())
-        _ENGINES[key] = e
-    return _ENGINES[key]
-
-
-def _seed(case, S, n, d, salt=0):
-    g = torch.Generator().manual_seed(31 * case.seed + 7 * n + S + salt)
-    return torch.rand((S, n, d), generator=g)
-
-
-def _rel(a, ref):
-    return float((a.double() - ref).abs().max()) / max(float(ref.abs().max()), 1e-300)
-
-
-def _check(bad, key, got, p32, p64):
-    """Record (e_eng, e32) under key; append a message to `bad` when the engine misses the rule."""
-    got = got.detach().cpu()
-    if tuple(got.shape) != tuple(p64.shape):
-        bad.append('%s: shape %s vs %s' % (key, tuple(got.shape), tuple(p64.shape)))
-        return
-    if not bool(torch.isfinite(got).all()):
-        bad.append('%s: non-finite values' % key)
-        return
-    e_eng, e32 = _rel(got, p64), _rel(p32, p64)
-    REPORT[key] = (e_eng, e32)
-    if e_eng > max(K_RATIO * e32, FLOOR):
-        i = int((got.double() - p64).abs().argmax())
-        idx = np.unravel_index(i, tuple(p64.shape))
-        bad.append('%s: e_eng %.3e > max(%g x e32 %.3e, %g); worst element %s: engine %.9g, fp64 %.9g' % (
-            key, e_eng, K_RATIO, e32, FLOOR, tuple(int(v) for v in idx), float(got.reshape(-1)[i]), float(p64.reshape(-1)[i])))
+    h.finish('XFR_LAYER_PARITY_REPORT', merge=False)
 
 
 def _assert_ran(name, where, before):
@@ -144,7 +99,6 @@ def test_every_firing_matches_float64(gpu_device, name):
 
 
 # the schedule matrix: (tag, batch, streams, switches); the switches are reset to the engine's defaults after each entry
-FUSION_SEPARATE = 3 | (1 << 3) | (1 << 4) | (1 << 6) | (1 << 7) | (1 << 8)
 SCHEDULES = [
     ('default', 3, 1, {}),
     ('lean_b4', 4, 1, {'lean': 1}), ('lean_b8', 8, 1, {'lean': 1}), ('literal_b4', 4, 1, {'lean': 0}),
@@ -161,13 +115,6 @@ SCHEDULE_MODE = {'stem': 'affineonly_with_prior', 'projection': 'norelu', 'avg_s
                  'avg_generic': 'norelu', 'signed_tail': 'affineonly'}
 NO_LEAN_NETS = ('mfm', 'classifier', 'mfm_pool2', 'encode_tail', 'global_big', 'signed_tail')
 SPLIT_NETS = ('bf16x6', 'halo64', 'halo65')
-
-
-def _apply(eng, sw):
-    eng.set_lean(sw.get('lean', 1))
-    eng.set_split_gemm(sw.get('split', 3))
-    eng.set_epilogue_fusion(sw.get('fusion', 3))
-    eng.set_tail_balance(sw.get('tail', 1))
 
 
 @pytest.mark.parametrize('name', [c.name for c in L.CASES])

@@ -4,7 +4,7 @@ xfr_layerwise_ebp, and the gather / reverse / merge tail of xfr_weighted_subtree
 scatters, global pools, the normalize tail and a signed map, none of which stresnet_mini (test_gpu_subtree.py) has.
 
 The truths come from tests/layerwise_inputs.py (the oracle tape in float64, with the float32 tape as the yardstick of precision); the rule is the one of
-test_gpu_layer_parity.py, for every tensor:  e_eng = max|engine - fp64| / max|fp64| <= max(K_RATIO * e32, FLOOR), K_RATIO = 4, FLOOR = 2e-6, and a map
+tests/parity_harness.py, for every tensor:  e_eng = max|engine - fp64| / max|fp64| <= max(K_RATIO * e32, FLOOR) with K_RATIO 4 and FLOOR 2e-6, and a map
 whose truth is identically zero must be identically zero.  XFR_LAYERWISE_PARITY_REPORT=<path> writes every measured (e_eng, e32, cond) there as JSON.
 
 Layerwise rows are held to  e_eng <= max(K_RATIO * e32 + cond, FLOOR)  instead: with a one-element prior the map is a product of a few individual
@@ -35,7 +35,6 @@ ascending call, the maps of a sweep that is idle for every image held what an ea
 due); layerwise_run now zeroes those rows (subtree.hip).
 """
 import hashlib
-import json
 import os
 import pickle
 import subprocess
@@ -47,12 +46,11 @@ import torch
 
 import layer_nets as L
 import layerwise_inputs as W
+from parity_harness import FLOOR, K_RATIO, Harness
 from xfr_amd.engine import Engine
 
 pytestmark = pytest.mark.gpu
 
-K_RATIO = 4.0           # test_gpu_layer_parity.py's, restated
-FLOOR = 2e-6
 # one subtree mode per net for the parts that need only one (test_gpu_layer_parity.SCHEDULE_MODE, restated: all four across the catalogue)
 NET_MODE = {'stem': 'affineonly_with_prior', 'projection': 'norelu', 'avg_shortcut': 'all', 'bf16x6': 'affineonly_with_prior',
             'halo64': 'affineonly', 'halo65': 'all', 'mfm': 'affineonly', 'classifier': 'norelu', 'valid_wide': 'affineonly_with_prior',
@@ -61,30 +59,15 @@ NET_MODE = {'stem': 'affineonly_with_prior', 'projection': 'norelu', 'avg_shortc
             'avg_generic': 'norelu', 'signed_tail': 'affineonly', 'global_4225': 'all'}
 NAMES = [c.name for c in L.CASES]
 F32, F64 = torch.float32, torch.float64
-REPORT = {}
-REPORT_ALL = bool(os.environ.get('XFR_LAYERWISE_PARITY_REPORT'))
-_ENGINES = {}
+# without the variable a row at or under FLOOR is recorded without its e32, which costs a sweep of the float32 tape (Harness.rule)
+h = Harness(report_all=bool(os.environ.get('XFR_LAYERWISE_PARITY_REPORT')))
+_engine, _rule = h.engine, h.rule
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _engines_and_report():
     yield
-    for e in _ENGINES.values():
-        e.close()
-    _ENGINES.clear()
-    path = os.environ.get('XFR_LAYERWISE_PARITY_REPORT')
-    if path:
-        with open(path, 'w') as f:
-            json.dump(REPORT, f, indent=0, sort_keys=True)
-
-
-def _engine(case, device, max_batch=8):
-    key = (case.name, max_batch)
-    if key not in _ENGINES:
-        e = Engine(case.program(), max_batch, device)
-        e.load_weights(case.params())
-        _ENGINES[key] = e
-    return _ENGINES[key]
+    h.finish('XFR_LAYERWISE_PARITY_REPORT', merge=False)
 
 
 def _setup(name, device):
@@ -92,36 +75,6 @@ def _setup(name, device):
     eng = _engine(case, device)
     st = case.program().marks['classify']
     return case, eng, st, eng.firing_count(st)
-
-
-def _rule(bad, key, got, ref32, ref64, cond=0.0):
-    """Record (e_eng, e32) under key; append a message to `bad` when `got` misses the rule against the float64 truth.  ref32 may be a function: the
-    float32 tape's tensor is only needed where e_eng exceeds FLOOR (or for the report), and costs a sweep of the tape.  cond: the conditioning allowance
-    of a layerwise row (layerwise_inputs.one_element_cond), added to e32."""
-    got = torch.as_tensor(np.asarray(got.detach().cpu() if torch.is_tensor(got) else got)).double()
-    ref64 = torch.as_tensor(np.asarray(ref64)).double()
-    if tuple(got.shape) != tuple(ref64.shape):
-        bad.append('%s: shape %s vs %s' % (key, tuple(got.shape), tuple(ref64.shape)))
-        return
-    if not bool(torch.isfinite(got).all()):
-        bad.append('%s: non-finite values' % key)
-        return
-    scale = float(ref64.abs().max())
-    if scale == 0:
-        if float(got.abs().max()) != 0:
-            bad.append('%s: the truth is identically zero, the engine has max|.| %.3e' % (key, float(got.abs().max())))
-        return
-    e_eng = float((got - ref64).abs().max()) / scale
-    if e_eng <= FLOOR and callable(ref32) and not REPORT_ALL:
-        REPORT[key] = (e_eng, None, float(cond))
-        return
-    ref32 = torch.as_tensor(np.asarray(ref32() if callable(ref32) else ref32)).double()
-    e32 = float((ref32 - ref64).abs().max()) / scale
-    REPORT[key] = (e_eng, e32, float(cond))
-    if e_eng > max(K_RATIO * e32 + cond, FLOOR):
-        i = int((got - ref64).abs().argmax())
-        bad.append('%s: e_eng %.3e > max(%g x e32 %.3e + cond %.3e, %g); worst element %d: engine %.9g, fp64 %.9g' % (
-            key, e_eng, K_RATIO, e32, cond, FLOOR, i, float(got.reshape(-1)[i]), float(ref64.reshape(-1)[i])))
 
 
 @pytest.mark.parametrize('name', NAMES + [W.TIE_CASE.name])
@@ -190,7 +143,7 @@ def test_captures(gpu_device, name):
                             continue
                         want = float(flat[b, int(el[k, b])])
                         err = abs(float(cap[k, b]) - want) / scale
-                        REPORT[key] = (err, e32)
+                        h.report[key] = (err, e32)
                         if not err <= max(K_RATIO * e32, FLOOR):
                             bad.append('%s: element %d: engine %.9g, fp64 %.9g, error / max|P| %.3e > max(4 x %.3e, %g)' % (
                                 key, int(el[k, b]), cap[k, b], want, err, e32, FLOOR))

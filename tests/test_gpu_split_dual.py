@@ -26,12 +26,11 @@ import pytest
 import torch
 
 import layer_nets as L
+from parity_harness import FLOOR, K_RATIO
 from xfr_amd.engine import Engine
 
 pytestmark = pytest.mark.gpu
 
-K_RATIO = 4.0          # tests/test_gpu_layer_parity.py
-FLOOR = 2e-6
 MODE = 'affineonly_with_prior'
 BATCHES = (4, 8)
 

@@ -25,13 +25,12 @@ import pytest
 import torch
 
 import layer_nets as L
+from parity_harness import FLOOR, K_RATIO
 from xfr_amd import _lib
 from xfr_amd.engine import Engine
 
 pytestmark = pytest.mark.gpu
 
-K_RATIO = 4.0
-FLOOR = 2e-6
 # cin, k, pad, cout, S
 PATCH = [(32, 3, 1, 128, 2), (48, 3, 1, 128, 2)]
 SLAB = [(96, 1, 0, 256, 2), (80, 1, 0, 256, 2), (144, 1, 0, 256, 3)]

@@ -2,16 +2,15 @@
 backward-data pass runs as one stride-1 GEMM per phase, scattered onto a zero-filled gradient tensor (xfr_amd/csrc/plan.hip PhaseRec,
 backward.hip bwd_conv_params).
 
-The rule and its constants are those of test_gpu_layer_parity.py, restated: for every tensor  e_eng = max|engine - fp64| / max|fp64|,
-e32 = max|fp32 oracle - fp64| / max|fp64|, and  e_eng <= max(4 * e32, 2e-6).  The layerwise rows use the rule of test_gpu_layerwise_parity.py
-(the same, plus the conditioning allowance of a one-element prior, layerwise_inputs.one_element_cond).
+The rule, its constants and the engine / oracle / report plumbing are tests/parity_harness.py's: for every tensor  e_eng = max|engine - fp64| / max|fp64|,
+e32 = max|fp32 oracle - fp64| / max|fp64|, and  e_eng <= max(4 * e32, 2e-6).  The layerwise rows add the conditioning allowance of a one-element
+prior (layerwise_inputs.one_element_cond).
 XFR_LAYER_PARITY_REPORT=<path> writes every measured (e_eng, e32) pair there as JSON.
 Measured on the MI355X over the 531 per-firing and pooled comparisons of this file: e32 between 8.6e-8 and 2.4e-6, e_eng at most 2.2e-6, e_eng / e32 at
 most 3.9; the tightest comparison uses 98 % of its bound (basic_block, mode all, one image, P[2]: e_eng 2.21e-6 against 4 x 5.64e-7).  Inputs and seeds
 are fixed and the kernels deterministic, so the margins repeat run to run.
 """
 import hashlib
-import json
 import os
 import pickle
 import subprocess
@@ -22,108 +21,30 @@ import pytest
 import torch
 
 import layerwise_inputs as W
+import parity_harness as H
 import strided_nets as S
 from xfr_amd.engine import Engine
 
 pytestmark = pytest.mark.gpu
 
-K_RATIO = 4.0
-FLOOR = 2e-6
-MODES = ('affineonly', 'affineonly_with_prior', 'all', 'norelu')
 # one subtree mode per net for the un-observed schedules (all four across the catalogue)
 SCHEDULE_MODE = {'s2_odd': 'affineonly_with_prior', 's2_valid': 'norelu', 'basic_block': 'all', 'bottleneck_v15': 'affineonly', 's3_5x5': 'norelu',
                  'patch2': 'all', 'mid7': 'affineonly_with_prior'}
-FUSION_SEPARATE = 3 | (1 << 3) | (1 << 4) | (1 << 6) | (1 << 7) | (1 << 8)
-SCHEDULES = [('default', 3, {}), ('default_b4', 4, {}), ('fusion0', 3, {'fusion': 0}), ('fusion_separate', 3, {'fusion': FUSION_SEPARATE}), ('literal_b4', 4, {'lean': 0})]
 NAMES = [c.name for c in S.CASES]
-REPORT = {}
-_ENGINES = {}
-_ORACLE = {}
+h = H.Harness(print_check=True)
+_engine, _oracle, _rule = h.engine, h.oracle, h.rule
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _engines_and_report():
     yield
-    for e in _ENGINES.values():
-        e.close()
-    _ENGINES.clear()
-    path = os.environ.get('XFR_LAYER_PARITY_REPORT')
-    if path:
-        merged = {}
-        if os.path.exists(path):          # test_gpu_layer_parity.py writes the same file earlier in a session: add to it
-            with open(path) as f:
-                merged = json.load(f)
-        merged.update(REPORT)
-        with open(path, 'w') as f:
-            json.dump(merged, f, indent=0, sort_keys=True)
-
-
-def _engine(case, device, max_batch=8):
-    if case.name not in _ENGINES:
-        e = Engine(case.program(), max_batch, device)
-        e.load_weights(case.params())
-        _ENGINES[case.name] = e
-    return _ENGINES[case.name]
-
-
-def _seed(case, n, d, salt=0):
-    g = torch.Generator().manual_seed(31 * case.seed + 7 * n + 1 + salt)
-    return torch.rand((1, n, d), generator=g)
-
-
-def _rel(a, ref):
-    return float((a.double() - ref).abs().max()) / max(float(ref.abs().max()), 1e-300)
-
-
-def _check(bad, key, got, p32, p64):
-    got = got.detach().cpu()
-    if tuple(got.shape) != tuple(p64.shape):
-        bad.append('%s: shape %s vs %s' % (key, tuple(got.shape), tuple(p64.shape)))
-        return
-    if not bool(torch.isfinite(got).all()):
-        bad.append('%s: non-finite values' % key)
-        return
-    e_eng, e32 = _rel(got, p64), _rel(p32, p64)
-    REPORT[key] = (e_eng, e32)
-    print('%s e_eng %.3e e32 %.3e' % (key, e_eng, e32))
-    if e_eng > max(K_RATIO * e32, FLOOR):
-        i = int((got.double() - p64).abs().argmax())
-        idx = np.unravel_index(i, tuple(p64.shape))
-        bad.append('%s: e_eng %.3e > max(%g x e32 %.3e, %g); worst element %s: engine %.9g, fp64 %.9g' % (
-            key, e_eng, K_RATIO, e32, FLOOR, tuple(int(v) for v in idx), float(got.reshape(-1)[i]), float(p64.reshape(-1)[i])))
-
-
-def _oracle(case, n, mode, salt):
-    """(x, seed, P fp32 list, P fp64 list) of one sweep, computed once per session."""
-    key = (case.name, n, mode, salt)
-    if key not in _ORACLE:
-        x = case.inputs(n, seed=salt)
-        tape, out = case.tape(x, torch.float64)
-        d = int(tape.T[out].shape[1])
-        seed = _seed(case, n, d, salt)
-        P64 = tape.backward(out, seed[0], mode, 1e-16)[0]
-        P32 = case.oracle_P(x, seed[0], mode)[0]
-        _ORACLE[key] = (x, seed, P32, P64)
-    return _ORACLE[key]
+    h.finish('XFR_LAYER_PARITY_REPORT', merge=True)          # test_gpu_layer_parity.py writes the same file earlier in a session: add to it
 
 
 @pytest.mark.parametrize('name', NAMES)
 def test_every_firing_matches_float64(gpu_device, name):
     """Engine.ebp_firing(k) for every firing k including k == firing_count (the P[-1] gather), four subtree modes, one and three images."""
-    case = S.BY_NAME[name]
-    eng = _engine(case, gpu_device)
-    st = case.program().marks['classify']
-    bad = []
-    for n in (1, 3):
-        for mode in MODES:
-            eng.set_mode(mode)
-            x, seed, P32, P64 = _oracle(case, n, mode, 0)
-            nf = eng.firing_count(st)
-            assert nf + 1 == len(P64), (name, nf, len(P64))
-            xd, sd = x.to(gpu_device), seed.to(gpu_device)
-            for k in range(nf + 1):
-                _check(bad, '%s/%s/n%d/P[%d]' % (name, mode, n, k), eng.ebp_firing(xd, st, sd, k), P32[k], P64[k])
-    assert not bad, '\n'.join(bad)
+    H.run_every_firing(h, S.BY_NAME[name], gpu_device)
 
 
 def test_unread_rows_get_zero_gradient(gpu_device):
@@ -146,48 +67,11 @@ def test_unread_rows_get_zero_gradient(gpu_device):
     assert hits >= 1
 
 
-def _apply(eng, sw):
-    eng.set_lean(sw.get('lean', 1))
-    eng.set_epilogue_fusion(sw.get('fusion', 3))
-
-
 @pytest.mark.parametrize('name', NAMES)
 def test_schedule_pooled_matches_float64(gpu_device, name):
     """Engine.ebp(want_pooled=True), the un-observed sweep, against the float64 pooled P[-2]: the default schedule at three and four images (lean where
     it applies), fusion off, fusion with its optional bits off, and the literal schedule at four images."""
-    case = S.BY_NAME[name]
-    mode = SCHEDULE_MODE[name]
-    eng = _engine(case, gpu_device)
-    eng.set_mode(mode)
-    st = case.program().marks['classify']
-    bad = []
-    try:
-        for tag, n, sw in SCHEDULES:
-            x, seed, P32, P64 = _oracle(case, n, mode, 1)
-            _apply(eng, sw)
-            _, pooled = eng.ebp(x.to(gpu_device), st, seed.to(gpu_device), want_mwp=False, want_pooled=True)
-            torch.cuda.synchronize()
-            _check(bad, '%s/%s/%s' % (name, mode, tag), pooled[0], P32[-2].sum(dim=1), P64[-2].sum(dim=1))
-    finally:
-        _apply(eng, {})
-    assert not bad, '\n'.join(bad)
-
-
-def _rule(bad, key, got, ref32, ref64, cond):
-    got, ref64 = got.detach().cpu().double(), torch.as_tensor(np.asarray(ref64)).double()
-    if not bool(torch.isfinite(got).all()):
-        bad.append('%s: non-finite values' % key)
-        return
-    scale = float(ref64.abs().max())
-    if scale == 0:
-        if float(got.abs().max()) != 0:
-            bad.append('%s: the truth is identically zero, the engine has max|.| %.3e' % (key, float(got.abs().max())))
-        return
-    e_eng = float((got - ref64).abs().max()) / scale
-    e32 = float((torch.as_tensor(np.asarray(ref32)).double() - ref64).abs().max()) / scale
-    REPORT[key] = (e_eng, e32, float(cond))
-    if e_eng > max(K_RATIO * e32 + cond, FLOOR):
-        bad.append('%s: e_eng %.3e > max(%g x e32 %.3e + cond %.3e, %g)' % (key, e_eng, K_RATIO, e32, cond, FLOOR))
+    H.run_schedule_pooled(h, S.BY_NAME[name], gpu_device, SCHEDULE_MODE[name], H.SCHEDULES)
 
 
 def test_layerwise_priors_around_the_strided_layer(gpu_device):

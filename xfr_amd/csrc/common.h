@@ -352,11 +352,21 @@ inline size_t group_pack_index(int g, int co_local, int k, int co_per_group, int
 {
     return (((size_t)g * group_row_blocks(co_per_group) + co_local / GROUP_ROWS) * group_pack_rows(k_per_group) + k) * GROUP_ROWS + co_local % GROUP_ROWS;
 }
+// What launch_conv_group and launch_conv_depthwise both ask of a launch.  (In a dense output the sample index and pixel of column m are m itself: the
+// launch must not cover more pixels than the tensor has.)
+inline bool grouped_launch_contract_ok(const ConvParams& p)
+{
+    const int G = p.groups;
+    if (G < 2 || p.Cin % G || p.CoutTot % G || p.chain.n > 0 || p.dualacc || p.co_pair || p.tap_major || p.as_strided || p.pair_m) return false;
+    if (p.nhalves < 1 || p.nhalves > 2 || (p.nhalves == 2 && (!p.w_pos || !p.out1)) || !p.w || !p.in || !p.out0 || p.M <= 0) return false;
+    if (p.K != p.Cin / G * p.kh * p.kw) return false;
+    return p.out_stride >= 1 && (p.OH - 1) * p.out_stride < p.out_H && (p.OW - 1) * p.out_stride < p.out_W && p.NB <= p.in_nb && p.NB <= p.out_nb;
+}
 bool launch_conv_group(const ConvParams& p, hipStream_t s);
 long conv_group_launches();
 // Depthwise launches (conv_depthwise.hip, configuration 14): the grouped launches with min(Cin, CoutTot) / groups == 1 -- a depthwise layer's forward
 // (any channel multiplier), its backward-data pass, the phases of a strided one -- in fp32 on the vector ALU from one LDS staging of the input.  The
-// contract and the packs are launch_conv_group's.  false: not a launch this kernel takes (see the caps in its head comment), nothing was launched:
+// contract (grouped_launch_contract_ok) and the packs are launch_conv_group's.  false: not a launch this kernel takes (see the caps in its head comment), nothing was launched:
 // the caller goes on to launch_conv_group
 bool launch_conv_depthwise(const ConvParams& p, hipStream_t s);
 long conv_depthwise_launches();

@@ -1,7 +1,7 @@
 // conv_depthwise.hip -- depthwise launches on the vector ALU, configuration 14: the grouped launches (ConvParams::groups > 1) with one input or one
 // output channel per group, min(Ci, Co) == 1 for Ci = Cin / groups, Co = CoutTot / groups.  That is the forward of a depthwise layer with channel
 // multiplier m (Ci 1, Co m), its backward-data pass (Ci m, Co 1, K = m kh kw) and the phases of a strided one.  The contract is launch_conv_group's
-// field by field (common.h): the per-group packs through group_pack_index (one row block, K ordered (ci, kh, kw)), one or two halves (W and relu(W)
+// field by field (common.h, both launchers open with grouped_launch_contract_ok): the per-group packs through group_pack_index (one row block, K ordered (ci, kh, kw)), one or two halves (W and relu(W)
 // from the same staging into out0 / out1 with bias / bias_pos), relu_in, stride, pad, pad_dw, the batch prefix (NB <= in_nb, out_nb), accumulate and
 // the scattered store (out_stride, out_H, out_W, a pre-offset out0).  On the MFMA kernel such a group fills one of 16 rows of a row block and fetches
 // every X element once per tap; here a few FLOPs per byte run as plain fp32 FMAs next to the loads.
@@ -248,14 +248,11 @@ long conv_depthwise_launches() { return g_launches.load(); }
 
 bool launch_conv_depthwise(const ConvParams& p, hipStream_t s)
 {
-    const int G = p.groups;
-    if (G < 2 || p.Cin % G || p.CoutTot % G || p.chain.n > 0 || p.dualacc || p.co_pair || p.tap_major || p.as_strided || p.pair_m) return false;
-    if (p.nhalves < 1 || p.nhalves > 2 || (p.nhalves == 2 && (!p.w_pos || !p.out1)) || !p.w || !p.in || !p.out0 || p.M <= 0) return false;
-    const int Ci = p.Cin / G, Co = p.CoutTot / G;
+    if (!grouped_launch_contract_ok(p)) return false;
+    const int G = p.groups, Ci = p.Cin / G, Co = p.CoutTot / G;
     if ((Ci != 1 && Co != 1) || Ci > MAX_CH || Co > MAX_CH) return false;
-    if (p.kh < 1 || p.kw < 1 || p.kh > MAX_TAP || p.kw > MAX_TAP || p.K != Ci * p.kh * p.kw || p.stride < 1) return false;
+    if (p.kh < 1 || p.kw < 1 || p.kh > MAX_TAP || p.kw > MAX_TAP || p.stride < 1) return false;
     if (p.OH < 1 || p.OW < 1 || p.H < 1 || p.W < 1 || p.M != p.NB * p.OH * p.OW) return false;
-    if (p.out_stride < 1 || (p.OH - 1) * p.out_stride >= p.out_H || (p.OW - 1) * p.out_stride >= p.out_W || p.NB > p.in_nb || p.NB > p.out_nb) return false;
     if (G > 65535) return false;
     const long HW = (long)p.H * p.W, ohw = (long)p.OH * p.OW;
     const long Wp = (long)(p.OW - 1) * p.stride + p.kw;

@@ -198,13 +198,8 @@ long conv_group_launches() { return g_launches.load(); }
 
 bool launch_conv_group(const ConvParams& p, hipStream_t s)
 {
-    const int G = p.groups;
-    if (G < 2 || p.Cin % G || p.CoutTot % G || p.chain.n > 0 || p.dualacc || p.co_pair || p.tap_major || p.as_strided || p.pair_m) return false;
-    if (p.nhalves < 1 || p.nhalves > 2 || (p.nhalves == 2 && (!p.w_pos || !p.out1)) || !p.w || !p.in || !p.out0 || p.M <= 0) return false;
-    const int Ci = p.Cin / G, Co = p.CoutTot / G;
-    if (p.K != Ci * p.kh * p.kw) return false;
-    // in a dense output the sample index and pixel of column m are m itself: the launch must not cover more pixels than the tensor has
-    if (p.out_stride < 1 || (p.OH - 1) * p.out_stride >= p.out_H || (p.OW - 1) * p.out_stride >= p.out_W || p.NB > p.in_nb || p.NB > p.out_nb) return false;
+    if (!grouped_launch_contract_ok(p)) return false;
+    const int G = p.groups, Ci = p.Cin / G, Co = p.CoutTot / G;
     const int nrb = group_row_blocks(Co);
     const int RB = nrb >= 4 ? 4 : (nrb >= 2 ? 2 : 1);
     const int chunks = (nrb + RB - 1) / RB;

@@ -32,36 +32,29 @@ static xfr_status fwd_op(xfr_engine* e, int k, int B, bool want_pos, hipStream_t
 static xfr_status pos_op(xfr_engine* e, int k, int B, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------------
+// the event pair (and record slot) the next profiled launch takes; it counts as used once that launch is recorded
+static xfr_status next_event_pair(xfr_engine* e, std::pair<Event, Event>*& ev)
+{
+    if (e->ev_used == e->ev_pool.size()) {
+        Event a, b;
+        XFR_TRY(a.create(true));
+        XFR_TRY(b.create(true));
+        e->ev_pool.emplace_back(std::move(a), std::move(b));
+    }
+    if (e->ev_params.size() < e->ev_pool.size()) { e->ev_params.resize(e->ev_pool.size()); e->ev_cfg.resize(e->ev_pool.size()); }
+    ev = &e->ev_pool[e->ev_used];
+    return XFR_OK;
+}
+
 xfr_status run_conv(xfr_engine* e, const ConvParams& p_in, hipStream_t s)
 {
-    if (p_in.groups > 1) {
-        // a grouped layer (conv_group.hip, configuration 13; a depthwise launch: conv_depthwise.hip, configuration 14): no chain, no bf16x6, no tail balancing
-        if (e->profile_on) {
-            if (e->ev_used == e->ev_pool.size()) {
-                Event a, b;
-                XFR_TRY(a.create(true));
-                XFR_TRY(b.create(true));
-                e->ev_pool.emplace_back(std::move(a), std::move(b));
-            }
-            if (e->ev_params.size() < e->ev_pool.size()) { e->ev_params.resize(e->ev_pool.size()); e->ev_cfg.resize(e->ev_pool.size()); }
-            HIP_TRY(hipEventRecord(e->ev_pool[e->ev_used].first, s));
-        }
-        const bool dw = e->depthwise_valu && launch_conv_depthwise(p_in, s);
-        if (!dw && !launch_conv_group(p_in, s)) return fail(XFR_STATE_ERROR, "a grouped convolution launch (groups %d) the grouped kernel does not take", p_in.groups);
-        if (e->profile_on) {
-            e->ev_params[e->ev_used] = p_in;
-            e->ev_cfg[e->ev_used] = dw ? CFG_DEPTHWISE : CFG_GROUP;
-            HIP_TRY(hipEventRecord(e->ev_pool[e->ev_used++].second, s));
-            e->prof_flops += 2.0 * (double)p_in.K * (double)p_in.M * (double)p_in.CoutTot * (double)p_in.nhalves;      // K of one group
-        }
-        return XFR_OK;
-    }
+    // a grouped layer (conv_group.hip, configuration 13; a depthwise launch: conv_depthwise.hip, configuration 14): no chain, no bf16x6, no tail balancing
+    const bool grouped = p_in.groups > 1;
     ConvParams p = p_in;
-    p.chain_interpret = e->interpret_chains ? 1 : 0;
+    p.chain_interpret = e->interpret_chains ? 1 : 0;      // (these three: read by the dense kernels only)
     p.split_ok = (e->split_mask & (p.bwd ? 2 : 1)) ? (e->split_any_grid ? 2 : 1) : 0;
-    p.tail_force = 1;
-    if (e->tail_balance) {
-        p.tail_force = 0;
+    p.tail_force = e->tail_balance ? 0 : 1;
+    if (!grouped && e->tail_balance) {
         int k = 0;
         while (k < e->n_tail_ws && e->tail_ws[k].s != s) ++k;
         if (k == e->n_tail_ws && k < 8) {
@@ -79,28 +72,30 @@ xfr_status run_conv(xfr_engine* e, const ConvParams& p_in, hipStream_t s)
             p.tail_ws_bytes = XFR_TAIL_WS_BYTES;
         }
     }
+    std::pair<Event, Event>* ev = nullptr;
     if (e->profile_on) {
-        if (e->ev_used == e->ev_pool.size()) {
-            Event a, b;
-            XFR_TRY(a.create(true));
-            XFR_TRY(b.create(true));
-            e->ev_pool.emplace_back(std::move(a), std::move(b));
-        }
-        if (e->ev_params.size() < e->ev_pool.size()) { e->ev_params.resize(e->ev_pool.size()); e->ev_cfg.resize(e->ev_pool.size()); }
-        const int why = conv_gemm_cannot_launch(p);
-        if (why) return fail(XFR_STATE_ERROR, "%s", conv_gemm_refusal(why));          // nothing launched: no event pair, no record
+        if (const int why = grouped ? 0 : conv_gemm_cannot_launch(p)) return fail(XFR_STATE_ERROR, "%s", conv_gemm_refusal(why));          // nothing launched: no event pair, no record
         // (HIP events misread the FIRST GEMM of a profiled run -- 0.87 ms for a 0.37 ms stem in round 3, 1.03 ms with a stream synchronise in
         // front of it in round 4: the start event is stamped on a queue that has just been idle.  The per-shape tables of profiles/ therefore
         // also come from the kernels' own stamps: bench.py --serial --launch-log-csv, profiles/layer_table.py.)
-        e->ev_params[e->ev_used] = p;
-        auto& ev = e->ev_pool[e->ev_used++];
-        HIP_TRY(hipEventRecord(ev.first, s));
-        launch_conv_gemm(p, s);
-        e->ev_cfg[e->ev_used - 1] = conv_gemm_last_cfg();
-        HIP_TRY(hipEventRecord(ev.second, s));
-        e->prof_flops += 2.0 * (double)(p.K_logical ? p.K_logical : p.K) * (double)p.M * (double)p.CoutTot * (double)(p.dualacc ? 2 : p.nhalves);
-    } else if (!launch_conv_gemm(p, s)) {
+        XFR_TRY(next_event_pair(e, ev));
+        HIP_TRY(hipEventRecord(ev->first, s));
+    }
+    int cfg;
+    if (grouped) {
+        cfg = (e->depthwise_valu && launch_conv_depthwise(p, s)) ? CFG_DEPTHWISE : CFG_GROUP;
+        if (cfg == CFG_GROUP && !launch_conv_group(p, s)) return fail(XFR_STATE_ERROR, "a grouped convolution launch (groups %d) the grouped kernel does not take", p.groups);
+    } else if (launch_conv_gemm(p, s)) {
+        cfg = conv_gemm_last_cfg();
+    } else {
         return fail(XFR_STATE_ERROR, "%s", conv_gemm_refusal(conv_gemm_cannot_launch(p)));
+    }
+    if (ev) {
+        e->ev_params[e->ev_used] = p;
+        e->ev_cfg[e->ev_used++] = cfg;          // the configuration that ran
+        HIP_TRY(hipEventRecord(ev->second, s));
+        // (a grouped launch has no dualacc, and its K_logical is its K, the K of ONE group -- conv_geometry: Kf == K, plan.hip -- or 0: bwd_conv_params)
+        e->prof_flops += 2.0 * (double)(p.K_logical ? p.K_logical : p.K) * (double)p.M * (double)p.CoutTot * (double)(p.dualacc ? 2 : p.nhalves);
     }
     return XFR_OK;
 }
