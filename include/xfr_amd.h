@@ -834,6 +834,34 @@ xfr_status xfr_debug_conv(const float* in_dev, const float* w_host, const float*
                           int32_t h, int32_t w, int32_t nb, int32_t cout, int32_t kh, int32_t kw, int32_t stride,
                           int32_t pad, int32_t relu_in, int32_t cfg, int32_t reps, float* ms_out);
 
+/* Test hook: ONE grouped-convolution launch (Conv2d(groups = G): configuration 13, the grouped MFMA kernel, or 14, the depthwise kernel) outside any
+ * engine, on the caller's pointers as the engine's forward, backward-data and phase launches make them.  Additive entry point, ABI version 7.
+ *   in_dev               [cin][in_nb][h][w] float32; the first nb images of every channel are read
+ *   out0_dev, out1_dev   [cout][out_nb][out_H][out_W]; the first nb images are written.  The pointers are taken as they come: a caller that wants
+ *                        a phase's pre-offset target, or a pointer that is not 16-byte aligned, passes it so.  out1_dev: the relu(W) half, read only
+ *                        when nhalves == 2
+ *   w_host               [cout][cin / groups][kh][kw], PyTorch's layout; the call builds the per-group pack and, for nhalves == 2, the pack of
+ *                        max(w, 0).  A backward-data or phase launch is a forward launch to the kernels: its caller prepares the flipped,
+ *                        transposed or phase-sliced weight
+ *   bias_host, bias_pos_host   NULL or cout floats, added to out0 / out1
+ *   pad, pad_dw          rows are padded by pad, columns by pad + pad_dw on both sides: OH = (h + 2 pad - kh) / stride + 1,
+ *                        OW = (w + 2 (pad + pad_dw) - kw) / stride + 1, M = nb OH OW, K = cin / groups * kh * kw
+ *   accumulate           1: out += result
+ *   out_stride, out_H, out_W   output (oh, ow) lands at (oh out_stride, ow out_stride) of an out_H x out_W map; out_H = out_W = 0: the dense
+ *                        OH x OW map (out_stride 1)
+ *   cfg                  13: the grouped kernel; 14: the depthwise kernel, XFR_UNSUPPORTED_LAYER with nothing launched where it does not take the
+ *                        launch; 0: as the engine picks -- the depthwise kernel where it takes the launch, else the grouped one
+ *   cfg_out, tile_out    NULL, or where the configuration that ran and the depthwise kernel's tile (outputs per workgroup; 0 for configuration 13) go
+ * One launch on the null stream, then the call WAITS for it; nothing is timed.  XFR_INVALID_ARG before any device call, with a text naming the
+ * values: a null in_dev, out0_dev or w_host; nhalves outside 1 .. 2 or two halves without out1_dev; a cfg other than 0, 13, 14; fewer than two
+ * groups or groups that do not divide cin and cout; a size, tap count or stride below 1; nb below 1 or above in_nb or out_nb; flags other than 0 / 1;
+ * padding that leaves no output; a target map that does not hold the strided outputs; a tensor of 2^31 elements or more. */
+xfr_status XFR_EX xfr_debug_conv_grouped(const float* in_dev, float* out0_dev, float* out1_dev, const float* w_host, const float* bias_host,
+                                         const float* bias_pos_host, int32_t cin, int32_t cout, int32_t groups, int32_t h, int32_t w, int32_t nb,
+                                         int32_t in_nb, int32_t out_nb, int32_t kh, int32_t kw, int32_t stride, int32_t pad, int32_t pad_dw,
+                                         int32_t relu_in, int32_t nhalves, int32_t accumulate, int32_t out_stride, int32_t out_H, int32_t out_W,
+                                         int32_t cfg, int32_t* cfg_out, int32_t* tile_out);
+
 /* Tuning hook: while stamps_dev is non-NULL, every GEMM launch of this process records, per wave, 8 64-bit words at
  * stamps_dev[(block * 4 + wave) * 8]: s_memrealtime (100 MHz) at kernel entry / first operands landed / K loop done / epilogue entered / exit,
  * then HW_ID, XCC_ID, and the wave's life in shader-clock cycles (s_memtime; with the 100 MHz stamps: the effective clock) (tools/conv_sweep.py --stamps draws a launch's timeline from them).  The buffer holds

@@ -1,5 +1,5 @@
 """The float64 parity rule of the layer catalogues and the plumbing around it, stated once for test_gpu_layer_parity.py, test_gpu_layerwise_parity.py,
-test_gpu_strided_parity.py, test_gpu_grouped_parity.py and test_gpu_depthwise_parity.py.
+test_gpu_strided_parity.py, test_gpu_grouped_parity.py and test_gpu_depthwise_parity.py; test_gpu_grouped_direct.py holds single launches to the same rule.
 
 The rule, for every tensor:  e_eng = max|engine - fp64| / max|fp64|,  e32 = max|fp32 oracle - fp64| / max|fp64| (the reference's own precision on the
 same tensor), and  e_eng <= max(K_RATIO * e32 + cond, FLOOR);  cond is zero except on layerwise rows (layerwise_inputs.one_element_cond).  K_RATIO and
@@ -25,6 +25,7 @@ SCHEDULES = [('default', 3, {}), ('default_b4', 4, {}), ('fusion0', 3, {'fusion'
 CFG_GROUP = 13              # the profile records' configuration of the grouped MFMA kernel
 CFG_DEPTHWISE = 14          # ... of the depthwise kernel
 KEEP_ON_13 = 1 << 10        # the fusion-mask bit that keeps depthwise launches on configuration 13
+_written = set()            # the report files this process has written (Harness.finish)
 _SETTERS = {'lean': ('set_lean', 1), 'split': ('set_split_gemm', 3), 'fusion': ('set_epilogue_fusion', 3), 'tail': ('set_tail_balance', 1)}
 
 
@@ -69,16 +70,18 @@ class Harness(object):
             getattr(eng, setter)(sw.get(name, default))
 
     def finish(self, env_var, merge):
-        """Close the engines; write the report to the file `env_var` names, on top of what an earlier module of the session left there if `merge`."""
+        """Close the engines; write the report to the file `env_var` names, on top of what is there if `merge`.  Whatever `merge` says, what an earlier
+        module of THIS session wrote there stays: the module that starts the file afresh (merge False) does not come first in every collection order."""
         for e in self.engines.values():
             e.close()
         self.engines.clear()
         path = os.environ.get(env_var)
         if path:
             out = {}
-            if merge and os.path.exists(path):
+            if (merge or os.path.abspath(path) in _written) and os.path.exists(path):
                 with open(path) as f:
                     out = json.load(f)
+            _written.add(os.path.abspath(path))
             out.update(self.report)
             with open(path, 'w') as f:
                 json.dump(out, f, indent=0, sort_keys=True)

@@ -84,6 +84,54 @@ def test_debug_contrast_tail_refuses_before_any_device_call():
     refused(b'contrast_dev 0xffffc4 (64 bytes) overlaps p_dev', o=p - 60)
 
 
+def test_debug_conv_grouped_refuses_before_any_device_call():
+    """xfr_debug_conv_grouped checks its arguments before it allocates, copies or launches, so the refusals show without a device: the device pointers
+    are numbers that are never followed, the weight is real host memory that is never read.  (tests/test_gpu_grouped_direct.py runs the launches.)"""
+    lib = _lib.load()
+    w = (ctypes.c_float * (8 * 2 * 9))()
+    x, o0, o1 = 1 << 24, 1 << 28, 1 << 29
+    good = dict(x=x, o0=o0, o1=o1, w=ctypes.addressof(w), cin=8, cout=8, groups=4, h=9, wd=8, nb=2, in_nb=2, out_nb=2, kh=3, kw=3, stride=1, pad=1, pad_dw=0,
+                relu_in=0, nhalves=2, accumulate=0, out_stride=1, out_H=0, out_W=0, cfg=0)
+
+    def refused(text, **kw):
+        a = dict(good, **kw)
+        cfg_out, tile_out = ctypes.c_int32(-1), ctypes.c_int32(-1)
+        st = lib.xfr_debug_conv_grouped(a['x'], a['o0'], a['o1'], a['w'], None, None, a['cin'], a['cout'], a['groups'], a['h'], a['wd'], a['nb'], a['in_nb'],
+                                        a['out_nb'], a['kh'], a['kw'], a['stride'], a['pad'], a['pad_dw'], a['relu_in'], a['nhalves'], a['accumulate'],
+                                        a['out_stride'], a['out_H'], a['out_W'], a['cfg'], ctypes.byref(cfg_out), ctypes.byref(tile_out))
+        assert st == _lib.XFR_INVALID_ARG, (text, st)
+        assert text in lib.xfr_last_error(), lib.xfr_last_error()
+        assert (cfg_out.value, tile_out.value) == (0, 0)
+
+    refused(b'null argument', x=None)
+    refused(b'null argument', o0=None)
+    refused(b'null argument', w=None)
+    refused(b'nhalves 2, out1_dev (nil)', o1=None)
+    refused(b'nhalves 3', nhalves=3)
+    refused(b'nhalves 0', nhalves=0)
+    refused(b'cfg 12', cfg=12)
+    refused(b'cfg 9', cfg=9)
+    refused(b'cin 8, cout 8, groups 1', groups=1)
+    refused(b'cin 8, cout 8, groups 3', groups=3)
+    refused(b'cin 8, cout 6, groups 4', cout=6)
+    refused(b'h 0, w 8', h=0)
+    refused(b'kh 3, kw 0', kw=0)
+    refused(b'stride 0', stride=0)
+    refused(b'nb 0, in_nb 2, out_nb 2', nb=0)
+    refused(b'nb 3, in_nb 2, out_nb 4', nb=3, out_nb=4)
+    refused(b'nb 3, in_nb 4, out_nb 2', nb=3, in_nb=4)
+    refused(b'relu_in 2, accumulate 0', relu_in=2)
+    refused(b'relu_in 0, accumulate -1', accumulate=-1)
+    refused(b'pad -4, pad_dw 0 leave no output', pad=-4)
+    refused(b'pad 1, pad_dw -4 leave no output', pad_dw=-4)
+    refused(b'out_stride 2, out_H 0, out_W 0', out_stride=2)
+    refused(b'out_stride 1, out_H 9, out_W 0', out_H=9)
+    refused(b'out_stride 2, out_H 17, out_W 14 do not hold the 9 x 8 outputs', out_stride=2, out_H=17, out_W=14)
+    refused(b'out_stride 2, out_H 16, out_W 15 do not hold the 9 x 8 outputs', out_stride=2, out_H=16, out_W=15)
+    refused(b'out_stride 0', out_stride=0)
+    refused(b'2^31 elements', in_nb=1 << 30, nb=2)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason='checks the no-GPU failure mode')
 def test_no_gpu_means_loud_failure_not_fallback():
     from parity_utils import make_backbone, make_images

@@ -370,6 +370,7 @@ long conv_group_launches();
 // the caller goes on to launch_conv_group
 bool launch_conv_depthwise(const ConvParams& p, hipStream_t s);
 long conv_depthwise_launches();
+int conv_depthwise_last_tile();   // the tile TM (outputs per workgroup: 1024, 512, 256 or 128) of the calling thread's last launch_conv_depthwise that launched
 
 // g = src[idx]; run chain; dst[idx] = (accumulate ? dst[idx] : 0) + g.   Tensors are [C][SB][HW] for the gradient
 // and [C][B][HW] for the forward-side sources (sample b = sb % B).

@@ -38,6 +38,7 @@ constexpr int SPAN_MAX = 1 << 22;     // a tile's input span and output span in 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 std::atomic<long> g_launches{0};
+thread_local int g_last_tile = 0;     // TM of this thread's last launch_conv_depthwise that launched (conv_depthwise_last_tile)
 
 struct DwArgs {
     const float *in, *w, *w_pos, *bias, *bias_pos;
@@ -245,6 +246,7 @@ void launch_co(const DwArgs& a, int nhalves, bool vec, dim3 grid, int threads, s
 }  // namespace
 
 long conv_depthwise_launches() { return g_launches.load(); }
+int conv_depthwise_last_tile() { return g_last_tile; }
 
 bool launch_conv_depthwise(const ConvParams& p, hipStream_t s)
 {
@@ -288,5 +290,6 @@ bool launch_conv_depthwise(const ConvParams& p, hipStream_t s)
     else if (CO == 4) launch_co<4>(a, p.nhalves, vec, grid, threads, lds, s);
     else launch_co<8>(a, p.nhalves, vec, grid, threads, lds, s);
     g_launches++;
+    g_last_tile = TM;
     return true;
 }

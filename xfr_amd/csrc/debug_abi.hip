@@ -175,6 +175,94 @@ xfr_status xfr_debug_conv(const float* in_dev, const float* w_host, const float*
     return XFR_OK;
 }
 
+// one grouped launch (configuration 13 or 14) on the caller's pointers, as run_conv and the backward pass make them: no engine, no plan, no timing
+xfr_status xfr_debug_conv_grouped(const float* in_dev, float* out0_dev, float* out1_dev, const float* w_host, const float* bias_host,
+                                  const float* bias_pos_host, int32_t cin, int32_t cout, int32_t groups, int32_t h, int32_t w, int32_t nb, int32_t in_nb,
+                                  int32_t out_nb, int32_t kh, int32_t kw, int32_t stride, int32_t pad, int32_t pad_dw, int32_t relu_in, int32_t nhalves,
+                                  int32_t accumulate, int32_t out_stride, int32_t out_H, int32_t out_W, int32_t cfg, int32_t* cfg_out, int32_t* tile_out)
+{
+    if (cfg_out) *cfg_out = 0;
+    if (tile_out) *tile_out = 0;
+    if (!in_dev || !out0_dev || !w_host)
+        return fail(XFR_INVALID_ARG, "debug_conv_grouped: null argument (in_dev %p, out0_dev %p, w_host %p)", (const void*)in_dev, (void*)out0_dev, (const void*)w_host);
+    if (nhalves < 1 || nhalves > 2 || (nhalves == 2 && !out1_dev))
+        return fail(XFR_INVALID_ARG, "debug_conv_grouped: nhalves %d, out1_dev %p: one half, or two with a second output", nhalves, (void*)out1_dev);
+    if (cfg != 0 && cfg != CFG_GROUP && cfg != CFG_DEPTHWISE)
+        return fail(XFR_INVALID_ARG, "debug_conv_grouped: cfg %d: 0 (as the engine picks), %d or %d", cfg, (int)CFG_GROUP, (int)CFG_DEPTHWISE);
+    if (groups < 2 || cin < 1 || cout < 1 || cin % groups || cout % groups)
+        return fail(XFR_INVALID_ARG, "debug_conv_grouped: cin %d, cout %d, groups %d: at least two groups that divide both", cin, cout, groups);
+    if (h < 1 || w < 1 || kh < 1 || kw < 1 || stride < 1)
+        return fail(XFR_INVALID_ARG, "debug_conv_grouped: h %d, w %d, kh %d, kw %d, stride %d: each at least 1", h, w, kh, kw, stride);
+    if (nb < 1 || nb > in_nb || nb > out_nb)
+        return fail(XFR_INVALID_ARG, "debug_conv_grouped: nb %d, in_nb %d, out_nb %d: a batch prefix of both tensors, at least 1", nb, in_nb, out_nb);
+    if ((relu_in | accumulate) & ~1) return fail(XFR_INVALID_ARG, "debug_conv_grouped: relu_in %d, accumulate %d: flags, 0 or 1", relu_in, accumulate);
+    const long nh = (long)h + 2L * pad - kh, nw = (long)w + 2L * ((long)pad + pad_dw) - kw;
+    if (nh < 0 || nw < 0 || nh / stride + 1 > 32767 || nw / stride + 1 > 32767)
+        return fail(XFR_INVALID_ARG, "debug_conv_grouped: pad %d, pad_dw %d leave no output (or more than 32767 rows or columns) of a %d x %d map under %d x %d taps",
+                    pad, pad_dw, h, w, kh, kw);
+    const int OH = (int)(nh / stride) + 1, OW = (int)(nw / stride) + 1;
+    if ((out_H == 0) != (out_W == 0) || out_H < 0 || out_stride < 1 || (out_H == 0 && out_stride != 1) ||
+        (out_H != 0 && ((long)(OH - 1) * out_stride >= out_H || (long)(OW - 1) * out_stride >= out_W)))
+        return fail(XFR_INVALID_ARG, "debug_conv_grouped: out_stride %d, out_H %d, out_W %d do not hold the %d x %d outputs (0, 0: dense, stride 1)", out_stride, out_H,
+                    out_W, OH, OW);
+    if (out_H == 0) { out_H = OH; out_W = OW; }
+    // the kernels index a tensor with 32-bit offsets
+    if ((double)cin * in_nb * h * w >= 2147483648.0 || (double)cout * out_nb * out_H * out_W >= 2147483648.0 || (double)nb * OH * OW >= 2147483648.0)
+        return fail(XFR_INVALID_ARG, "debug_conv_grouped: a tensor of 2^31 elements or more (cin %d, in_nb %d, %d x %d; cout %d, out_nb %d, %d x %d)", cin, in_nb, h, w,
+                    cout, out_nb, out_H, out_W);
+    const int G = groups, Ci = cin / G, Co = cout / G;
+    if ((double)Ci * kh * kw >= 1048576.0) return fail(XFR_INVALID_ARG, "debug_conv_grouped: K = %d x %d x %d of one group is 2^20 or more", Ci, kh, kw);
+    const int K = Ci * kh * kw;
+
+    // the per-group packs, as the forward branch of pack_weights fills them (weights.hip)
+    const size_t pack = group_pack_floats(G, Co, K);
+    std::vector<float> host((size_t)nhalves * pack, 0.f);
+    for (int co = 0; co < cout; ++co) {
+        const int g = co / Co, col = co % Co;
+        const float* src = w_host + (size_t)co * K;
+        for (int kk = 0; kk < K; ++kk) {
+            const size_t at = group_pack_index(g, col, kk, Co, K);
+            host[at] = src[kk];
+            if (nhalves == 2) host[pack + at] = src[kk] > 0.f ? src[kk] : 0.f;
+        }
+    }
+    DevBuf<float> wd, bd, bpd;
+    XFR_TRY(wd.alloc(host.size()));
+    HIP_TRY(hipMemcpy(wd, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (bias_host) {
+        XFR_TRY(bd.alloc(cout));
+        HIP_TRY(hipMemcpy(bd, bias_host, cout * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (bias_pos_host && nhalves == 2) {
+        XFR_TRY(bpd.alloc(cout));
+        HIP_TRY(hipMemcpy(bpd, bias_pos_host, cout * sizeof(float), hipMemcpyHostToDevice));
+    }
+    ConvParams p;
+    memset(&p, 0, sizeof(p));
+    p.in = in_dev; p.w = wd; p.w_pos = nhalves == 2 ? wd + pack : nullptr; p.bias = bd; p.bias_pos = bpd; p.out0 = out0_dev; p.out1 = nhalves == 2 ? out1_dev : nullptr;
+    p.Cin = cin; p.H = h; p.W = w; p.NB = nb; p.in_nb = in_nb; p.out_nb = out_nb;
+    p.kh = kh; p.kw = kw; p.stride = stride; p.pad = pad; p.pad_dw = pad_dw;
+    p.OH = OH; p.OW = OW; p.K = K; p.K_logical = K; p.M = nb * OH * OW; p.CoutTot = cout; p.nhalves = nhalves; p.ldw = GROUP_ROWS;
+    p.relu_in = relu_in; p.accumulate = accumulate; p.out_H = out_H; p.out_W = out_W; p.out_stride = out_stride;
+    p.in_bytes = (unsigned)((size_t)cin * in_nb * h * w * sizeof(float));
+    p.groups = G;
+    int ran = 0;
+    if (cfg != CFG_GROUP && launch_conv_depthwise(p, 0)) ran = CFG_DEPTHWISE;
+    if (!ran && cfg == CFG_DEPTHWISE)
+        return fail(XFR_UNSUPPORTED_LAYER, "debug_conv_grouped: a launch the depthwise kernel does not take (Ci %d, Co %d, %d x %d taps, %d x %d map): nothing was launched", Ci,
+                    Co, kh, kw, h, w);
+    if (!ran) {
+        if (!launch_conv_group(p, 0)) return fail(XFR_UNSUPPORTED_LAYER, "debug_conv_grouped: a launch the grouped kernel does not take: nothing was launched");
+        ran = CFG_GROUP;
+    }
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(0);      // the packs go away with the call: nothing reads them then
+    if (err != hipSuccess) return fail(XFR_HIP_ERROR, "debug_conv_grouped: %s", hipGetErrorString(err));
+    if (cfg_out) *cfg_out = ran;
+    if (tile_out) *tile_out = ran == CFG_DEPTHWISE ? conv_depthwise_last_tile() : 0;
+    return XFR_OK;
+}
+
 xfr_status xfr_debug_conv_stamps(void* stamps_dev, int32_t capacity_workgroups)
 {
     if (stamps_dev && (capacity_workgroups == 0 || (capacity_workgroups < 0 && -capacity_workgroups < 256)))
