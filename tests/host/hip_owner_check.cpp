@@ -1,9 +1,12 @@
 // hip_owner_check.cpp -- xfr_amd/csrc/hip_owner.h against the stand-in runtime of hip/hip_runtime.h: ownership, grow, failed creations, the
-// all-or-nothing group idiom and the status mapping, on the host compiler alone (tests/test_hip_owner.py builds and runs it under the sanitizers).
+// all-or-nothing group idiom and the status mapping; and xfr_amd/csrc/scoped.h, the guard: a scope's value goes back on every way out.  All on the host
+// compiler alone (tests/test_hip_owner.py builds and runs it under the sanitizers).
 // Exit status 0: every case holds; otherwise the failing case is printed.
 #include "../../xfr_amd/csrc/hip_owner.h"
+#include "../../xfr_amd/csrc/scoped.h"
 
 #include <cstdio>
+#include <type_traits>
 #include <utility>
 
 using namespace xfr;
@@ -145,9 +148,72 @@ static int status_mapping()
     return 0;
 }
 
+static_assert(!std::is_copy_constructible<Scoped<int>>::value && !std::is_copy_assignable<Scoped<int>>::value, "a guard is not copied");
+static_assert(!std::is_copy_constructible<Scoped<const float*>>::value && !std::is_copy_assignable<Scoped<const float*>>::value, "a guard is not copied");
+
+// leaves through the early return when `early`, through the end otherwise; `seen` is what the callee read
+static xfr_status scoped_callee(int& slot, bool early, int& seen)
+{
+    Scoped<int> g(slot, 7);
+    seen = slot;
+    if (early) return fail(XFR_INVALID_ARG, "an early way out");
+    XFR_TRY(tried(hipSuccess));
+    return XFR_OK;
+}
+
+static int scoped_values()
+{
+    int slot = 3;                                         // the previous value comes back, not a constant
+    {
+        Scoped<int> g(slot, 5);
+        CHECK(slot == 5);
+    }
+    CHECK(slot == 3);
+    int seen = -1;                                        // an early return restores it, like the end of the function
+    CHECK(scoped_callee(slot, true, seen) == XFR_INVALID_ARG && seen == 7 && slot == 3);
+    slot = 4;
+    CHECK(scoped_callee(slot, false, seen) == XFR_OK && seen == 7 && slot == 4);
+    {                                                     // two guards on one variable go in reverse order
+        Scoped<int> outer(slot, 1);
+        {
+            Scoped<int> inner(slot, 2);
+            CHECK(slot == 2);
+        }
+        CHECK(slot == 1);
+        Scoped<int> again(slot, 9);                       // (same scope: `again` goes first, then `outer`)
+        CHECK(slot == 9);
+    }
+    CHECK(slot == 4);
+    const float a[2] = {1.f, 2.f};                        // a pointer, to null and back; a bool
+    const float* bank = a;
+    bool on = false;
+    {
+        Scoped<const float*> g(bank, nullptr);
+        Scoped<bool> h(on, true);
+        CHECK(bank == nullptr && on);
+        {
+            Scoped<const float*> k(bank, a + 1);
+            CHECK(bank == a + 1);
+        }
+        CHECK(bank == nullptr);
+    }
+    CHECK(bank == a && !on);
+    DevBuf<float> d;                                      // what the engine does: an owner converts to the pointer the guard writes
+    CHECK(d.alloc(4) == XFR_OK);
+    float* cur = nullptr;
+    {
+        Scoped<float*> g(cur, d);
+        CHECK(cur == d.p);
+    }
+    CHECK(cur == nullptr && d.cap == 4);
+    d.reset();
+    CHECK(none_live());
+    return 0;
+}
+
 int main()
 {
-    if (basic_ownership() || grow_keeps_and_grows() || failed_grow() || groups() || status_mapping()) return 1;
+    if (basic_ownership() || grow_keeps_and_grows() || failed_grow() || groups() || status_mapping() || scoped_values()) return 1;
     printf("hip_owner_check: all cases hold\n");
     return 0;
 }

@@ -125,6 +125,57 @@ def test_layerwise_batch_rows_and_idle_sweeps(gpu_device):
                 assert_map_close(maps[j, b], one, 'row (%d, %d)' % (j, b))
 
 
+def test_call_order_does_not_matter(gpu_device):
+    """What one call needs travels with the call, so a plain xfr_ebp is the same call whatever ran on the engine before it: the
+    same bytes and the same number of lean launches after every observing entry point (layer weights, captures, layerwise sweeps with an idle row,
+    a stored firing, the image hook) and after one refused call of each family, and again right behind a layerwise call.  Four images, so that the
+    lean schedule applies (n % 4 == 0) and a call that lost it would show in the launch count.
+    The engine holds six images, not four: three sweeps of four images are twelve gradient rows, and an engine admits 2 * max_batch of them."""
+    from xfr_amd import _lib
+    from xfr_amd.engine import _stream_ptr
+    import ctypes
+    subj, sd, x0 = _mini('all')
+    wb = subj.wb
+    wb.net.default_max_batch = 6
+    n = 4
+    eng = wb._engine(n)
+    assert eng.max_batch == 6
+    x = torch.cat((x0, make_images('stresnet_mini', n - 1, seed=12)), dim=0).to(gpu_device)
+    st, seed = wb.net.seed_for(torch.tensor([[1.0, 0.0]]), n)
+    nf = eng.firing_count(st)
+
+    def plain_ebp():
+        before = eng.lean_launches()
+        pooled = eng.ebp(x, st, seed.unsqueeze(0))[1]
+        return pooled.cpu().numpy().tobytes(), eng.lean_launches() - before
+
+    first, lean = plain_ebp()
+    assert lean > 0
+    w_, idx = eng.subtree_weights(x, st, torch.stack((seed, seed), 0))
+    cap = eng.ebp_capture(x, st, seed.unsqueeze(0), idx)
+    F = np.array([[3, 7, 5, 9], [12, -1, 14, 16], [33, 20, 30, 25]], dtype=np.int32)      # ascending per image; row (1, 1) idle
+    E = np.array([[idx[max(f, 0), b] if f >= 0 else 0 for b, f in enumerate(row)] for row in F], dtype=np.int32)
+    V = np.array([[cap[max(f, 0), b] if f >= 0 else 0.0 for b, f in enumerate(row)] for row in F], dtype=np.float32)
+    maps = eng.layerwise(x, st, F, E, V).cpu().numpy()
+    assert maps.shape[:2] == (3, n) and np.all(maps[1, 1] == 0)
+    assert tuple(eng.ebp_firing(x, st, seed, 12).shape[:1]) == (n,)
+    assert tuple(eng.ebp_firing(x, st, seed, nf).shape) == (n,) + tuple(x.shape[1:])          # the image hook
+    # one refused call of each family: both by argument checks, before any device work
+    bad = F.copy()
+    bad[2, 0] = nf
+    with pytest.raises(ValueError, match=r'firing %d outside \[0, %d\)' % (nf, nf)):          # XFR_INVALID_ARG
+        eng.layerwise(x, st, bad, E, V)
+    el = np.ascontiguousarray(idx.astype(np.int32))
+    out = np.zeros((nf + 1) * n, dtype=np.float32)
+    with torch.cuda.device(eng.device):
+        status = eng.lib.xfr_ebp_capture(eng._h, x.data_ptr(), n, int(st), seed.data_ptr(), el.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), nf + 1, _stream_ptr(eng.device))
+    assert status == _lib.XFR_INVALID_ARG and eng.lib.xfr_last_error().decode() == 'expected %d firings, got %d' % (nf, nf + 1)
+    assert plain_ebp() == (first, lean)
+    eng.layerwise(x, st, F, E, V)
+    assert plain_ebp() == (first, lean)
+
+
 @pytest.mark.parametrize('k', [5, 20, 40])
 def test_layerwise_argmax_golden(gpu_device, k):
     g = GC.golden('golden_subtree_mini')

@@ -1,8 +1,11 @@
 """The ownership rule of the host files ("Ownership"), without a device.
 
 test_owners_against_a_fake_runtime builds tests/host/hip_owner_check.cpp -- xfr_amd/csrc/hip_owner.h against the stand-in hip/hip_runtime.h beside it
--- with the host compiler under AddressSanitizer and UBSan, and runs it: ownership, grow, failed creations, all-or-nothing groups, status mapping.
-test_raw_lifetime_calls_live_in_the_owner_header reads the sources: outside hip_owner.h nothing creates or destroys a device resource by hand."""
+-- with the host compiler under AddressSanitizer and UBSan, and runs it: ownership, grow, failed creations, all-or-nothing groups, status mapping,
+and the guard of xfr_amd/csrc/scoped.h (a scope's value goes back on every way out).
+test_raw_lifetime_calls_live_in_the_owner_header reads the sources: outside hip_owner.h nothing creates or destroys a device resource by hand.
+test_call_state_is_not_engine_state reads them for DESIGN.md section 9m: a sweep's context and the one-shots of a call are arguments, not members of
+the engine; no .hip file defines a guard of its own; nobody can call the sweep without saying which context it runs in."""
 import glob
 import os
 import re
@@ -52,3 +55,46 @@ def test_raw_lifetime_calls_live_in_the_owner_header():
     assert tws == 1, 'the tail workspace of xfr_debug_conv is one line'
     owner = open(os.path.join(CSRC, 'hip_owner.h')).read()
     assert len(set(m.group(1) for m in RAW.finditer(owner))) == 9      # every one of them lives there (both stream creations)
+
+
+# what one call used to leave on the engine for its callees to read back
+PER_CALL = ('rc_priors', 'rc_caps', 'rc_prior_row', 'rc_cap_row', 'rc_dense_slot', 'rc_prior_dense', 'rc_active', 'rc_n', 'lazy_zero', 'store_slot', 'tab_sb',
+            'store_tensor', 'store_sb', 'inputs_event', 'stage_slot')
+
+
+def _strip_comments(text):
+    return re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', text, flags=re.S))
+
+
+def _braced(text, start):
+    """The text between the brace that follows `start` and its partner."""
+    i = text.index('{', start)
+    depth = 0
+    for j in range(i, len(text)):
+        depth += {'{': 1, '}': -1}.get(text[j], 0)
+        if depth == 0:
+            return text[i + 1:j]
+    raise AssertionError('unbalanced braces')
+
+
+def test_call_state_is_not_engine_state():
+    header = _strip_comments(open(os.path.join(CSRC, 'engine_internal.h')).read())
+    body = _braced(header, header.index('struct xfr_engine'))
+    assert 'cur_slot' in body and 'hold_forward' in body and len(body) > 4000          # (the engine's body it is)
+    declared = set(re.findall(r'[A-Za-z_]\w*', body))
+    assert not declared & set(PER_CALL), 'per-call state declared on the engine: %s' % sorted(declared & set(PER_CALL))
+    # one guard type (scoped.h) and HoldGuard beside it in the header: none defined inside a function of a .hip file
+    local = []
+    for path in sorted(glob.glob(os.path.join(CSRC, '*.hip'))):
+        for m in re.finditer(r'\bstruct\s+(\w*Guard|Unpipe)\b\s*[{:]', _strip_comments(open(path).read())):
+            local.append('%s: struct %s' % (os.path.basename(path), m.group(1)))
+    assert not local, 'guard structs defined in .hip files:\n' + '\n'.join(local)
+    assert re.search(r'\bclass\s+Scoped\b', open(os.path.join(CSRC, 'scoped.h')).read()) and '#include "scoped.h"' in header
+    assert 'hip/' not in open(os.path.join(CSRC, 'scoped.h')).read()                 # the host compiler alone builds it
+    # the sweep's context is an explicit argument: a SweepCtx parameter without a default in each declaration
+    for fn in ('run_backward', 'resolve_chain', 'bwd_conv_params', 'lean_applies', 'ebp_core'):
+        m = re.search(r'\b%s\s*\(([^;{]*)\)\s*;' % fn, header)
+        assert m, 'no declaration of %s in engine_internal.h' % fn
+        params = [p.strip() for p in m.group(1).split(',')]
+        ctx = [p for p in params if 'SweepCtx' in p]
+        assert len(ctx) == 1 and '=' not in ctx[0], '%s(%s)' % (fn, m.group(1))

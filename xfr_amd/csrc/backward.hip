@@ -15,7 +15,7 @@ static int prior_action_for(int mode, int kind)
 
 // Symbolic chain -> pointers.  What the fields of the overloaded chain heads and stores mean (EW_POOL2_IN, EW_AVGUP_IN, EW_STORE actions 1 / 2) is
 // written down once, at their constructors in plan_fuse.hip (fuse_pool2_head, fuse_avgup_head, fuse_store_save / _restore).
-void resolve_chain(xfr_engine* e, const std::vector<BwdStep::Sym>& syms, EwChain& ch, double* trace, int SB, bool plain)
+void resolve_chain(xfr_engine* e, const SweepCtx& cx, const std::vector<BwdStep::Sym>& syms, EwChain& ch, double* trace, int SB, bool plain)
 {
     ch.n = 0;
     for (const auto& sy : syms) {
@@ -36,19 +36,19 @@ void resolve_chain(xfr_engine* e, const std::vector<BwdStep::Sym>& syms, EwChain
                 if (sy.tap) q.pstore = e->ws + e->tap_off;
                 if (e->trace_on && sy.slot >= 0 && trace) q.trace = trace + (size_t)sy.slot * SB;
                 if (sy.slot >= 0) {
-                    if (sy.slot == e->store_slot && !sy.tap) q.pstore = e->store_dev;
-                    if (e->rc_priors && sy.slot == e->rc_dense_slot) {
+                    if (sy.slot == cx.store_slot && !sy.tap) q.pstore = cx.store_dst;
+                    if (cx.priors && sy.slot == cx.dense_slot) {
                         q.prior_sb = 0;
-                        q.prior_dense = e->rc_prior_dense;
+                        q.prior_dense = cx.prior_dense;
                         q.prior_action = prior_action_for(e->mode, e->ops[sy.op].d.kind);
-                    } else if (e->rc_priors && sy.slot < (int)e->rc_prior_row.size() && e->rc_prior_row[sy.slot]) {
-                        q.prior_elem = e->tab_elem_d + (size_t)sy.slot * e->tab_sb;
-                        q.prior_val = e->tab_val_d + (size_t)sy.slot * e->tab_sb;
+                    } else if (cx.priors && sy.slot < (int)cx.prior_row.size() && cx.prior_row[sy.slot]) {
+                        q.prior_elem = cx.tab_elem + (size_t)sy.slot * cx.tab_sb;
+                        q.prior_val = cx.tab_val + (size_t)sy.slot * cx.tab_sb;
                         q.prior_action = prior_action_for(e->mode, e->ops[sy.op].d.kind);
                     }
-                    if (e->rc_caps && sy.slot < (int)e->rc_cap_row.size() && e->rc_cap_row[sy.slot]) {
-                        q.cap_elem = e->tab_elem_d + (size_t)sy.slot * e->tab_sb;
-                        q.cap_dst = e->cap_dev + (size_t)sy.slot * e->tab_sb;
+                    if (cx.caps && sy.slot < (int)cx.cap_row.size() && cx.cap_row[sy.slot]) {
+                        q.cap_elem = cx.tab_elem + (size_t)sy.slot * cx.tab_sb;
+                        q.cap_dst = cx.cap_dst + (size_t)sy.slot * cx.tab_sb;
                     }
                 }
                 break;
@@ -74,7 +74,7 @@ void resolve_chain(xfr_engine* e, const std::vector<BwdStep::Sym>& syms, EwChain
 
 // launch parameters of a backward-data GEMM step (with its fused chain resolved against the workspace); ph: the phase of a strided KxK layer.
 // false: a layer that runs by phases was asked for without one, or a phase came with another layer -- p is not a launch
-bool bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& st, int B, int SB, int SBa, ConvParams& p, const PhaseRec* ph)
+bool bwd_conv_params(xfr_engine* e, const SweepCtx& cx, const BwdPlan& plan, const BwdStep& st, int B, int SB, int SBa, ConvParams& p, const PhaseRec* ph)
 {
     const OpRec& o = e->ops[st.op];
     const xfr_op_desc& d = o.d;
@@ -128,7 +128,7 @@ bool bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& st, int 
     }
     p.M = SBa * p.OH * p.OW;
     if (!st.chain.empty()) {
-        resolve_chain(e, st.chain, p.chain, nullptr, SB);
+        resolve_chain(e, cx, st.chain, p.chain, nullptr, SB);
         p.chain_B = B;
         p.chain_eps = e->eps;
         p.accumulate = 0;
@@ -143,7 +143,7 @@ bool bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& st, int 
 // the interpreter has no fan-out step.  Every other fusion falls back to the interpreted epilogue; a network whose merged fan-out
 // chain is not in chain_sigs.inc falls back to the schedule without fan-outs (plan.fused_gemm_nofan).  Decided once per plan: whether
 // a chain has a compiled signature depends on the layer program and the mode, not on the batch (the fan-out requires HW % 4 == 0).
-static bool fanout_compiled(xfr_engine* e, BwdPlan& plan, int B, int SB)
+static bool fanout_compiled(xfr_engine* e, const SweepCtx& cx, BwdPlan& plan, int B, int SB)
 {
     if (plan.fan_ok >= 0) return plan.fan_ok != 0;
     plan.fan_ok = 1;
@@ -153,14 +153,14 @@ static bool fanout_compiled(xfr_engine* e, BwdPlan& plan, int B, int SB)
         for (const auto& sy : st.chain) if (sy.type == EW_MAXHALF_OUT) fan = true;
         if (!fan) continue;
         ConvParams p;
-        if (!bwd_conv_params(e, plan, st, B, SB, SB, p)) { plan.fan_ok = 0; break; }      // (a layer that runs by phases carries no chain)
+        if (!bwd_conv_params(e, cx, plan, st, B, SB, SB, p)) { plan.fan_ok = 0; break; }      // (a layer that runs by phases carries no chain)
         p.chain_interpret = 0;
         if (conv_gemm_cannot_launch(p)) { plan.fan_ok = 0; break; }
     }
     return plan.fan_ok != 0;
 }
 
-xfr_status run_backward(xfr_engine* e, BwdPlan& plan, int B, int S, hipStream_t s)
+xfr_status run_backward(xfr_engine* e, const SweepCtx& cx, BwdPlan& plan, int B, int S, hipStream_t s)
 {
     const int SB = S * B;
     double* trace = e->dbl_ws + 2 * e->max_batch;
@@ -170,21 +170,21 @@ xfr_status run_backward(xfr_engine* e, BwdPlan& plan, int B, int S, hipStream_t 
         e->last_trace_sb = SB;
         e->last_trace_kinds = plan.firing_kinds;
     }
-    const bool special = e->rc_priors || e->rc_caps || e->store_slot >= 0;
+    const bool special = cx.observing();
     const bool use_fused = !e->trace_on && !plan.fused.empty() && !plan.plain;
-    // Layerwise sweeps sorted by firing (rc_active): stream j is identically zero until the step that holds its prior
+    // Layerwise sweeps sorted by firing (cx.active): stream j is identically zero until the step that holds its prior
     // hook, so the GEMMs and hook chains before that step leave it out (the gradient region was zero-filled; the small
     // pool / copy kernels still run over all streams and move zeros).  SBa = streams alive at this step.
-    const bool prefix = !e->rc_active.empty() && (int)e->rc_active.size() * e->rc_n == SB;
+    const bool prefix = !cx.active.empty() && (int)cx.active.size() * cx.n == SB;
     int run_max = -1;
     const bool use_gemm_fusion = use_fused && e->fuse_gemm_epilogue && !special && !plan.fused_gemm.empty();
-    const bool fanout = use_gemm_fusion && !e->interpret_chains && fanout_compiled(e, plan, B, SB);
+    const bool fanout = use_gemm_fusion && !e->interpret_chains && fanout_compiled(e, cx, plan, B, SB);
     const bool lean = e->lean_cur == &plan && use_gemm_fusion && plan.lean_state == 1;
     if (e->lean_cur == &plan && !lean) return fail(XFR_STATE_ERROR, "lean schedule: the probe forward ran lean and the sweep cannot");
-    // On-demand zeroing of the prefix sweeps (e->lazy_zero): wr[t] = leading rows of G(t) that hold defined values.  A launch that reads rows
+    // On-demand zeroing of the prefix sweeps (cx.lazy_zero): wr[t] = leading rows of G(t) that hold defined values.  A launch that reads rows
     // [0, r) first gets the rows [wr[t], r) zeroed (one 2-D memset over the channels); launches that walk whole tensors or use another layout
     // (pool / copy VJPs, scattering and compact strided GEMMs, chain heads that expand a pooled gradient) get whole tensors.
-    const bool lazy = prefix && e->lazy_zero;
+    const bool lazy = prefix && cx.lazy_zero;
     std::vector<int> wr;
     if (lazy) { wr.assign(e->tens.size(), 0); wr[plan.seed_tensor] = SB; }
     auto need = [&](int t, int rows) -> xfr_status {
@@ -201,7 +201,7 @@ xfr_status run_backward(xfr_engine* e, BwdPlan& plan, int B, int S, hipStream_t 
         if (prefix) {
             for (const auto& sy : st.chain)
                 if (sy.type == EW_HOOK && sy.slot > run_max) run_max = sy.slot;
-            SBa = (int)(std::upper_bound(e->rc_active.begin(), e->rc_active.end(), run_max) - e->rc_active.begin()) * e->rc_n;
+            SBa = (int)(std::upper_bound(cx.active.begin(), cx.active.end(), run_max) - cx.active.begin()) * cx.n;
             if (SBa == 0) continue;
         }
         if (lazy) {
@@ -228,7 +228,7 @@ xfr_status run_backward(xfr_engine* e, BwdPlan& plan, int B, int S, hipStream_t 
         switch (st.kind) {
             case ST_EW: {
                 EwChain ch;
-                resolve_chain(e, st.chain, ch, trace, SB, plan.plain);
+                resolve_chain(e, cx, st.chain, ch, trace, SB, plan.plain);
                 const Tensor& x = e->tens[st.ew_t];
                 launch_ew_chain(e->G(st.src_t), e->G(st.dst_t), st.accumulate, ch, x.C, SB, B, x.HW(), e->eps, s, SBa);
                 break;
@@ -257,7 +257,7 @@ xfr_status run_backward(xfr_engine* e, BwdPlan& plan, int B, int S, hipStream_t 
                 }
                 xfr_status rs = XFR_OK;
                 for (size_t q = 0; q < std::max<size_t>(phases.size(), 1) && rs == XFR_OK; ++q) {
-                    if (!bwd_conv_params(e, plan, st, B, SB, SBa, p, phases.empty() ? nullptr : &phases[q]))
+                    if (!bwd_conv_params(e, cx, plan, st, B, SB, SBa, p, phases.empty() ? nullptr : &phases[q]))
                         rs = fail(XFR_STATE_ERROR, "backward-data GEMM of op %d: phase and layer do not match", st.op);
                     else
                         rs = run_conv(e, p, (side && (q & 3)) ? (hipStream_t)side->s[(q & 3) - 1] : s);

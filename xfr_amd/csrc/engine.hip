@@ -93,7 +93,7 @@ xfr_status fence_slot0(xfr_engine* e, hipStream_t s)
     return XFR_OK;
 }
 
-xfr_status ebp_core(xfr_engine* e, const float* x_dev, int n, int S, int seed_tensor, const float* seed_dev, hipStream_t s)
+xfr_status ebp_core(xfr_engine* e, const SweepCtx& cx, const float* x_dev, int n, int S, int seed_tensor, const float* seed_dev, hipStream_t s)
 {
     // the one-shot promise of xfr_engine_set_inputs_ready covers THIS call, whatever becomes of it: consumed before the first check that
     // can fail, so an early error never leaves it standing for a later call that declared nothing
@@ -108,8 +108,8 @@ xfr_status ebp_core(xfr_engine* e, const float* x_dev, int n, int S, int seed_te
     // overlaps the backward sweep of the previous call (which is still reading the other slot)
     const bool pipe = e->pipeline_all && !e->profile_on && e->s_b;
     hipStream_t sf = pipe ? e->s_b : s;
-    e->cur_slot = pipe ? (int)(e->seq++ % e->n_slots) : 0;
-    const int slot = e->cur_slot;
+    const int slot = pipe ? (int)(e->seq++ % e->n_slots) : 0;
+    Scoped<int> cur_slot(e->cur_slot, slot);
     if (pipe && e->slot_pending[slot]) HIP_TRY(hipStreamWaitEvent(sf, e->ev_slot_done[slot], 0));
     // (the promise covers ONE call: a caller that forgets to renew it falls back to the safe ordering, never to a stale promise)
     if (pipe && !ready) {
@@ -117,21 +117,19 @@ xfr_status ebp_core(xfr_engine* e, const float* x_dev, int n, int S, int seed_te
         // whose inputs are resident declare it with xfr_engine_set_inputs_ready and keep the cross-call overlap.
         XFR_TRY(fork_streams(e, s, sf));
     }
-    struct LeanGuard { xfr_engine* e; ~LeanGuard() { e->lean_cur = nullptr; } } lean_guard{e};
-    e->lean_cur = lean_applies(e, *plan, n) ? plan : nullptr;
+    Scoped<const BwdPlan*> lean_cur(e->lean_cur, lean_applies(e, *plan, n, cx) ? plan : nullptr);
     st = forward_all(e, x_dev, n, seed_tensor, true, sf);
-    if (st != XFR_OK) { e->cur_slot = 0; return st; }
+    if (st != XFR_OK) return st;
     if (pipe) XFR_TRY(join_streams(e, s, nullptr, sf));
     const Tensor& sd = e->tens[seed_tensor];
     launch_seed_to_cnhw(seed_dev, e->G(seed_tensor), S * n, sd.C, sd.HW(), s);
-    st = run_backward(e, *plan, n, S, s);
+    st = run_backward(e, cx, *plan, n, S, s);
     if (pipe && st == XFR_OK) {
         HIP_TRY(hipEventRecord(e->ev_slot_done[slot], s));
         e->slot_pending[slot] = true;
     } else if (st == XFR_OK) {
         st = fence_slot0(e, s);
     }
-    e->cur_slot = 0;
     return st;
 }
 
@@ -262,15 +260,15 @@ xfr_status xfr_forward(xfr_engine* e, const float* x_dev, int32_t n, int32_t ten
         if (st != XFR_OK) return st;
         const Tensor& t = e->tens[tensor_id];
         const size_t in_per_n = (size_t)e->in_c * e->in_h * e->in_w;
-        struct BankGuard { xfr_engine* e; ~BankGuard() { e->t_bank = nullptr; } } bank_guard{e};
         XFR_TRY(fork_streams(e, s, e->s_a, e->s_b));      // after everything already on the caller's stream (inputs, earlier sweeps)
         // whatever was enqueued on the internal streams (also by a half that then failed) is ordered before anything the caller puts on s next
         auto join = [&]() -> xfr_status { return join_streams(e, s, e->s_a, e->s_b); };
-        e->t_bank = e->ws_enc;
-        st = forward_all(e, x_dev, n0, tensor_id, false, e->s_a);
-        if (st != XFR_OK) { const std::string why = g_err; join(); g_err = why; return st; }
-        launch_cnhw_to_nchw(e->T(tensor_id), out_dev, n0, t.C, t.HW(), e->s_a);
-        e->t_bank = nullptr;
+        {
+            Scoped<float*> bank(e->t_bank, e->ws_enc);
+            st = forward_all(e, x_dev, n0, tensor_id, false, e->s_a);
+            if (st != XFR_OK) { const std::string why = g_err; join(); g_err = why; return st; }
+            launch_cnhw_to_nchw(e->T(tensor_id), out_dev, n0, t.C, t.HW(), e->s_a);
+        }
         const float* x_hi = e->u8_on ? reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(x_dev) + (size_t)n0 * e->in_h * e->in_w * e->u8_pre.channels)
                                      : x_dev + (size_t)n0 * in_per_n;
         st = forward_all(e, x_hi, n - n0, tensor_id, false, e->s_b);
@@ -301,7 +299,7 @@ xfr_status xfr_ebp(xfr_engine* e, const float* x_dev, int32_t n, int32_t n_strea
     if (n_streams < 1 || n_streams > 2) return fail(XFR_INVALID_ARG, "n_streams must be 1 or 2");
     hipStream_t s = (hipStream_t)stream;
     prof_begin(e);
-    st = ebp_core(e, x_dev, n, n_streams, seed_tensor, seed_dev, s);
+    st = ebp_core(e, SweepCtx(), x_dev, n, n_streams, seed_tensor, seed_dev, s);
     if (st != XFR_OK) return st;
     const Tensor& t1 = e->tens[1];
     const int SB = n_streams * n;
@@ -375,7 +373,7 @@ static xfr_status contrastive(xfr_engine* e, const float* x_dev, int32_t n, int3
     if (percentile > 100.f) return fail(XFR_INVALID_ARG, "percentile must be <= 100 (or < 0 for plain contrastive)");
     hipStream_t s = (hipStream_t)stream;
     prof_begin(e);
-    st = ebp_core(e, x_dev, n, 2, seed_tensor, seed_dev, s);
+    st = ebp_core(e, SweepCtx(), x_dev, n, 2, seed_tensor, seed_dev, s);
     if (st != XFR_OK) return st;
     st = contrastive_tail(e, n, percentile, out_dev, s, tail);
     if (st != XFR_OK) return st;
@@ -400,10 +398,12 @@ xfr_status xfr_contrastive_u8(xfr_engine* e, const float* x_dev, int32_t n, int3
     return contrastive(e, x_dev, n, seed_tensor, seed_dev, percentile, sal_dev, stream, TAIL_U8);
 }
 
-// xfr_triplet_contrastive (float maps, the ebp_version 6 tail) and xfr_triplet_contrastive_u8tail (bytes, the tail of the other versions)
+// xfr_triplet_contrastive (float maps, the ebp_version 6 tail) and xfr_triplet_contrastive_u8tail (bytes, the tail of the other versions).
+// in_ev / stage_slot, the engine's own staging (xfr_triplet_contrastive_u8_host; nullptr / -1 otherwise): the inputs are complete when the copy's event
+// fires -- nothing on the caller's stream concerns them, so the forwards of a pipelined call need not wait for it -- and sit in that staging slot
 static xfr_status triplet_contrastive(xfr_engine* e, const float* probes_dev, const float* gallery_dev, int32_t n,
                                       int32_t encode_tensor, float scale, float percentile, void* sal_dev, void* stream,
-                                      int32_t inputs_ready, ContrastTail tail)
+                                      int32_t inputs_ready, ContrastTail tail, hipEvent_t in_ev, int stage_slot)
 {
     xfr_status st = check_run(e, probes_dev, n);
     if (st != XFR_OK) return st;
@@ -434,15 +434,8 @@ static xfr_status triplet_contrastive(xfr_engine* e, const float* probes_dev, co
     const bool pipe = fork && e->pipeline;
     hipStream_t sa = fork ? e->s_a : s, sb = fork ? e->s_b : s;
     // every exit path (errors included) leaves the engine on slot 0 / the main bank: the non-pipelined entry points assume it
-    struct SlotGuard { xfr_engine* e; ~SlotGuard() { e->cur_slot = 0; e->t_bank = nullptr; } } slot_guard{e};
-    e->cur_slot = pipe ? (int)(e->seq++ % e->n_slots) : 0;
-    const int slot = e->cur_slot;
-    // the engine's own staging (xfr_triplet_contrastive_u8_host): the inputs are complete when the copy's event fires -- nothing on the caller's stream
-    // concerns them, so the forwards of a pipelined call need not wait for it (one-shot: consumed here, whatever becomes of the call)
-    hipEvent_t in_ev = e->inputs_event;
-    const int stage_slot = e->stage_slot;
-    e->inputs_event = nullptr;
-    e->stage_slot = -1;
+    const int slot = pipe ? (int)(e->seq++ % e->n_slots) : 0;
+    Scoped<int> cur_slot(e->cur_slot, slot);
     if (fork) {
         if (pipe && (inputs_ready || in_ev)) {
             if (e->slot_pending[slot]) {       // the backward that last read this slot must be done
@@ -459,16 +452,17 @@ static xfr_status triplet_contrastive(xfr_engine* e, const float* probes_dev, co
     } else if (in_ev) HIP_TRY(hipStreamWaitEvent(s, in_ev, 0));
     const Tensor& sd = e->tens[encode_tensor];
     float* seed_dst = pipe ? e->seedbuf[slot] : e->G(encode_tensor);
-    e->t_bank = e->ws_enc;
-    st = forward_all(e, gallery_dev, 2 * n, encode_tensor, false, sa);
-    // seeds: stream 0 = scale * encode(mate_i), stream 1 = scale * encode(nonmate_i)  (demo/test_whitebox.py:129 with the
-    // one-hot priors of whitebox.py:512,518 folded through the un-hooked 2-way classifier).  Layouts coincide:
-    // both are [D][2n][1].
-    if (st == XFR_OK) launch_scale(e->T(encode_tensor), seed_dst, (long)sd.per_n() * 2 * n, scale, 0, sa);
-    e->t_bank = nullptr;
+    {
+        Scoped<float*> bank(e->t_bank, e->ws_enc);
+        st = forward_all(e, gallery_dev, 2 * n, encode_tensor, false, sa);
+        // seeds: stream 0 = scale * encode(mate_i), stream 1 = scale * encode(nonmate_i)  (demo/test_whitebox.py:129 with the
+        // one-hot priors of whitebox.py:512,518 folded through the un-hooked 2-way classifier).  Layouts coincide:
+        // both are [D][2n][1].
+        if (st == XFR_OK) launch_scale(e->T(encode_tensor), seed_dst, (long)sd.per_n() * 2 * n, scale, 0, sa);
+    }
     if (st != XFR_OK) return st;
-    struct LeanGuard { xfr_engine* e; ~LeanGuard() { e->lean_cur = nullptr; } } lean_guard{e};
-    e->lean_cur = lean_applies(e, *plan, n) ? plan : nullptr;
+    const SweepCtx plain;
+    Scoped<const BwdPlan*> lean_cur(e->lean_cur, lean_applies(e, *plan, n, plain) ? plan : nullptr);
     st = forward_all(e, probes_dev, n, encode_tensor, true, sb);
     if (st != XFR_OK) return st;
     if (fork) XFR_TRY(join_streams(e, s, sa, sb));
@@ -478,7 +472,7 @@ static xfr_status triplet_contrastive(xfr_engine* e, const float* probes_dev, co
         e->stage_busy[stage_slot] = true;
     }
     if (pipe) launch_copy_acc(seed_dst, e->G(encode_tensor), (long)sd.per_n() * 2 * n, 0, s);
-    st = run_backward(e, *plan, n, 2, s);
+    st = run_backward(e, plain, *plan, n, 2, s);
     if (st != XFR_OK) return st;
     st = contrastive_tail(e, n, percentile, sal_dev, s, tail);
     if (st != XFR_OK) return st;
@@ -486,7 +480,6 @@ static xfr_status triplet_contrastive(xfr_engine* e, const float* probes_dev, co
         HIP_TRY(hipEventRecord(e->ev_slot_done[slot], s));
         e->slot_pending[slot] = true;
     }
-    e->cur_slot = 0;
     return prof_end(e, s);
 }
 
@@ -494,14 +487,14 @@ xfr_status xfr_triplet_contrastive(xfr_engine* e, const float* probes_dev, const
                                    int32_t encode_tensor, float scale, float percentile, float* sal_dev, void* stream,
                                    int32_t inputs_ready)
 {
-    return triplet_contrastive(e, probes_dev, gallery_dev, n, encode_tensor, scale, percentile, sal_dev, stream, inputs_ready, TAIL_V6);
+    return triplet_contrastive(e, probes_dev, gallery_dev, n, encode_tensor, scale, percentile, sal_dev, stream, inputs_ready, TAIL_V6, nullptr, -1);
 }
 
 xfr_status xfr_triplet_contrastive_u8tail(xfr_engine* e, const float* probes_dev, const float* gallery_dev, int32_t n,
                                           int32_t encode_tensor, float scale, float percentile, uint8_t* sal_dev, void* stream,
                                           int32_t inputs_ready)
 {
-    return triplet_contrastive(e, probes_dev, gallery_dev, n, encode_tensor, scale, percentile, sal_dev, stream, inputs_ready, TAIL_U8);
+    return triplet_contrastive(e, probes_dev, gallery_dev, n, encode_tensor, scale, percentile, sal_dev, stream, inputs_ready, TAIL_U8, nullptr, -1);
 }
 
 xfr_status xfr_engine_set_u8_preprocess(xfr_engine* e, const xfr_u8_preprocess* p)
@@ -520,15 +513,11 @@ xfr_status xfr_engine_set_u8_preprocess(xfr_engine* e, const xfr_u8_preprocess* 
     return XFR_OK;
 }
 
-namespace {
-struct U8Guard { xfr_engine* e; explicit U8Guard(xfr_engine* e_) : e(e_) { e->u8_on = true; } ~U8Guard() { e->u8_on = false; } };
-}
-
 xfr_status xfr_forward_u8(xfr_engine* e, const uint8_t* x_u8_dev, int32_t n, int32_t tensor_id, float* out_dev, void* stream)
 {
     xfr_status st = require_u8(e);
     if (st != XFR_OK) return st;
-    U8Guard g(e);
+    Scoped<bool> u8(e->u8_on, true);
     return xfr_forward(e, reinterpret_cast<const float*>(x_u8_dev), n, tensor_id, out_dev, stream);
 }
 
@@ -537,7 +526,7 @@ xfr_status xfr_triplet_contrastive_u8(xfr_engine* e, const uint8_t* probes_u8_de
 {
     xfr_status st = require_u8(e);
     if (st != XFR_OK) return st;
-    U8Guard g(e);
+    Scoped<bool> u8(e->u8_on, true);
     return xfr_triplet_contrastive(e, reinterpret_cast<const float*>(probes_u8_dev), reinterpret_cast<const float*>(gallery_u8_dev), n, encode_tensor, scale,
                                    percentile, sal_dev, stream, inputs_ready);
 }
@@ -591,14 +580,9 @@ xfr_status xfr_triplet_contrastive_u8_host(xfr_engine* e, const uint8_t* probes_
     HIP_TRY(hipMemcpyAsync(pro, probes_u8_host, (size_t)n * img, hipMemcpyHostToDevice, e->s_copy));
     HIP_TRY(hipEventRecord(e->ev_copied[slot], e->s_copy));
     e->last_copied = e->ev_copied[slot];
-    e->inputs_event = e->ev_copied[slot];
-    e->stage_slot = slot;
-    U8Guard g(e);
-    st = xfr_triplet_contrastive(e, reinterpret_cast<const float*>(pro), reinterpret_cast<const float*>(gal), n, encode_tensor, scale, percentile,
-                                 sal_dev, stream, 0);
-    e->inputs_event = nullptr;                 // (an argument error returned before the call consumed them)
-    e->stage_slot = -1;
-    return st;
+    Scoped<bool> u8(e->u8_on, true);
+    return triplet_contrastive(e, reinterpret_cast<const float*>(pro), reinterpret_cast<const float*>(gal), n, encode_tensor, scale, percentile, sal_dev,
+                               stream, 0, TAIL_V6, e->ev_copied[slot], slot);
 }
 
 xfr_status xfr_engine_wait_inputs_copied(xfr_engine* e)

@@ -5,6 +5,7 @@
 //   forward.hip        forward fusers and the forward executor
 //   backward.hip       chain resolution and the sweep executor
 //   hip_owner.h        the error helpers and the owners of device buffers, pinned buffers, events and streams (included here)
+//   scoped.h           Scoped<T>: a value written for the length of a scope, the one guard of these files (included here)
 //   engine.hip         the C ABI: create / destroy / weights / setters / forward / EBP / contrastive / triplet / uint8 / profiling
 //   weights.hip        the packs of the weight arena, filled on the host; the bf16 planes of the covered packs
 //   debug_abi.hip      the C ABI: the xfr_debug_* entry points
@@ -21,6 +22,7 @@
 #include "../../include/xfr_amd.h"
 #include "common.h"
 #include "hip_owner.h"
+#include "scoped.h"
 
 #include <algorithm>
 #include <cmath>
@@ -200,72 +202,72 @@ struct PhaseStreams {
     Event fork, done[3];
 };
 
+// What one sweep needs beyond its plan, as a value: the entry point that observes a sweep (priors, captures, a stored firing, ascending prefixes; subtree.hip)
+// builds one on its stack and hands it down; nothing of it lives on the engine.  A default-constructed one is the plain sweep.
+struct SweepCtx {
+    bool priors = false, caps = false;                // are the priors / the captures of this call live?
+    std::vector<char> prior_row, cap_row;             // per firing: does the row of the tables hold any entry?
+    int dense_slot = -1;                              // firing that carries the dense prior (-1: none) ...
+    const float* prior_dense = nullptr;               // ... and that tensor (single sweep of one image)
+    int store_slot = -1;                              // firing whose full P tensor is kept (-1: none) ...
+    float* store_dst = nullptr;                       // ... and where
+    // the tables [n_firings][tab_sb] over the gradient rows sb (stream * n + sample), on the device (common.h: EwStep::prior_elem / cap_elem)
+    const int* tab_elem = nullptr;                    // prior element (or capture element) per (firing, row); -1: none
+    const float* tab_val = nullptr;                   // prior value per (firing, row)
+    float* cap_dst = nullptr;                         // captured value per (firing, row)
+    int tab_sb = 0;                                   // their row length
+    std::vector<int> active;                          // layerwise sweeps in ascending firing order: stream j (all its samples) is identically zero before firing active[j]
+    int n = 1;                                        // samples per stream of that batch
+    bool lazy_zero = false;                           // prefix sweeps: run_backward zeroes un-written gradient rows on demand (xfr_layerwise_ebp)
+    bool observing() const { return priors || caps || store_slot >= 0; }      // such a sweep keeps its chains in launches of their own, and never runs lean
+};
+
 struct xfr_engine {
+    // ---- geometry: the network, its plans and the layout of the workspace (plan.hip)
     int device = 0;
     int max_batch = 0;
     int in_c = 0, in_h = 0, in_w = 0;
     std::vector<OpRec> ops;
     std::vector<Tensor> tens;
     int n_weights = 0;
-    // Streams and events first: members go in reverse order, so every buffer below is freed before the streams and events it was used on.
+    std::vector<char> is_hook_a;       // per tensor: some hook takes its a (and x) from this tensor's forward values
+    bool need_dirty = true;
+    std::deque<BwdPlan> plans;         // deque: get_plan() hands out pointers that must survive later insertions
+    size_t arena_floats = 0, ws_floats = 0, idx_bytes = 0;
+    size_t x_off = 0, seed_off = 0, tap_off = 0, pooled_off = 0, blur_a_off = 0, blur_b_off = 0, misc_off = 0, thr_off = 0;
+    size_t g_begin = 0, g_end = 0;                    // the gradient region of the workspace (floats)
+    size_t t_region_floats = 0, fwd_region_floats = 0;
+    size_t trace_cap = 0;          // firings capacity
+    // ---- streams and events.  They come first: members go in reverse order, so every buffer below is freed before the streams and events it was used on.
     Stream s_a, s_b;                   // the two internal streams, with ev_fork / ev_a / ev_b one all-or-nothing group (ensure_streams)
     Event ev_fork, ev_a, ev_b;
     // xfr_triplet_contrastive_u8_host: the engine's own copy stream and one uint8 staging buffer per forward slot -- fresh inputs keep the cross-call overlap
     Stream s_copy;
     Event ev_copied[3], ev_stage_a[3], ev_stage_b[3];
+    hipEvent_t last_copied = nullptr;  // xfr_engine_wait_inputs_copied
     Event ev_slot_done[3];             // cross-step pipelining, with seedbuf[] below
     Event ev_tab;                      // the last host-to-device table copy (subtree scratch)
     std::unique_ptr<PhaseStreams> ph_streams;      // built at the first sweep through a strided KxK layer (backward.hip)
-    bool overlap_phases = true;        // the phases of one layer run side by side (they write disjoint pixels); profiled runs keep them in a row
-    bool depthwise_valu = true;        // depthwise launches on the vector-ALU kernel (conv_depthwise.hip, configuration 14); fusion-mask bit 10 keeps them on 13
     std::vector<std::pair<Event, Event>> ev_pool;      // profiling: one pair per GEMM launch of a run
-    // parameters
-    DevBuf<float> arena;
-    size_t arena_floats = 0;
+    // ---- buffers
+    DevBuf<float> arena;               // parameters
     bool weights_loaded = false;
-    // workspace
     DevBuf<float> fwd_ws[3];           // [0]: the whole workspace (forward slot 0, gradients, scratch); [1], [2]: the forward regions of pipeline slots 1 and 2
     DevBuf<float>& ws = fwd_ws[0];
-    size_t ws_floats = 0;
     DevBuf<uint8_t> fwd_idx[3];        // max-pool argmax bytes, per forward slot
-    size_t idx_bytes = 0;
-    size_t x_off = 0, seed_off = 0, tap_off = 0, pooled_off = 0, blur_a_off = 0, blur_b_off = 0, misc_off = 0, thr_off = 0;
     DevBuf<double> dbl_ws;         // sums [2*maxB] + trace
-    size_t trace_cap = 0;          // firings capacity
     DevBuf<char> trunc_ws;
-    // mode
-    int mode = XFR_MODE_AFFINEONLY_WITH_PRIOR;
-    float eps = 1e-16f;
-    int with_bias = 0;
-    bool need_dirty = true;
-    // plans
-    std::deque<BwdPlan> plans;         // deque: get_plan() hands out pointers that must survive later insertions
-    // trace / profile
-    int trace_on = 0;
-    // per-call context of the backward sweep ("next" rows: layerwise / weighted-subtree EBP)
-    // xfr_engine_hold_forward: the forward state of (held_x, held_B, held_last) is still in slot 0
-    bool hold_forward = false, held_pos = false;
-    const float* held_x = nullptr;
-    int held_B = 0, held_last = -1;
-    hipStream_t held_stream = nullptr;
-    bool lazy_zero = false;                           // prefix sweeps: run_backward zeroes un-written gradient rows on demand (xfr_layerwise_ebp)
-    std::vector<int> rc_active;                       // layerwise sweeps in ascending firing order: stream j (all its samples) is identically zero before firing rc_active[j]
-    int rc_n = 1;                                     // samples per stream of the current layerwise batch
-    size_t g_begin = 0, g_end = 0;                    // the gradient region of the workspace (floats)
-    // priors / captures of the current sweep: tables [n_firings][tab_sb] over the gradient rows sb (stream * n + sample),
-    // staged in pinned host memory and copied once per call (common.h: EwStep::prior_elem / cap_elem)
-    bool rc_priors = false, rc_caps = false;
-    int tab_sb = 0;                                   // row length of the tables of the current call
-    std::vector<char> rc_prior_row, rc_cap_row;       // per firing: does the row hold any entry?
-    int rc_dense_slot = -1;                           // firing that carries the dense prior (-1: none)
-    const float* rc_prior_dense = nullptr;            // dense prior tensor (single sweep of one image)
-    // the subtree scratch, one all-or-nothing group with ev_tab (ensure_subtree_scratch); cap_dev stands for it
+    DevBuf<float> ws_enc;          // second bank of true activations (T region only), allocated on first use
+    DevBuf<uint8_t> u8_stage[3];         // the staging buffers of xfr_triplet_contrastive_u8_host: with their nine events one all-or-nothing group
+    bool stage_busy[3] = {false, false, false};
+    // the subtree scratch, one all-or-nothing group with ev_tab (ensure_subtree_scratch); cap_dev stands for it.  The tables of priors / captures are
+    // staged in pinned host memory and copied once per call; the call's SweepCtx carries their device pointers to the sweep
     PinnedBuf<int> tab_elem_h;                        // prior element (or capture element) per (firing, row); -1: none
     DevBuf<int> tab_elem_d;
     PinnedBuf<float> tab_val_h;                       // prior value per (firing, row)
     DevBuf<float> tab_val_d;
     size_t tab_cap = 0;                               // entries allocated
-    DevBuf<float> cap_dev;                            // [n_firings][tab_sb] captured values
+    DevBuf<float> cap_dev;                            // [n_firings][rows] captured values
     DevBuf<float> stat_v;                             // [n_firings][max_batch]
     DevBuf<int> stat_i;
     DevBuf<char> stat_scratch;
@@ -273,9 +275,7 @@ struct xfr_engine {
     DevBuf<int> stat_f2u;
     const void* stat_plan = nullptr;
     int stat_nu = 0;
-    int store_slot = -1;                              // firing whose full P tensor is kept in store_dev
-    DevBuf<float> store_dev;
-    int store_tensor = -1, store_sb = 0;
+    DevBuf<float> store_dev;                          // the full P tensor of one firing (xfr_ebp_store_firing)
     // xfr_weighted_subtree_ebp: row-max keys of a round (device + pinned host), the round's gather pairs and the merge table (device + pinned
     // host), and the top-k store used when the caller passes no top_dev (grown on demand)
     DevBuf<unsigned> wst_key_d;                       // the round buffers: one all-or-nothing group, wst_key_d stands for it
@@ -285,15 +285,26 @@ struct xfr_engine {
     DevBuf<SubtreeSlot> wst_tab_d;                    // the merge table: a pair of one capacity
     PinnedBuf<SubtreeSlot> wst_tab_h;
     DevBuf<float> wst_store;
-    std::vector<char> is_hook_a;       // per tensor: some hook takes its a (and x) from this tensor's forward values
-    std::vector<char> fwd_done;        // per forward pass: ops whose work was folded into an earlier GEMM epilogue
-    std::vector<char> pos_done;        // ... and whose positive-pass output was produced there too
-    int fwd_last_op = 0;
     // tail-balancing scratch (conv_gemm.hip), one per stream that launches GEMMs; kernels on one stream serialise,
     // so consecutive launches share it
     struct TailWs { hipStream_t s; DevBuf<float> ws; unsigned* cnt; };
     TailWs tail_ws[8];
     int n_tail_ws = 0;
+    std::unique_ptr<ProbeSweep> sweep;      // xfr_strise_* and xfr_inpaint_*: side stream, events, input and embedding buffers, built on first use
+    std::unique_ptr<StriseState> strise;    // the families' own buffers, each built on its first call
+    std::unique_ptr<InpaintState> inpaint;
+    std::unique_ptr<MatchState> match;
+    std::unique_ptr<IntakeState> intake;
+    std::unique_ptr<FinishState> finish;
+    // ---- options set through the ABI
+    int mode = XFR_MODE_AFFINEONLY_WITH_PRIOR;
+    float eps = 1e-16f;
+    int with_bias = 0;
+    int trace_on = 0;
+    int profile_on = 0;
+    std::string profile_csv;
+    bool overlap_phases = true;        // the phases of one layer run side by side (they write disjoint pixels); profiled runs keep them in a row
+    bool depthwise_valu = true;        // depthwise launches on the vector-ALU kernel (conv_depthwise.hip, configuration 14); fusion-mask bit 10 keeps them on 13
     bool tail_balance = true;          // xfr_engine_set_tail_balance
     bool split_forward = true;         // xfr_engine_set_forward_split: forward-only batches of >= 32 images as two halves on the internal streams
     bool interpret_chains = false;     // xfr_engine_set_epilogue_fusion bit 2: fused chains run through the interpreted epilogue (tests)
@@ -308,30 +319,23 @@ struct xfr_engine {
                                        // hook chain that follows (EW_AVGUP_IN; xfr_engine_set_epilogue_fusion bit 6 clear)
     bool fuse_branch = true;           // projection-shortcut blocks: the main path's hook chain as a side branch of the Add-output GEMM's epilogue (EW_STORE actions
                                        // 1 / 2; xfr_engine_set_epilogue_fusion bit 7 clear)
-    // uint8 entry points (xfr_forward_u8 / xfr_triplet_contrastive_u8): the image pointer handed to the forward is uint8 H x W x C and the layout
-    // kernel in front of the first convolution does the reference's preprocessing arithmetic (xfr_engine_set_u8_preprocess)
-    bool u8_on = false;
-    bool u8_set = false;
-    U8Pre u8_pre;
-    bool split_any_grid = false;       // xfr_engine_set_split_gemm mode + 4: covered layers take the bf16x6 kernel whatever the launch's grid (tests, tuning)
-    int split_mask = 3;                // xfr_engine_set_split_gemm: which covered layers run the bf16x6 kernel (conv_gemm_split.hip K17) -- bit 0 the forward
-                                       // convolutions, bit 1 the sweep's backward-data GEMMs; both by default since round 6 (short in-pipe sums)
-    bool lean = true;                  // xfr_engine_set_lean: plain sweeps (no trace / prior / capture / stored firing, batch % 4 == 0) take the lean schedule
-    const BwdPlan* lean_cur = nullptr; // the plan whose lean tables the running probe forward / sweep follow (null: literal)
-    bool lean_decide = false;          // lean_prepare's dry run of the probe forward: decide per convolution, record in lean_q_run / lean_final_run
-    bool dry_run = false;              // ... which launches nothing
-    bool lean_missing_sig = false;     // ... and found a lean epilogue without a compiled signature
-    long lean_launches = 0;            // dual-accumulator launches so far (xfr_engine_lean_stats)
-    std::vector<char> lean_q_run;
-    std::vector<int> lean_final_run;
     bool pair_tiles = true;            // backward chain GEMMs over two streams walk their m-tiles stream-interleaved (xfr_engine_set_epilogue_fusion bit 5 clear)
     bool fuse_pools = true;            // Light-CNN's maxpool + avgpool pair: one forward kernel (xfr_engine_set_epilogue_fusion bit 0 switches it with the rest)
     bool fuse_gemm_epilogue = true;    // hook chains that follow a backward GEMM run in its (vector) epilogue
                                        // (both: xfr_engine_set_epilogue_fusion; DESIGN.md section 6 has the measurements)
+    bool split_any_grid = false;       // xfr_engine_set_split_gemm mode + 4: covered layers take the bf16x6 kernel whatever the launch's grid (tests, tuning)
+    int split_mask = 3;                // xfr_engine_set_split_gemm: which covered layers run the bf16x6 kernel (conv_gemm_split.hip K17) -- bit 0 the forward
+                                       // convolutions, bit 1 the sweep's backward-data GEMMs; both by default since round 6 (short in-pipe sums)
+    bool lean = true;                  // xfr_engine_set_lean: plain sweeps (no trace / prior / capture / stored firing, batch % 4 == 0) take the lean schedule
+    // uint8 entry points (xfr_forward_u8 / xfr_triplet_contrastive_u8): the image pointer handed to the forward is uint8 H x W x C and the layout
+    // kernel in front of the first convolution does the reference's preprocessing arithmetic (xfr_engine_set_u8_preprocess)
+    bool u8_set = false;
+    U8Pre u8_pre;
+    bool u8_on = false;                // (Scoped) the running call is one of them
+    bool inputs_ready = false;     // xfr_engine_set_inputs_ready: the NEXT level-2 call may read x_dev without waiting for the caller's stream (one-shot, ebp_core consumes it)
+    // ---- profiling record: what the last traced / profiled run left for the getters
     int last_trace_firings = 0, last_trace_sb = 0;
     std::vector<int> last_trace_kinds;
-    int profile_on = 0;
-    std::string profile_csv;
     std::vector<ConvParams> ev_params;
     std::vector<int> ev_cfg;           // the configuration each profiled launch really ran
     double fam_ms[2] = {0.0, 0.0}, fam_flops[2] = {0.0, 0.0};      // last profiled run, by kernel family: [0] fp32 MFMA, [1] bf16x6
@@ -341,33 +345,33 @@ struct xfr_engine {
     double last_gemm_ms = 0.0;
     long last_gemm_launches = 0;
     double last_gemm_flops = 0.0;
-
-    std::unique_ptr<ProbeSweep> sweep;      // xfr_strise_* and xfr_inpaint_*: side stream, events, input and embedding buffers, built on first use
-    std::unique_ptr<StriseState> strise;    // the families' own buffers, each built on its first call
-    std::unique_ptr<InpaintState> inpaint;
-    std::unique_ptr<MatchState> match;
-    std::unique_ptr<IntakeState> intake;
-    std::unique_ptr<FinishState> finish;
-
-    float* t_bank = nullptr;       // when set, true activations live in this bank (gallery forward of a triplet step)
-    DevBuf<float> ws_enc;          // second bank of true activations (T region only), allocated on first use
-    size_t t_region_floats = 0;
-    DevBuf<uint8_t> u8_stage[3];         // the staging buffers of xfr_triplet_contrastive_u8_host: with their nine events one all-or-nothing group
-    bool stage_busy[3] = {false, false, false};
-    hipEvent_t inputs_event = nullptr;   // one-shot, set by the _host entry point: the inputs of THIS call are complete when it fires (instead of the caller's stream order)
-    int stage_slot = -1;                 // ... and the staging slot its forwards read
-    hipEvent_t last_copied = nullptr;    // xfr_engine_wait_inputs_copied
-    // cross-step pipelining (xfr_engine_set_pipeline): two forward slots (T, Pv, norms, argmax) so that the forward of
+    // ---- pipeline slots: cross-step pipelining (xfr_engine_set_pipeline) -- two forward slots (T, Pv, norms, argmax) so that the forward of
     // triplet call i+1 may run while the backward sweep of call i still reads slot i%2
     bool pipeline = false;
-    bool pipeline_all = false;     // level 2: xfr_ebp / xfr_contrastive calls are pipelined too
-    bool inputs_ready = false;     // xfr_engine_set_inputs_ready: the NEXT level-2 call may read x_dev without waiting for the caller's stream (one-shot)
-    int cur_slot = 0;
-    long seq = 0;
+    bool pipeline_all = false;     // level 2: xfr_ebp / xfr_contrastive calls are pipelined too ((Scoped) off around the image hook's sweep)
     int n_slots = 2;               // xfr_engine_set_pipeline bit 2: three forward slots (the forwards may run two calls ahead of the sweep)
-    size_t fwd_region_floats = 0;
+    long seq = 0;
     DevBuf<float> seedbuf[3];
     bool slot_pending[3] = {false, false, false};
+    int cur_slot = 0;              // (Scoped) the slot the running call's forward writes and its sweep reads; 0 between calls
+    float* t_bank = nullptr;       // (Scoped) when set, true activations live in this bank (gallery forward of a triplet step)
+    // ---- held forward.  xfr_engine_hold_forward: the forward state of (held_x, held_B, held_last) is still in slot 0
+    bool hold_forward = false, held_pos = false;
+    const float* held_x = nullptr;
+    int held_B = 0, held_last = -1;
+    hipStream_t held_stream = nullptr;
+    std::vector<char> fwd_done;        // per forward pass: ops whose work was folded into an earlier GEMM epilogue
+    std::vector<char> pos_done;        // ... and whose positive-pass output was produced there too
+    int fwd_last_op = 0;
+    // ---- lean run state
+    const BwdPlan* lean_cur = nullptr; // (Scoped) the plan whose lean tables the running probe forward / sweep follow (null: literal)
+    bool lean_decide = false;          // (Scoped) lean_prepare's dry run of the probe forward: decide per convolution, record in lean_q_run / lean_final_run
+    bool dry_run = false;              // (Scoped) ... which launches nothing
+    bool lean_missing_sig = false;     // ... and found a lean epilogue without a compiled signature
+    long lean_launches = 0;            // dual-accumulator launches so far (xfr_engine_lean_stats)
+    std::vector<char> lean_q_run;
+    std::vector<int> lean_final_run;
+
     float* fwd_base() { return fwd_ws[cur_slot]; }
     uint8_t* idx_base() { return fwd_idx[cur_slot]; }
     float* T(int t) { const Tensor& x = tens[t]; return (t_bank ? t_bank : fwd_base()) + tens[x.alias >= 0 ? root(t) : t].t_off; }
@@ -376,6 +380,17 @@ struct xfr_engine {
     float* G(int t) { return ws + tens[t].g_off; }
     int root(int t) const { while (tens[t].alias >= 0) t = tens[t].alias; return t; }
     size_t max_per_n() const { size_t m = 0; for (const Tensor& x : tens) m = std::max(m, (size_t)x.per_n()); return m; }      // elements per sample of the largest tensor
+};
+
+// xfr_weighted_subtree_ebp holds one forward for all its phases: the caller's hold (an enclosing group) survives the call, ours ends with it -- and
+// drops the held forward, which a plain Scoped<bool> would not
+struct HoldGuard {
+    xfr_engine* e;
+    const bool prev;
+    explicit HoldGuard(xfr_engine* e_) : e(e_), prev(e_->hold_forward) { if (!prev) { e->hold_forward = true; e->held_x = nullptr; } }
+    ~HoldGuard() { if (!prev) { e->hold_forward = false; e->held_x = nullptr; } }
+    HoldGuard(const HoldGuard&) = delete;
+    HoldGuard& operator=(const HoldGuard&) = delete;
 };
 
 namespace xfr {
@@ -406,17 +421,17 @@ bool fuse_mfm_forward(xfr_engine* e, int k, int B, bool keep_raw, ConvParams& p,
 // keep_raw: no positive pass, but a plain-weight backward pass follows (xfr_subtree_weights): the MaxFeatureMap forwards still store the raw halves its VJP reads
 xfr_status forward_all(xfr_engine* e, const float* x_dev, int B, int last_tensor, bool with_pos, hipStream_t s, bool keep_raw = false);
 void lean_prepare(xfr_engine* e, BwdPlan& plan, int B);
-bool lean_applies(xfr_engine* e, BwdPlan& plan, int B);
+bool lean_applies(xfr_engine* e, BwdPlan& plan, int B, const SweepCtx& cx);
 
 // backward.hip
-void resolve_chain(xfr_engine* e, const std::vector<BwdStep::Sym>& syms, EwChain& ch, double* trace, int SB, bool plain = false);
-xfr_status run_backward(xfr_engine* e, BwdPlan& plan, int B, int S, hipStream_t s);
-bool bwd_conv_params(xfr_engine* e, const BwdPlan& plan, const BwdStep& st, int B, int SB, int SBa, ConvParams& p, const PhaseRec* ph = nullptr);
+void resolve_chain(xfr_engine* e, const SweepCtx& cx, const std::vector<BwdStep::Sym>& syms, EwChain& ch, double* trace, int SB, bool plain = false);
+xfr_status run_backward(xfr_engine* e, const SweepCtx& cx, BwdPlan& plan, int B, int S, hipStream_t s);
+bool bwd_conv_params(xfr_engine* e, const SweepCtx& cx, const BwdPlan& plan, const BwdStep& st, int B, int SB, int SBa, ConvParams& p, const PhaseRec* ph = nullptr);
 
 // engine.hip
 xfr_status check_run(xfr_engine* e, const void* x, int n);
 xfr_status fence_slot0(xfr_engine* e, hipStream_t s);
-xfr_status ebp_core(xfr_engine* e, const float* x_dev, int n, int S, int seed_tensor, const float* seed_dev, hipStream_t s);
+xfr_status ebp_core(xfr_engine* e, const SweepCtx& cx, const float* x_dev, int n, int S, int seed_tensor, const float* seed_dev, hipStream_t s);
 xfr_status require_u8(xfr_engine* e);                                       // precondition of every uint8 entry point
 
 // weights.hip

@@ -623,19 +623,18 @@ void lean_prepare(xfr_engine* e, BwdPlan& plan, int B)
     // dry run of the probe forward: the same decisions the real one takes, nothing launched
     e->lean_q_run.assign(nt, 0);
     e->lean_final_run.assign(nt, -1);
-    e->lean_decide = true;
-    e->dry_run = true;
     e->lean_missing_sig = false;
     e->fwd_done.assign(e->ops.size(), 0);
     e->pos_done.assign(e->ops.size(), 0);
     e->fwd_last_op = last_op;
-    for (int k = 0; k <= last_op; ++k) {
-        const int kind = e->ops[k].d.kind;
-        if (e->fwd_done[k] || (kind != XFR_OP_CONV && kind != XFR_OP_LINEAR)) continue;
-        if (fwd_op(e, k, B, true, nullptr) != XFR_OK) e->lean_missing_sig = true;
+    {
+        Scoped<bool> decide(e->lean_decide, true), dry(e->dry_run, true);
+        for (int k = 0; k <= last_op; ++k) {
+            const int kind = e->ops[k].d.kind;
+            if (e->fwd_done[k] || (kind != XFR_OP_CONV && kind != XFR_OP_LINEAR)) continue;
+            if (fwd_op(e, k, B, true, nullptr) != XFR_OK) e->lean_missing_sig = true;
+        }
     }
-    e->lean_decide = false;
-    e->dry_run = false;
     bool any = false;
     for (int t = 0; t < nt; ++t) any = any || e->lean_q_run[t] == 1;
     if (!any || e->lean_missing_sig) return;
@@ -643,9 +642,9 @@ void lean_prepare(xfr_engine* e, BwdPlan& plan, int B)
 }
 
 // may this call take the lean schedule?  (B % 4: every lean epilogue is a float4 epilogue)
-bool lean_applies(xfr_engine* e, BwdPlan& plan, int B)
+bool lean_applies(xfr_engine* e, BwdPlan& plan, int B, const SweepCtx& cx)
 {
-    if (!e->lean || (B & 3) != 0 || e->trace_on || e->rc_priors || e->rc_caps || e->store_slot >= 0 || e->hold_forward || plan.plain) return false;
+    if (!e->lean || (B & 3) != 0 || e->trace_on || cx.observing() || e->hold_forward || plan.plain) return false;
     if (!e->fuse_probe_fwd || !e->fuse_gemm_epilogue || e->interpret_chains) return false;
     lean_prepare(e, plan, B);
     return plan.lean_state == 1;

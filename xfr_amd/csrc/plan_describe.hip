@@ -102,6 +102,7 @@ xfr_status xfr_plan_describe(const xfr_op_desc* ops, int32_t n_ops, int32_t n_we
     // A schedule, one line per step.  SCHED_FULL: every step with its shape; SCHED_OBSERVED: only the GEMMs that carry a chain; SCHED_LEAN: only the steps
     // that carry a chain.
     enum SchedStyle { SCHED_FULL, SCHED_OBSERVED, SCHED_LEAN };
+    const SweepCtx plain;      // the plain sweep: what is described observes nothing
     static const char* kn[] = {"EW", "CONV_BWD", "MAXPOOL_BWD", "AVGPOOL_BWD", "COPY", "MAXHALVES_BWD", "NORMALIZE_BWD", "ZERO"};
     auto print_schedule = [&](const char* prefix, const std::vector<BwdStep>& steps, SchedStyle style) {
         for (const BwdStep& b : steps) {
@@ -118,7 +119,7 @@ xfr_status xfr_plan_describe(const xfr_op_desc* ops, int32_t n_ops, int32_t n_we
                     // (M 0: the layer runs by phases, whose PHASE lines below carry their own M)
                     const OpRec& go = e->ops[b.op];
                     ConvParams gp;
-                    const bool one = go.phases.empty() && bwd_conv_params(e, *plan, b, batch, 2 * batch, 2 * batch, gp);
+                    const bool one = go.phases.empty() && bwd_conv_params(e, plain, *plan, b, batch, 2 * batch, 2 * batch, gp);
                     snprintf(line, sizeof(line), " groups %d Ci %d Co %d M %d cfg %d", go.groups, go.d.cout / go.groups, go.Cin / go.groups, one ? gp.M : 0, CFG_GROUP);
                     out += line;
                 }
@@ -126,7 +127,7 @@ xfr_status xfr_plan_describe(const xfr_op_desc* ops, int32_t n_ops, int32_t n_we
             if (!b.chain.empty()) {
                 EwChain ch;
                 EwLoads ld;
-                resolve_chain(e, b.chain, ch, nullptr, 2 * batch);
+                resolve_chain(e, plain, b.chain, ch, nullptr, 2 * batch);
                 ew_plan_loads(ch, e->G(b.dst_t), ld, b.kind == ST_CONV_BWD ? EW_FWD_SLOTS_WIDE : EW_FWD_SLOTS_BASE);
                 if (b.kind == ST_CONV_BWD) emit_sig(ch);
                 else { snprintf(line, sizeof(line), " steps %d", ch.n); out += line; }
@@ -140,7 +141,7 @@ xfr_status xfr_plan_describe(const xfr_op_desc* ops, int32_t n_ops, int32_t n_we
             if (style == SCHED_FULL && b.kind == ST_CONV_BWD)
                 for (const PhaseRec& ph : e->ops[b.op].phases) {
                     ConvParams p;
-                    if (!bwd_conv_params(e, *plan, b, batch, 2 * batch, 2 * batch, p, &ph)) continue;
+                    if (!bwd_conv_params(e, plain, *plan, b, batch, 2 * batch, 2 * batch, p, &ph)) continue;
                     const int G = e->ops[b.op].groups;
                     snprintf(line, sizeof(line), "%s PHASE op %d (%d,%d) kernel %dx%d cfg %d K %d M %d origin (%d,%d) grid %d x %d", prefix, b.op, ph.r, ph.c,
                              ph.ka, ph.kb, G > 1 ? (int)CFG_GROUP : conv_gemm_pick_cfg(p), p.K, p.M, ph.ih0, ph.iw0, ph.nq, ph.nu);
@@ -161,9 +162,8 @@ xfr_status xfr_plan_describe(const xfr_op_desc* ops, int32_t n_ops, int32_t n_we
     // the lean schedule of the same plan (xfr_engine_set_lean): probe-forward epilogues over two accumulator tiles, sweep chains on stored quotients
     lean_prepare(e, *plan, batch);
     if (plan->lean_state == 1) {
-        e->lean_cur = plan;
-        const int n_lean = fwd_sigs(FWD_LEAN);
-        e->lean_cur = nullptr;
+        int n_lean = 0;
+        { Scoped<const BwdPlan*> lean_cur(e->lean_cur, plan); n_lean = fwd_sigs(FWD_LEAN); }
         print_schedule("lean-bwd", plan->fused_gemm_lean, SCHED_LEAN);
         snprintf(line, sizeof(line), "lean convolutions %d\n", n_lean);
         out += line;

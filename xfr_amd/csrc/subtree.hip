@@ -53,8 +53,7 @@ xfr_status xfr_subtree_weights(xfr_engine* e, const float* x_dev, int32_t n, int
     if (st != XFR_OK) return st;
     const Tensor& sd = e->tens[seed_tensor];
     launch_seed_to_cnhw(seed_dev, e->G(seed_tensor), 2 * n, sd.C, sd.HW(), s);
-    e->rc_priors = e->rc_caps = false; e->store_slot = -1;
-    st = run_backward(e, *plan, n, 2, s);
+    st = run_backward(e, SweepCtx(), *plan, n, 2, s);
     if (st != XFR_OK) return st;
     if (e->stat_plan != plan) {       // descriptor table of this plan: one entry per distinct gradient tensor
         std::vector<StatDesc> desc;
@@ -79,20 +78,21 @@ xfr_status xfr_subtree_weights(xfr_engine* e, const float* x_dev, int32_t n, int
     return XFR_OK;
 }
 
-// stage the element / value tables of a call: the pinned host copies may only be rewritten once the previous call's
-// host-to-device copy has completed
-static xfr_status tables_begin(xfr_engine* e, int nf, int rows)
+// stage the element / value tables of a call, whose sweep finds them through cx: the pinned host copies may only be rewritten once the previous
+// call's host-to-device copy has completed
+static xfr_status tables_begin(xfr_engine* e, SweepCtx& cx, int nf, int rows)
 {
     if ((size_t)nf * rows > e->tab_cap) return fail(XFR_INVALID_ARG, "%d firings x %d gradient rows exceed the table scratch", nf, rows);
     HIP_TRY(hipEventSynchronize(e->ev_tab));
-    e->tab_sb = rows;
+    cx.tab_sb = rows;
+    cx.tab_elem = e->tab_elem_d; cx.tab_val = e->tab_val_d; cx.cap_dst = e->cap_dev;
     for (size_t i = 0; i < (size_t)nf * rows; ++i) { e->tab_elem_h[i] = -1; e->tab_val_h[i] = 0.f; }
     return XFR_OK;
 }
 
-static xfr_status tables_commit(xfr_engine* e, int nf, bool with_vals, hipStream_t s)
+static xfr_status tables_commit(xfr_engine* e, const SweepCtx& cx, int nf, bool with_vals, hipStream_t s)
 {
-    const size_t n = (size_t)nf * e->tab_sb;
+    const size_t n = (size_t)nf * cx.tab_sb;
     HIP_TRY(hipMemcpyAsync(e->tab_elem_d, e->tab_elem_h, n * sizeof(int), hipMemcpyHostToDevice, s));
     if (with_vals) HIP_TRY(hipMemcpyAsync(e->tab_val_d, e->tab_val_h, n * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(e->ev_tab, s));
@@ -112,23 +112,22 @@ xfr_status xfr_ebp_capture(xfr_engine* e, const float* x_dev, int32_t n, int32_t
     st = get_plan(e, seed_tensor, &plan);
     if (st != XFR_OK) return st;
     if (n_firings != plan->n_firings) return fail(XFR_INVALID_ARG, "expected %d firings, got %d", plan->n_firings, n_firings);
-    st = tables_begin(e, n_firings, n);
+    SweepCtx cx;
+    st = tables_begin(e, cx, n_firings, n);
     if (st != XFR_OK) return st;
-    e->rc_priors = false; e->store_slot = -1;
-    e->rc_cap_row.assign(n_firings, 0);
+    cx.cap_row.assign(n_firings, 0);
     for (int f = 0; f < n_firings; ++f) {
         const Tensor& x = e->tens[plan->firing_tensor[f]];
         for (int b = 0; b < n; ++b) {
             const int el = elem_host[(size_t)f * n + b];
-            if (el >= 0 && el < x.per_n()) { e->tab_elem_h[(size_t)f * n + b] = el; e->rc_cap_row[f] = 1; }
+            if (el >= 0 && el < x.per_n()) { e->tab_elem_h[(size_t)f * n + b] = el; cx.cap_row[f] = 1; }
         }
     }
-    st = tables_commit(e, n_firings, false, s);
+    st = tables_commit(e, cx, n_firings, false, s);
     if (st != XFR_OK) return st;
     HIP_TRY(hipMemsetAsync(e->cap_dev, 0, (size_t)n_firings * n * sizeof(float), s));
-    e->rc_caps = true;
-    st = ebp_core(e, x_dev, n, 1, seed_tensor, seed_dev, s);
-    e->rc_caps = false;
+    cx.caps = true;
+    st = ebp_core(e, cx, x_dev, n, 1, seed_tensor, seed_dev, s);
     if (st != XFR_OK) return st;
     HIP_TRY(hipMemcpyAsync(p_host, e->cap_dev, (size_t)n_firings * n * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -158,68 +157,60 @@ static xfr_status layerwise_run(xfr_engine* e, const float* x_dev, int32_t n, in
     for (long r = 0; r < rows; ++r)
         if (firing_host[r] >= nf || (firing_host[r] < 0 && dense_prior_dev))
             return fail(XFR_INVALID_ARG, "firing %d outside [0, %d)", firing_host[r], nf);
-    st = tables_begin(e, nf, (int)rows);
+    SweepCtx cx;
+    st = tables_begin(e, cx, nf, (int)rows);
     if (st != XFR_OK) return st;
-    e->rc_caps = false; e->store_slot = -1;
-    e->rc_prior_row.assign(nf, 0);
-    e->rc_dense_slot = -1;
-    e->rc_prior_dense = dense_prior_dev;
+    cx.priors = true;
+    cx.prior_row.assign(nf, 0);
+    cx.prior_dense = dense_prior_dev;
     if (dense_prior_dev) {
-        e->rc_dense_slot = firing_host[0];
+        cx.dense_slot = firing_host[0];
     } else {
         for (long r = 0; r < rows; ++r) {          // row r = sweep j * n + image b; firing < 0: an idle row (stays zero)
             const int f = firing_host[r];
             if (f < 0) continue;
             e->tab_elem_h[(size_t)f * rows + r] = elem_host[r];
             e->tab_val_h[(size_t)f * rows + r] = val_host[r];
-            e->rc_prior_row[f] = 1;
+            cx.prior_row[f] = 1;
         }
-        st = tables_commit(e, nf, true, s);
+        st = tables_commit(e, cx, nf, true, s);
         if (st != XFR_OK) return st;
     }
     // Sweeps handed over in ascending firing order (per image): sweep j -- identically zero above the earliest of its n priors --
     // only joins the GEMMs and hook chains from the step that holds that prior hook (run_backward: the launches cover a prefix
     // of the gradient rows)
-    e->rc_active.clear();
-    e->rc_n = n;
+    cx.n = n;
     std::vector<int> first(n_sweeps, nf);
     for (int j = 0; j < n_sweeps; ++j)
         for (int b = 0; b < n; ++b) { const int f = firing_host[(size_t)j * n + b]; if (f >= 0) first[j] = std::min(first[j], f); }
     bool ascending = n_sweeps > 1;
     for (int j = 1; j < n_sweeps; ++j) ascending = ascending && first[j] >= first[j - 1];
-    if (ascending && !e->trace_on) e->rc_active = first;
+    if (ascending && !e->trace_on) cx.active = first;
     // A sweep that is idle for every image (first[j] == nf) never joins the prefix launches, so nothing would write its rows of P[-2]: they are zeroed
     // below, before the sweep (the launches that honour the prefix leave them alone, those that walk every row write the zeros the on-demand zeroing feeds them)
     int live_sweeps = n_sweeps;
     while (live_sweeps > 0 && first[live_sweeps - 1] >= nf) --live_sweeps;
     // one forward for all sweeps (whitebox.py:581 runs ebp(img, 0*P0) again for every layer); zero seeds: all the
     // gradient enters through the priors
-    e->rc_priors = true;
     st = forward_all(e, x_dev, n, seed_tensor, true, s);
-    if (st == XFR_OK) {
-        const Tensor& sd = e->tens[seed_tensor];
-        // Rows of a gradient tensor that no launch has written must read as zero (a sweep joins at its own firing).  The whole gradient region
-        // used to be zero-filled here -- 30 GB at 256 rows, a third of a round; now run_backward zeroes exactly the rows a launch is about to
-        // read and nobody has written (XFR_EAGER_ZERO=1: the old fill, for A/B runs; XFR_POISON_G=1, tests: NaN-fill first, so that a row the
-        // bookkeeping misses shows up in the maps)
-        static const bool eager = getenv("XFR_EAGER_ZERO") != nullptr, poison = getenv("XFR_POISON_G") != nullptr;
-        e->lazy_zero = !e->rc_active.empty() && !eager;
-        if (!e->rc_active.empty() && (eager || poison))
-            HIP_TRY(hipMemsetAsync(e->ws + e->g_begin, eager ? 0 : 0xFF, (e->g_end - e->g_begin) * sizeof(float), s));
-        launch_fill(e->G(seed_tensor), (long)sd.per_n() * rows, 0.f, s);
-        if (!e->rc_active.empty() && live_sweeps < n_sweeps) {
-            const Tensor& tp = e->tens[1];
-            const size_t hw = (size_t)tp.HW();
-            (void)hipMemset2DAsync(e->ws + e->tap_off + (size_t)live_sweeps * n * hw, (size_t)rows * hw * sizeof(float), 0,
-                                   (size_t)(n_sweeps - live_sweeps) * n * hw * sizeof(float), (size_t)tp.C, s);
-        }
-        st = run_backward(e, *plan, n, n_sweeps, s);
+    if (st != XFR_OK) return st;
+    const Tensor& sd = e->tens[seed_tensor];
+    // Rows of a gradient tensor that no launch has written must read as zero (a sweep joins at its own firing).  The whole gradient region
+    // used to be zero-filled here -- 30 GB at 256 rows, a third of a round; now run_backward zeroes exactly the rows a launch is about to
+    // read and nobody has written (XFR_EAGER_ZERO=1: the old fill, for A/B runs; XFR_POISON_G=1, tests: NaN-fill first, so that a row the
+    // bookkeeping misses shows up in the maps)
+    static const bool eager = getenv("XFR_EAGER_ZERO") != nullptr, poison = getenv("XFR_POISON_G") != nullptr;
+    cx.lazy_zero = !cx.active.empty() && !eager;
+    if (!cx.active.empty() && (eager || poison))
+        HIP_TRY(hipMemsetAsync(e->ws + e->g_begin, eager ? 0 : 0xFF, (e->g_end - e->g_begin) * sizeof(float), s));
+    launch_fill(e->G(seed_tensor), (long)sd.per_n() * rows, 0.f, s);
+    if (!cx.active.empty() && live_sweeps < n_sweeps) {
+        const Tensor& tp = e->tens[1];
+        const size_t hw = (size_t)tp.HW();
+        (void)hipMemset2DAsync(e->ws + e->tap_off + (size_t)live_sweeps * n * hw, (size_t)rows * hw * sizeof(float), 0,
+                               (size_t)(n_sweeps - live_sweeps) * n * hw * sizeof(float), (size_t)tp.C, s);
     }
-    e->rc_active.clear();
-    e->lazy_zero = false;
-    e->rc_priors = false;
-    e->rc_prior_dense = nullptr;
-    e->rc_dense_slot = -1;
+    st = run_backward(e, cx, *plan, n, n_sweeps, s);
     if (st != XFR_OK) return st;
     const Tensor& t1 = e->tens[1];
     if (rowmax_key)
@@ -310,12 +301,7 @@ xfr_status xfr_weighted_subtree_ebp(xfr_engine* e, const float* x_dev, int32_t n
     float* store = top_dev ? top_dev : e->wst_store;
 
     // 1. one forward for every phase; the caller's hold (an enclosing group) survives the call, ours ends with it
-    struct HoldGuard {
-        xfr_engine* e;
-        bool prev;
-        ~HoldGuard() { if (!prev) { e->hold_forward = false; e->held_x = nullptr; } }
-    } hold{e, e->hold_forward};
-    if (!hold.prev) { e->hold_forward = true; e->held_x = nullptr; }
+    HoldGuard hold(e);
 
     // 2-3. layer weights, chosen elements and prior values
     std::vector<float> w((size_t)nf * n), vals((size_t)nf * n);
@@ -499,14 +485,11 @@ xfr_status xfr_ebp_store_firing(xfr_engine* e, const float* x_dev, int32_t n, in
         if (h) *h = e->in_h;
         if (w) *w = e->in_w;
         if (!out_dev) return XFR_OK;
-        e->rc_priors = e->rc_caps = false;
-        e->store_slot = -1;
         {
             // un-pipelined on purpose: the gather below reads the image from forward slot 0 on the caller's stream; a pipelined call would have
             // put it into slot seq % n_slots on an internal stream (and ebp_core resets cur_slot before it returns)
-            struct Unpipe { xfr_engine* e; bool was; ~Unpipe() { e->pipeline_all = was; } } unpipe{e, e->pipeline_all};
-            e->pipeline_all = false;
-            st = ebp_core(e, x_dev, n, 1, seed_tensor, seed_dev, s);
+            Scoped<bool> unpipe(e->pipeline_all, false);
+            st = ebp_core(e, SweepCtx(), x_dev, n, 1, seed_tensor, seed_dev, s);
         }
         if (st != XFR_OK) return st;
         const OpRec& o = e->ops[0];
@@ -522,11 +505,10 @@ xfr_status xfr_ebp_store_firing(xfr_engine* e, const float* x_dev, int32_t n, in
     if (h) *h = x.H;
     if (w) *w = x.W;
     if (!out_dev) return XFR_OK;          // shape query
-    e->rc_priors = e->rc_caps = false;
     const bool is_tap = (firing == plan->n_firings - 1);
-    e->store_slot = is_tap ? -1 : firing;
-    st = ebp_core(e, x_dev, n, 1, seed_tensor, seed_dev, s);
-    e->store_slot = -1;
+    SweepCtx cx;
+    if (!is_tap) { cx.store_slot = firing; cx.store_dst = e->store_dev; }
+    st = ebp_core(e, cx, x_dev, n, 1, seed_tensor, seed_dev, s);
     if (st != XFR_OK) return st;
     launch_cnhw_to_nchw(is_tap ? e->ws + e->tap_off : e->store_dev, out_dev, n, x.C, x.HW(), s);
     HIP_TRY(hipGetLastError());
